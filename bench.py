@@ -12,6 +12,8 @@ kernel and the reference's CPU path timed beside it.
                                         of the north star sharded the same way (`strong_scaling_512`), and the one gather
                                         of the slabs on rank 0 (`gather`)
   python bench.py --workload turb7      one of the other workloads as the timed workload, same evidence
+  python bench.py --dump-outputs DIR    also write what the last timed step computed to DIR (inputs are seeded: two builds
+                                        run with the same arguments can be compared output for output)
 
 `--gpus N` works both ways: started plainly it launches its N ranks itself (fresh children under
 torch.distributed.run, before this process touches a GPU) and returns their exit code; started BY
@@ -77,7 +79,40 @@ def parse(argv=None):
                          "default so that a rocprofv3 trace of this command holds only the contract's launches)")
     ap.add_argument("--print-launch", action="store_true",
                     help="print the command --gpus N would start and exit (no GPU is touched)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<workload>.npy (float32); an output "
+                         "above 64 MB is written as a fixed seeded sample of its elements, their flat indices beside it in "
+                         "DIR/<workload>_index.npy (float64).  N > 1: one pair per rank, suffixed _rank<r>")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
+
+
+# ---- --dump-outputs ----------------------------------------------------------------------------------
+DUMP_BYTES = 64 << 20      # all files of one run together
+DUMP_SAMPLE = 1 << 22      # elements kept of a larger output: 16 MB of values + 32 MB of indices
+DUMP_SEED = 20251015
+
+
+def dump_outputs(directory, name, t, rank=0, world=1):
+    """Writes the device tensor `t` (what a caller of the timed path receives) to directory/<name>.npy as float32.  When
+    the world's outputs would exceed DUMP_BYTES, a fixed seeded sample of each rank's elements is written instead (the
+    same elements every run), with their flat indices into `t` in <name>_index.npy as float64."""
+    os.makedirs(directory, exist_ok=True)
+    if world > 1:
+        name = f"{name}_rank{rank}"
+    flat = t.reshape(-1)
+    if flat.numel() * 4 * world <= DUMP_BYTES:
+        np.save(os.path.join(directory, f"{name}.npy"), t.float().cpu().numpy())
+        return
+    k = DUMP_SAMPLE // world
+    idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, flat.numel(), k, dtype=np.int64))
+    vals = flat[torch.from_numpy(idx).to(flat.device)].float().cpu().numpy()
+    np.save(os.path.join(directory, f"{name}.npy"), vals)
+    np.save(os.path.join(directory, f"{name}_index.npy"), idx.astype(np.float64))
 
 
 # ---- self-launch ---------------------------------------------------------------------------------
@@ -477,6 +512,9 @@ def main():
         s = torch.tensor([samples_per_rank], dtype=torch.float64, device=red_device)
         dist.all_reduce(s, op=dist.ReduceOp.SUM)
         total_samples = int(s[0])
+    if args.dump_outputs:  # before anything below reuses `out`
+        result = W.out if W.tex_pts is not None else out[: samples_per_rank].view(my_planes, n, n)
+        dump_outputs(args.dump_outputs, wl, result, rank, world)
 
     # ---- the one exchange of the sharded path: collect the slabs on rank 0 (outside the timed steps) ----
     gather = None

@@ -3,7 +3,8 @@
 
 TEST INFRASTRUCTURE.  Run in the build container only (needs /root/reference):
 
-    python oracle/gen_golden.py
+    python oracle/gen_golden.py                  (everything below)
+    python oracle/gen_golden.py --live-checks    (ref_live_checks.npz alone)
 
 Writes
   tests/golden/result_raw/*.raw      the 15 float32[256*256] grids the reference commits under
@@ -13,6 +14,8 @@ Writes
   tests/golden/ref_vectors.npz       inputs + outputs of the compiled reference's own classes
                                      (seeded numpy inputs; every output is produced by calling
                                      the reference through oracle/ref_shim.cpp)
+  tests/golden/ref_live_checks.npz   the same, for the checks that otherwise call the compiled
+                                     reference live (used where oracle/_ref was never built)
 The inputs are data, not code; nothing of the reference's source text is stored.
 """
 import glob
@@ -275,7 +278,38 @@ def main():
     json.dump(art, open(os.path.join(GOLD, "artefacts.json"), "w"), indent=1, sort_keys=True)
     sz = os.path.getsize(os.path.join(GOLD, "ref_vectors.npz"))
     print(f"wrote {len(out)} arrays, ref_vectors.npz = {sz / 1024:.0f} KiB")
+    live_checks(R)
+
+
+def live_checks(R):
+    """tests/golden/ref_live_checks.npz: what the tests that call the compiled reference live ask of it, so that they
+    run where oracle/_ref/libwnref.so was never built (the inputs are stored beside the outputs)."""
+    out = {}
+    h = R.ref_wn_new(16, 5)  # the rng is a member: a second generate continues the stream (WaveletNoise.h:47)
+    R.ref_wn_generate2d(h)
+    R.ref_wn_generate3d(h)
+    c = np.zeros(R.ref_wn_coeff_count(h), np.float32)
+    R.ref_wn_coeffs(h, c)
+    out["tile3d_16_5_after_2d"] = c
+    R.ref_wn_delete(h)
+    h = R.ref_wn_new(128, 12345)
+    R.ref_wn_generate3d(h)
+    for key, seed, lim, n in (("rng3", 3, 320, 20000), ("rng7", 7, 300, 4096)):
+        pts = np.ascontiguousarray(np.random.default_rng(seed).uniform(-lim, lim, (n, 3)).astype(np.float32))
+        e = np.zeros(n, np.float32)
+        R.ref_wn_eval3d(h, pts, n, e)
+        out[f"{key}_pts"], out[f"{key}_e3d"] = pts, e
+    R.ref_wn_delete(h)
+    path = os.path.join(GOLD, "ref_live_checks.npz")
+    np.savez_compressed(path, **out)
+    print(f"wrote {len(out)} arrays, ref_live_checks.npz = {os.path.getsize(path) / 1024:.0f} KiB")
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["--live-checks"]:
+        R = oracle.ref()
+        if R is None:
+            sys.exit("oracle/_ref/libwnref.so missing (oracle/Makefile builds it from the reference's sources): cannot generate")
+        live_checks(R)
+    else:
+        main()

@@ -22,6 +22,13 @@ def gold():
 
 
 @pytest.fixture(scope="session")
+def ref_checks():
+    """The compiled reference's answers to the checks that call it live (oracle/gen_golden.py --live-checks),
+    for where oracle/_ref/libwnref.so was never built."""
+    return np.load(os.path.join(GOLD, "ref_live_checks.npz"))
+
+
+@pytest.fixture(scope="session")
 def artefacts():
     import json
     return json.load(open(os.path.join(GOLD, "artefacts.json")))

@@ -78,3 +78,45 @@ def test_cpu_baseline_evaluators_compute_the_workloads_they_are_timed_beside():
         else:
             ref = oracle.noise_texture_value(oracle.perlin_perm(5489), 1.0, bench.OCTAVE, chunk)
         assert (got.view(np.uint32) == ref.view(np.uint32)).all(), (wl, kind)
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_steps_below_one_are_refused_before_any_gpu_work():
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True,
+                         env=env, timeout=300)
+    assert out.returncode != 0 and "--steps" in out.stderr
+
+
+def test_dump_outputs_writes_the_output_or_a_fixed_sample_of_it(tmp_path, monkeypatch):
+    """--dump-outputs: an output within the budget is written whole (float32, its shape); a larger one as the same seeded
+    sample of elements every run, with their flat indices, within the budget."""
+    import numpy as np
+    import torch
+    bench = _bench_module()
+    vol = torch.arange(4 * 8 * 8, dtype=torch.float32).view(4, 8, 8) * 0.5
+    bench.dump_outputs(str(tmp_path / "a"), "wavelet3d", vol)
+    got = np.load(tmp_path / "a" / "wavelet3d.npy")
+    assert got.dtype == np.float32 and got.shape == (4, 8, 8) and (got == vol.numpy()).all()
+
+    monkeypatch.setattr(bench, "DUMP_BYTES", 1024)
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 64)
+    big = torch.arange(100_000, dtype=torch.float32) * 0.25
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), "texture_points", big)
+    vals = np.load(tmp_path / "b" / "texture_points.npy")
+    idx = np.load(tmp_path / "b" / "texture_points_index.npy")
+    assert vals.dtype == np.float32 and idx.dtype == np.float64 and 0 < len(vals) == len(idx) <= 64
+    assert (vals == big.numpy()[idx.astype(np.int64)]).all()
+    assert (np.load(tmp_path / "c" / "texture_points_index.npy") == idx).all()
+    assert (np.load(tmp_path / "c" / "texture_points.npy") == vals).all()
+    assert sum(f.stat().st_size for f in (tmp_path / "b").iterdir()) < 64 * 12 + 512
+    bench.dump_outputs(str(tmp_path / "r"), "wavelet3d", big, rank=1, world=2)
+    assert sorted(f.name for f in (tmp_path / "r").iterdir()) == ["wavelet3d_rank1.npy", "wavelet3d_rank1_index.npy"]

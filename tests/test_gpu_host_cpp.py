@@ -3,9 +3,9 @@
  * tools/gridgen               -- experient/main.cpp's role with batched launches
  * tools/scalar_api_check      -- the SCALAR members (evaluate*, noise, value): the host evaluators (default) and the
    resident scalar kernel (WN_SCALAR_ON_DEVICE=1), both against the reference's vectors and the batched kernels
- * build/linkcheck/experient_main -- the REFERENCE'S OWN experient/main.cpp compiled against this
-   repo's headers (built by `make linkcheck` in the build container; the binary travels, the
-   source does not): its 15 outputs must be byte-identical to the reference's committed raws.
+ * oracle/_ref/linkcheck/experient_main -- the REFERENCE'S OWN experient/main.cpp compiled against this
+   repo's headers (built by oracle/Makefile from the reference's sources, which the repository does not
+   store): its 15 outputs must be byte-identical to the reference's committed raws.
 """
 import hashlib
 import json
@@ -97,9 +97,9 @@ def test_scalar_members_match_reference_vectors(gold, on_device):
 
 @pytest.mark.parametrize("on_device", [False, True], ids=["host_evaluators", "resident_scalar_kernel"])
 def test_reference_experient_main_linked_against_this_library(tmp_path, shas, on_device):
-    exe = os.path.join(PKG, "build", "linkcheck", "experient_main")
+    exe = os.path.join(ROOT, "oracle", "_ref", "linkcheck", "experient_main")
     if not os.path.exists(exe):
-        pytest.skip("build/linkcheck/experient_main not built (needs /root/reference at build time)")
+        pytest.skip("oracle/_ref/linkcheck/experient_main not built (needs the reference's sources at build time)")
     out = subprocess.run([exe], cwd=tmp_path, capture_output=True, text=True, timeout=900, env=scalar_env(on_device))
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     for octave in (3, 4, 5):

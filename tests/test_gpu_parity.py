@@ -53,7 +53,7 @@ def test_tile_generation_bit_exact(wn, noise2, noise3, tile2d_128, tile3d_128, a
     assert hashlib.sha256(c3.tobytes()).hexdigest() == artefacts["tile3d_128_12345"]["sha256"]
 
 
-def test_tile_generation_small_odd_and_repeated(wn, gold, ora):
+def test_tile_generation_small_odd_and_repeated(wn, gold, ora, ref_checks):
     for n, seed, dims, key in ((8, 7, 3, "tile3d_8_7"), (16, 12345, 3, "tile3d_16_12345"),
                                (16, 99, 2, "tile2d_16_99"), (7, 3, 2, "tile2d_7odd_3"),
                                (5, 11, 3, "tile3d_5odd_11")):
@@ -61,7 +61,9 @@ def test_tile_generation_small_odd_and_repeated(wn, gold, ora):
         (w.generateNoiseTile2D if dims == 2 else w.generateNoiseTile3D)()
         assert (bits(w.getNoiseCoefficients()) == bits(gold[key])).all(), key
         assert w.getTileSize() == n + (n % 2)
-    # the rng is a member: a second generate continues the stream (WaveletNoise.h:47)
+    # the rng is a member: a second generate continues the stream (WaveletNoise.h:47); the reference live when it was
+    # built, its stored answer otherwise
+    want = ref_checks["tile3d_16_5_after_2d"]
     R = ora.ref()
     if R is not None:
         h = R.ref_wn_new(16, 5)
@@ -69,10 +71,11 @@ def test_tile_generation_small_odd_and_repeated(wn, gold, ora):
         R.ref_wn_generate3d(h)
         want = np.zeros(R.ref_wn_coeff_count(h), np.float32)
         R.ref_wn_coeffs(h, want)
-        w = wn.WaveletNoise(16, 5)
-        w.generateNoiseTile2D()
-        w.generateNoiseTile3D()
-        assert (bits(w.getNoiseCoefficients()) == bits(want)).all()
+        R.ref_wn_delete(h)
+    w = wn.WaveletNoise(16, 5)
+    w.generateNoiseTile2D()
+    w.generateNoiseTile3D()
+    assert (bits(w.getNoiseCoefficients()) == bits(want)).all()
 
 
 # ---- point lists --------------------------------------------------------------------------------------
@@ -109,20 +112,19 @@ def test_scalar_api_and_empty_tile(wn, noise3, ora, tile3d_128):
     assert noise3.evaluate3D(np.zeros((0, 3), np.float32)).numel() == 0
 
 
-def test_large_random_point_list_vs_oracle(wn, noise3, ora, tile3d_128):
-    rng = np.random.default_rng(3)
-    pts = rng.uniform(-320, 320, (20000, 3)).astype(np.float32)
+def test_large_random_point_list_vs_oracle(wn, noise3, ora, ref_checks, tile3d_128):
+    pts = ref_checks["rng3_pts"]  # default_rng(3).uniform(-320, 320, (20000, 3)) as float32
     got = host(noise3.evaluate3D(pts))
+    want = ref_checks["rng3_e3d"]  # the reference's answer, stored; live below when it was built
     R = ora.ref()
     if R is not None:
         h = R.ref_wn_new(128, 12345)
         R.ref_wn_generate3d(h)
         want = np.zeros(len(pts), np.float32)
         R.ref_wn_eval3d(h, np.ascontiguousarray(pts), len(pts), want)
-    else:
-        want = ora.evaluate3d(tile3d_128, pts[:4000])
-        got = got[:4000]
+        R.ref_wn_delete(h)
     assert (bits(got) == bits(want)).all()
+    assert (bits(got[:4000]) == bits(ora.evaluate3d(tile3d_128, pts[:4000]))).all()
 
 
 def test_long_point_lists_take_plane_ordered_chunks_bit_exact(wn, noise3, ora, tile3d_128):
