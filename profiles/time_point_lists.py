@@ -1,8 +1,7 @@
 #!/usr/bin/env python3
 """Time WaveletNoise::evaluate3D / WMultibandNoise point lists (the C ABI's wn_eval3d_points / wn_multiband3d_points) on
 three kinds of 40 M-point lists -- uniformly random in 3-D, random on an axis-aligned plane, coherent (a scanline-ordered
-sweep) -- with HIP events on the launching stream.  With a -DWN_TUNE_ENV build, WN_NO_POINT_SORT=1 selects the plain
-kernels for comparison.  Run on the GPU box:  python profiles/time_point_lists.py
+sweep) -- with HIP events on the launching stream.  Run on the GPU box:  python profiles/time_point_lists.py
 """
 import importlib
 import json
@@ -26,7 +25,7 @@ lists = {
     "coherent_sweep": np.stack([np.tile(np.linspace(-40, 40, 4000), N // 4000), np.full(N, 0.25),
                                 np.repeat(np.linspace(-40, 40, N // 4000), 4000)], 1).astype(np.float32),
 }
-out = {"points": N, "sorted_kernel": "off (WN_NO_POINT_SORT)" if os.environ.get("WN_NO_POINT_SORT") else "on", "lists": {}}
+out = {"points": N, "sorted_kernel": "on", "lists": {}}
 for name, pts in lists.items():
     dev = torch.from_numpy(pts).cuda()
     row = {}

@@ -83,6 +83,12 @@ struct GridArgs {
 
 int check_grid(const wn_grid *g, bool needs_z, GridArgs *out);
 
+// n-1 when n is a power of two (indices wrap with a mask), else -1.
+__host__ __device__ __forceinline__ int pow2_mask(int n) { return (n > 0 && (n & (n - 1)) == 0) ? n - 1 : -1; }
+
+// 1/den when den is a power of two (then i * (1/den) == i / den exactly), else 0: see lattice_coord_fast.
+inline float inv_den_of(int den) { return ((den & (den - 1)) == 0) ? 1.0f / (float)den : 0.0f; }
+
 // Per-device facts, kept in mutex-protected tables keyed by the device ordinal (a host may drive
 // several devices from several threads).
 int current_device();
@@ -137,6 +143,20 @@ __device__ __forceinline__ float lattice_coord(int i, float den, float range, fl
     c = c * post;
     return c;
 }
+
+// lattice_coord with the division replaced by an exact multiply when den is a power of two (inv_den = inv_den_of(den)).
+__device__ __forceinline__ float lattice_coord_fast(int i, float den, float inv_den, float range, float oscale,
+                                                    float post)
+{
+    const float fi = (float)i;
+    float c = ((inv_den != 0.0f) ? fi * inv_den : fi / den) * range;
+    c = c * oscale;
+    c = c * post;
+    return c;
+}
+
+// Workgroup barrier that waits for the wave's LDS accesses only: no vmcnt drain of its outstanding global loads and stores.
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // Quadratic B-spline weights (WaveletNoise.cpp:194-200).
 __device__ __forceinline__ void bspline(float p, int &mid, float &w0, float &w1, float &w2)

@@ -65,11 +65,9 @@ struct TexParams { // what wn::wavelet_texture_value reads
     float octave_mul, inv_stddev;
 };
 
-__device__ __forceinline__ int mask_of(int n) { return (n > 0 && (n & (n - 1)) == 0) ? n - 1 : -1; }
-
 __device__ double serve(const Request &r)
 {
-    const int n = r.n, nmask = mask_of(n);
+    const int n = r.n, nmask = wn::pow2_mask(n);
     switch (r.op) {
     case kOpEval3d: {
         const float *coef = reinterpret_cast<const float *>(r.ptr);
@@ -270,8 +268,6 @@ int call(int device, Request &r, double *value)
     *value = b->resp->value;
     return WN_OK;
 }
-
-inline int pow2_mask(int n) { return (n > 0 && (n & (n - 1)) == 0) ? n - 1 : -1; }
 
 } // namespace
 

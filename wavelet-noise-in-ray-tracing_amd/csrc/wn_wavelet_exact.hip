@@ -149,7 +149,7 @@ int exact_lds_try(const wn_tile *tile, const GridArgs &g, float *out_dev, hipStr
     a.coef = tile->dev;
     a.out = out_dev;
     a.n = tile->n;
-    a.nmask = (tile->n > 0 && (tile->n & (tile->n - 1)) == 0) ? tile->n - 1 : -1;
+    a.nmask = pow2_mask(tile->n);
     a.g = g;
     a.nbx = (g.nx + kEX - 1) / kEX;
     a.nby = (g.ny + kEY - 1) / kEY;

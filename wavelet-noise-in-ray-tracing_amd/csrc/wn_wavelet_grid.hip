@@ -1,25 +1,27 @@
 // wn_wavelet_grid.hip -- dense-grid wavelet noise for gfx950 (K1/K3/K3p/K5 of SURVEY.md 8).
 //
-// These kernels stand under wn_eval3d_grid / wn_multiband3d_grid (tried in this order; wn_eval3d_grid first offers
-// the lattice to the strip-march kernel of wn_wavelet_strip.hip):
+// wn_eval3d_grid offers a lattice to these kernels in this order; the first whose regime covers it takes it:
+//   1. grid3d_mbp_kernel, the plane pipeline (wn_wavelet_multiband.hip), with one band;
+//   2. grid3d_strip_kernel, the strip march (wn_wavelet_strip.hip): rows of k*256 samples, >= 0.18 planes per step;
+//   3. grid3d_sep_kernel, the brick kernel below;
+//   4. grid3d_exact_lds_kernel (wn_wavelet_exact.hip): the reference's 27-tap loop on an LDS-staged box;
+//   5. grid3d_direct_kernel: one sample per lane, gathers from the tile.
+// WN_GRID_EXACT skips 1-3.  wn_multiband3d_grid offers 1 (up to 5 bands) and 3, then 5.  Kernels 4 and 5 keep the
+// reference's loop order and unfused arithmetic: bit-identical to evaluate3D.  The others sum in their own orders (each
+// within 1e-5 of it), so which kernel serves a lattice decides its last bits.
 //
-//  * grid3d_sep_kernel<NB, XW>  (default).  A dense lattice is axis-aligned, so the 27-tap sum of
-//    WaveletNoise::evaluate3D (WaveletNoise.cpp:202-213) factors per axis:
-//        out[x,y,z] = sum_i Wx[x,i] * ( sum_j Wy[y,j] * ( sum_k Wz[z,k] * C[i,j,k] ) ).
-//    Persistent workgroups (4*XW waves) walk bricks of 256*XW x 8 x BZ samples.  Per brick the
-//    coefficient box (periodic wrap resolved) is staged through LDS, y and z are collapsed for
-//    every sample row into LDS rows R[row][i] (9 FMAs per coefficient column), then each lane
-//    produces 4 consecutive x samples per row from a 4-wide window of R with its 16 window
-//    weights held in registers, and stores one float4: every wave store is 1 KiB contiguous.
-//    Per-axis weights/mids are computed exactly as the reference does; only the order of the
-//    final sums differs (measured <= 1.5e-6 abs; tolerance 1e-5).  NB > 1 accumulates NB bands
-//    in-kernel (Cook & DeRose WMultibandNoise) with one store.
-//    Bound: HBM write stream, 4 B/sample (+ the 8 MiB tile, read ~twice, L2/MALL resident).
-//
-//  * WN_GRID_EXACT, or lattices the brick scheme does not cover (step > 1/3 cell per sample, negative steps):
-//    grid3d_exact_lds_kernel (wn_wavelet_exact.hip: the reference's 27-tap loop on an LDS-staged box) when a
-//    brick's box fits LDS, else grid3d_direct_kernel: one sample per lane, gathers from the tile.  Both keep
-//    the reference's loop order and unfused arithmetic: bit-identical to evaluate3D.
+// grid3d_sep_kernel<NB, XW>.  A dense lattice is axis-aligned, so the 27-tap sum of
+// WaveletNoise::evaluate3D (WaveletNoise.cpp:202-213) factors per axis:
+//     out[x,y,z] = sum_i Wx[x,i] * ( sum_j Wy[y,j] * ( sum_k Wz[z,k] * C[i,j,k] ) ).
+// Persistent workgroups (4*XW waves) walk bricks of 256*XW x 8 x BZ samples.  Per brick the
+// coefficient box (periodic wrap resolved) is staged through LDS, y and z are collapsed for
+// every sample row into LDS rows R[row][i] (9 FMAs per coefficient column), then each lane
+// produces 4 consecutive x samples per row from a 4-wide window of R with its 16 window
+// weights held in registers, and stores one float4: every wave store is 1 KiB contiguous.
+// Per-axis weights/mids are computed exactly as the reference does; only the order of the
+// final sums differs (measured <= 1.5e-6 abs; tolerance 1e-5).  NB > 1 accumulates NB bands
+// in-kernel (Cook & DeRose WMultibandNoise) with one store.
+// Bound: HBM write stream, 4 B/sample (+ the 8 MiB tile, read ~twice, L2/MALL resident).
 //
 // 2-D and projected grids use direct kernels (bit-identical to evaluate2D / evaluate3DProjected).
 #include "wn_internal.hpp"
@@ -27,7 +29,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
 #include <type_traits>
 
 namespace {
@@ -86,17 +87,6 @@ __host__ __device__ constexpr int box_rows_bound(int d) { return d == 0 ? 36 : (
 __host__ __device__ constexpr int box_col_groups(int d, int brick_x)
 {
     return ((brick_x / 3 >> (d > 4 ? 4 : d)) + 8 + 63) / 64;
-}
-
-// lattice_coord with the division replaced by an exact multiply when den is a power of two.
-__device__ __forceinline__ float lattice_coord_fast(int i, float den, float inv_den, float range,
-                                                    float oscale, float post)
-{
-    const float fi = (float)i;
-    float c = ((inv_den != 0.0f) ? fi * inv_den : fi / den) * range;
-    c = c * oscale;
-    c = c * post;
-    return c;
 }
 
 // Persistent workgroups: each of the gridDim.x workgroups owns a contiguous range of bricks
@@ -164,8 +154,8 @@ __global__ __launch_bounds__(256 * XW) void grid3d_sep_kernel(const SepArgs a)
 #pragma unroll
             for (int bb = 1; bb < NB; ++bb) oscale = (b == bb) ? a.band[bb].oscale : oscale;
             const float c = is_const ? g.z_const
-                                     : lattice_coord_fast(idx, den, a.inv_den, g.base_range, oscale,
-                                                          g.post_scale);
+                                     : wn::lattice_coord_fast(idx, den, a.inv_den, g.base_range, oscale,
+                                                              g.post_scale);
             int m;
             float w0, w1, w2;
             wn::bspline(c, m, w0, w1, w2);
@@ -587,8 +577,6 @@ __global__ __launch_bounds__(256) void grid3d_projected_kernel(const ProjGridArg
     }
 }
 
-inline int pow2_mask(int n) { return (n > 0 && (n & (n - 1)) == 0) ? n - 1 : -1; }
-
 inline int grid_blocks(size_t total)
 {
     size_t b = (total + 255) / 256;
@@ -616,19 +604,13 @@ bool plan_sep_bz(const wn_tile *tile, const GridArgs &g, int nbands, const float
         const double padded2 = (double)((g.nx + 511) / 512) * 512, padded1 = (double)((g.nx + 255) / 256) * 256;
         if (padded2 > 1.1 * padded1) xw = 1;
     }
-#ifdef WN_TUNE_ENV
-    if (const char *e = getenv("WN_SEP_XW")) xw = atoi(e);
-#endif
     const int kBrickX = 256 * xw;
     a->xw = xw;
     if (tile->n == 0 || nbands < 1 || nbands > kMaxBands) return false;
-    if (pow2_mask(tile->n) < 0) return false; // the brick kernel wraps with a mask: power-of-two tiles
+    if (wn::pow2_mask(tile->n) < 0) return false; // the brick kernel wraps with a mask: power-of-two tiles
     if (g.nx <= 0 || g.ny <= 0 || g.nz <= 0) return false;
     if (!g.z_const_mode && g.z0 < 0) return false; // negative plane indices: the exact kernel (bounds below assume indices >= 0)
-    int BZ = g.nz >= bz_cap ? bz_cap : ceil_pow2(g.nz); // planes per brick
-#ifdef WN_TUNE_ENV
-    if (const char *e = getenv("WN_SEP_BZ")) BZ = std::min(BZ, atoi(e));
-#endif
+    const int BZ = g.nz >= bz_cap ? bz_cap : ceil_pow2(g.nz); // planes per brick
     const int rows = kBrickY * BZ;
     const double zmax = g.z_const_mode ? 0.0 : (double)g.z0 + g.nz;
     const double imax = fmax(fmax((double)g.nx, (double)g.ny), zmax);
@@ -676,9 +658,9 @@ bool plan_sep_bz(const wn_tile *tile, const GridArgs &g, int nbands, const float
     a->nbands = nbands;
     a->coef = tile->dev;
     a->n = tile->n;
-    a->nmask = pow2_mask(tile->n);
+    a->nmask = wn::pow2_mask(tile->n);
     a->g = g;
-    a->inv_den = ((g.den & (g.den - 1)) == 0) ? 1.0f / (float)g.den : 0.0f;
+    a->inv_den = wn::inv_den_of(g.den);
     return true;
 }
 
@@ -712,9 +694,6 @@ int persistent_grid(long long items, size_t lds_bytes, int xw, int nbands)
     int kmax = (int)((160 * 1024) / (lds_bytes + 2048));
     const int wave_cap = 8 / xw; // 32 waves per CU
     kmax = kmax > wave_cap ? wave_cap : (kmax < 1 ? 1 : kmax);
-#ifdef WN_TUNE_ENV
-    if (const char *e = getenv("WN_SEP_K")) return (int)std::min<long long>(items, (long long)cus * std::min(kmax, atoi(e)));
-#endif
     if (nbands == 1) return (int)std::min<long long>(items, (long long)cus * (xw == 1 ? 2 : 1)); // 8 waves per CU either way
     int best_k = kmax;
     double best_eff = -1.0;
@@ -747,24 +726,43 @@ bool launch_sep(const SepArgs &a, size_t lds, hipStream_t s)
     return a.xw == 2 ? launch_sep2<NB, 2>(a, lds, s) : launch_sep2<NB, 1>(a, lds, s);
 }
 
-// *launched = false: the runtime refused the LDS opt-in; the caller falls back to the direct kernel.
-int run_sep(const SepArgs &a, size_t lds, hipStream_t s, bool *launched)
+// Plans and launches the brick kernel when the lattice is in its regime and the runtime grants its LDS; *launched tells the caller.
+int sep_try(const wn_tile *tile, const GridArgs &g, int nbands, const float *oscale, const float *weights, float out_div,
+            float *out_dev, hipStream_t stream, bool *launched)
 {
+    *launched = false;
+    SepArgs a{};
+    size_t lds = 0;
+    if (!plan_sep(tile, g, nbands, oscale, weights, out_div, &a, &lds)) return WN_OK;
+    a.out = out_dev;
+    a.vec4_ok = (g.nx % 4 == 0) && ((reinterpret_cast<uintptr_t>(out_dev) & 15) == 0);
+    a.even_share_q10 = a.nbands == 1 ? 545 : 512;
     bool ok;
     switch (a.nbands) {
-    case 1: ok = launch_sep<1>(a, lds, s); break;
-    case 2: ok = launch_sep<2>(a, lds, s); break;
-    case 3: ok = launch_sep<3>(a, lds, s); break;
-    case 4: ok = launch_sep<4>(a, lds, s); break;
-    case 5: ok = launch_sep<5>(a, lds, s); break;
-    case 6: ok = launch_sep<6>(a, lds, s); break;
-    case 7: ok = launch_sep<7>(a, lds, s); break;
-    default: ok = launch_sep<8>(a, lds, s); break;
+    case 1: ok = launch_sep<1>(a, lds, stream); break;
+    case 2: ok = launch_sep<2>(a, lds, stream); break;
+    case 3: ok = launch_sep<3>(a, lds, stream); break;
+    case 4: ok = launch_sep<4>(a, lds, stream); break;
+    case 5: ok = launch_sep<5>(a, lds, stream); break;
+    case 6: ok = launch_sep<6>(a, lds, stream); break;
+    case 7: ok = launch_sep<7>(a, lds, stream); break;
+    default: ok = launch_sep<8>(a, lds, stream); break;
     }
-    *launched = ok;
     if (!ok) return WN_OK;
+    *launched = true;
     WN_LAUNCH_CHECK("grid3d_sep_kernel");
     return WN_OK;
+}
+
+// The gather kernel on the tile's padded copy when it has one (d.coef is set here); the caller checks the launch.
+void launch_direct(const DirectArgs &d, const wn_tile *tile, size_t total, hipStream_t stream)
+{
+    DirectArgs a = d;
+    a.coef = tile->dev_padded ? tile->dev_padded : tile->dev;
+    if (tile->dev_padded)
+        hipLaunchKernelGGL(grid3d_direct_kernel<true>, dim3(grid_blocks(total)), dim3(256), 0, stream, a);
+    else
+        hipLaunchKernelGGL(grid3d_direct_kernel<false>, dim3(grid_blocks(total)), dim3(256), 0, stream, a);
 }
 
 } // namespace
@@ -803,42 +801,22 @@ int wn_eval3d_grid(const wn_tile *tile, const wn_grid *grid, float *out_dev, voi
         if (rc || launched) return rc;
         rc = strip_try(tile, g, out_dev, as_stream(stream), &launched); // rows of k*256 samples, >= 0.18 planes per step
         if (rc || launched) return rc;
-        SepArgs a{};
-        size_t lds = 0;
-        const float os = g.octave_scale;
-        if (plan_sep(tile, g, 1, &os, nullptr, 1.0f, &a, &lds)) {
-            a.out = out_dev;
-            a.vec4_ok = (g.nx % 4 == 0) && ((reinterpret_cast<uintptr_t>(out_dev) & 15) == 0);
-            a.even_share_q10 = a.nbands == 1 ? 545 : 512;
-#ifdef WN_TUNE_ENV
-            if (const char *e = getenv("WN_SEP_EVEN_SHARE")) a.even_share_q10 = atoi(e);
-#endif
-            rc = run_sep(a, lds, as_stream(stream), &launched);
-            if (rc || launched) return rc;
-        }
+        rc = sep_try(tile, g, 1, &os1, nullptr, 1.0f, out_dev, as_stream(stream), &launched);
+        if (rc || launched) return rc;
     }
     {   // bit-exact: the reference's 27-tap loop on an LDS-staged coefficient box when the bricks' boxes fit ...
         bool launched = false;
-#ifdef WN_TUNE_ENV
-        if (!getenv("WN_NO_EXACT_LDS"))
-#endif
         rc = exact_lds_try(tile, g, out_dev, as_stream(stream), &launched);
         if (rc || launched) return rc;
     }
     // ... else on gathers from the tile
     DirectArgs d{};
-    d.coef = tile->dev;
     d.out = out_dev;
     d.n = tile->n;
     d.nmask = pow2_mask(tile->n);
     d.g = g;
     d.nbands = 0;
-    if (tile->dev_padded) {
-        d.coef = tile->dev_padded;
-        hipLaunchKernelGGL(grid3d_direct_kernel<true>, dim3(grid_blocks(total)), dim3(256), 0, as_stream(stream), d);
-    } else {
-        hipLaunchKernelGGL(grid3d_direct_kernel<false>, dim3(grid_blocks(total)), dim3(256), 0, as_stream(stream), d);
-    }
+    launch_direct(d, tile, total, as_stream(stream));
     WN_LAUNCH_CHECK("grid3d_direct_kernel");
     return WN_OK;
 }
@@ -882,30 +860,17 @@ int wn_multiband3d_grid(const wn_tile *tile, const wn_grid *grid, float s, int f
     // z_mode == WN_Z_CONST: band b sits at 2*z_const*2^(first_band+b), which the brick kernel's per-band
     // tables do not model (they scale lattice indices, not a constant) -> the direct kernel
     if (!(grid->flags & WN_GRID_EXACT) && active >= 1 && g.post_scale == 1.0f && !g.z_const_mode) {
-        SepArgs a{};
-        size_t lds = 0;
         GridArgs gb = g;
         gb.post_scale = 2.0f;
-        {   // the plane-pipeline kernel (wn_wavelet_multiband.hip) takes wide lattices of 2..5 bands ...
-            bool launched = false;
-            rc = multiband_try(tile, gb, active, oscale, wts, out_div, out_dev, as_stream(stream), &launched, 0);
-            if (rc || launched) return rc;
-        }
+        bool launched = false;
+        // the plane-pipeline kernel (wn_wavelet_multiband.hip) takes wide lattices of 1..5 bands ...
+        rc = multiband_try(tile, gb, active, oscale, wts, out_div, out_dev, as_stream(stream), &launched, 0);
+        if (rc || launched) return rc;
         // ... the brick kernel the rest
-        if (plan_sep(tile, gb, active, oscale, wts, out_div, &a, &lds)) {
-            a.out = out_dev;
-            a.vec4_ok = (g.nx % 4 == 0) && ((reinterpret_cast<uintptr_t>(out_dev) & 15) == 0);
-            a.even_share_q10 = a.nbands == 1 ? 545 : 512;
-#ifdef WN_TUNE_ENV
-            if (const char *e = getenv("WN_SEP_EVEN_SHARE")) a.even_share_q10 = atoi(e);
-#endif
-            bool launched = false;
-            rc = run_sep(a, lds, as_stream(stream), &launched);
-            if (rc || launched) return rc;
-        }
+        rc = sep_try(tile, gb, active, oscale, wts, out_div, out_dev, as_stream(stream), &launched);
+        if (rc || launched) return rc;
     }
     DirectArgs d{};
-    d.coef = tile->dev;
     d.out = out_dev;
     d.n = tile->n;
     d.nmask = pow2_mask(tile->n);
@@ -923,12 +888,7 @@ int wn_multiband3d_grid(const wn_tile *tile, const wn_grid *grid, float s, int f
         d.band_scale[0] = 1.0f;
         d.band_w[0] = 0.0f;
     }
-    if (tile->dev_padded) {
-        d.coef = tile->dev_padded;
-        hipLaunchKernelGGL(grid3d_direct_kernel<true>, dim3(grid_blocks(total)), dim3(256), 0, as_stream(stream), d);
-    } else {
-        hipLaunchKernelGGL(grid3d_direct_kernel<false>, dim3(grid_blocks(total)), dim3(256), 0, as_stream(stream), d);
-    }
+    launch_direct(d, tile, total, as_stream(stream));
     WN_LAUNCH_CHECK("grid3d_direct_kernel(multiband)");
     return WN_OK;
 }

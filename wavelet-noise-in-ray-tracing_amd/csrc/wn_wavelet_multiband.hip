@@ -34,7 +34,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
 #include <type_traits>
 
 namespace {
@@ -76,40 +75,15 @@ struct MbArgs {
     float inv_den; // 1/den when den is a power of two (exact), else 0
     int nbx, nby, nbz;
     int all_full;  // every brick lies wholly inside the lattice: no store of a plane is ever skipped
-    int debug;     // WN_TUNE_ENV builds: WN_MBP_DEBUG probes (0 in the product)
-    int permute, even_permille; // WN_TUNE_ENV builds: work-distribution experiments (0 / 500 in the product)
     MbBand band[kMaxNB];
     int pass_band[kPasses]; // -1: no such pass; passes are dealt in band order, a band's passes are consecutive
 };
-
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // v_readlane_b32 of a float (the builtin is typed int: pass the bits, not the value)
 __device__ __forceinline__ float readlane_f(float v, int l)
 {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
 }
-
-__device__ __forceinline__ float coord_of(int i, float den, float inv_den, float range, float oscale, float post)
-{
-    const float fi = (float)i;
-    float c = ((inv_den != 0.0f) ? fi * inv_den : fi / den) * range; // exact either way when den is a power of two
-    c = c * oscale;
-    c = c * post;
-    return c;
-}
-
-#ifdef WN_TUNE_ENV
-// in-kernel time stamps of workgroup 0 (WN_MBP_DEBUG=9): [wave slot 0..2 = a window, a collapse, a store wave][iteration][3]
-__device__ long long g_mbp_stamps[3 * 256 * 3];
-#define MBP_STAMP(k)                                                                                                \
-    do {                                                                                                            \
-        if (a.debug == 9 && blockIdx.x == 0 && lane == 0 && gp < 256 && (wave == 1 || wave == kWW + 1 || wave == kWW + kPW)) \
-            g_mbp_stamps[((wave == 1 ? 0 : wave == kWW + 1 ? 1 : 2) * 256 + gp) * 3 + (k)] = __builtin_amdgcn_s_memtime(); \
-    } while (0)
-#else
-#define MBP_STAMP(k) do { } while (0)
-#endif
 
 template <int NB>
 __global__ __launch_bounds__(64 * kWaves) void grid3d_mbp_kernel(const MbArgs a)
@@ -135,38 +109,10 @@ __global__ __launch_bounds__(64 * kWaves) void grid3d_mbp_kernel(const MbArgs a)
     // bricks mostly share their column (bx, by), so a band's coefficient box only moves by 0..2 rows in z between them
     const int nyz = a.nby * a.nbz;
     const long long total = (long long)a.nbx * nyz;
-    int item0 = (int)(total * blockIdx.x / gridDim.x), item1 = (int)(total * (blockIdx.x + 1) / gridDim.x);
-#ifdef WN_TUNE_ENV
-    // experiments (profiles/r03_workgroup_end_times.txt): which workgroup -- workgroup w runs on XCD w mod 8 -- takes which range
-    if (a.permute >= 10 && a.permute < 18 && gridDim.x == 256) { // range rotl8(w, permute - 10)
-        const int r = a.permute - 10;
-        const unsigned w = ((blockIdx.x << r) | (blockIdx.x >> (8 - r))) & 255u;
-        item0 = (int)(total * w / gridDim.x);
-        item1 = (int)(total * (w + 1) / gridDim.x);
-    }
-    if (a.even_permille != 500 && (gridDim.x & 1) == 0) { // uneven shares of a pair's bricks for its even / odd workgroup
-        const int pair = blockIdx.x >> 1;
-        const int p0 = (int)(total * (2 * pair) / gridDim.x), p1 = (int)(total * (2 * pair + 2) / gridDim.x);
-        const int mid = p0 + (int)((long long)(p1 - p0) * a.even_permille / 1000);
-        item0 = (blockIdx.x & 1) ? mid : p0;
-        item1 = (blockIdx.x & 1) ? p1 : mid;
-    }
-#endif
+    const int item0 = (int)(total * blockIdx.x / gridDim.x), item1 = (int)(total * (blockIdx.x + 1) / gridDim.x);
     const int nb = item1 - item0;
     if (nb <= 0) return;
     const int G = nb * kBZ; // planes this workgroup produces
-#ifdef WN_TUNE_ENV
-    if (a.debug == 12 && blockIdx.x == 0 && tid == 0) { // shader clock of this launch: cycles and 100 MHz ticks, start / end
-        g_mbp_stamps[0] = __builtin_amdgcn_s_memtime();
-        g_mbp_stamps[1] = __builtin_amdgcn_s_memrealtime();
-    }
-    if (a.debug == 13 && tid == 0 && blockIdx.x < 256) { // every workgroup: start / end in 100 MHz ticks, its XCC
-        unsigned xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        g_mbp_stamps[blockIdx.x * 3] = __builtin_amdgcn_s_memrealtime();
-        g_mbp_stamps[blockIdx.x * 3 + 2] = xcc & 15;
-    }
-#endif
 
     struct Brick { int bx, by, bz; };
     auto brick_of = [&](int item) {
@@ -194,7 +140,7 @@ __global__ __launch_bounds__(64 * kWaves) void grid3d_mbp_kernel(const MbArgs a)
             else idx = (slot == kSlotX) ? k.bx * kBX : min(k.bx * kBX + kBX - 1, g.nx - 1);
             // (the band's scale from LDS: indexed by a lane value the kernel argument becomes a vector-memory load, which in
             // this kernel would queue behind the store waves' stores)
-            const float c = coord_of(idx, (float)g.den, a.inv_den, g.base_range, s_oscale[b], g.post_scale);
+            const float c = wn::lattice_coord_fast(idx, (float)g.den, a.inv_den, g.base_range, s_oscale[b], g.post_scale);
             int m;
             float w0, w1, w2;
             wn::bspline(c, m, w0, w1, w2);
@@ -388,14 +334,13 @@ __global__ __launch_bounds__(64 * kWaves) void grid3d_mbp_kernel(const MbArgs a)
             v2f yc0[kBY / 2][K0 > 0 ? K0 : 1], yc1[kBY / 2][K1 > 0 ? K1 : 1]; // [pair of rows of samples][slot]
             float wzv0 = 0.0f, wzv1 = 0.0f;
             float *const Rw0 = lds + 64 * ps[0].id + lane, *const Rw1 = lds + 64 * ps[1].id + lane;
-            lds_barrier(); // the store waves' requests for the first brick's boxes have landed
+            wn::lds_barrier(); // the store waves' requests for the first brick's boxes have landed
             prep_brick(ps[0], yc0, wzv0, k0c);
             prep_brick(ps[1], yc1, wzv1, k1c);
             p1_slice(Rw0, 0, yc0, wzv0, k0c);
             p1_slice(Rw1, 0, yc1, wzv1, k1c);
-            lds_barrier();
+            wn::lds_barrier();
             for (int gp = 0; gp < G + 2; ++gp) {
-                MBP_STAMP(0);
                 const int zi = gp & (kBZ - 1);
                 if (gp < G) {
                     if (gp + 1 < G) {
@@ -403,20 +348,13 @@ __global__ __launch_bounds__(64 * kWaves) void grid3d_mbp_kernel(const MbArgs a)
                             prep_brick(ps[0], yc0, wzv0, k0c);
                             prep_brick(ps[1], yc1, wzv1, k1c);
                         }
-                        MBP_STAMP(1);
-#ifdef WN_TUNE_ENV
-                        if (a.debug != 10)
-#endif
-                        {
-                            const int rs = ((gp + 1) & 1) * kRPlane;
-                            p1_slice(Rw0 + rs, (gp + 1) & (kBZ - 1), yc0, wzv0, k0c);
-                            p1_slice(Rw1 + rs, (gp + 1) & (kBZ - 1), yc1, wzv1, k1c);
-                        }
+                        const int rs = ((gp + 1) & 1) * kRPlane;
+                        p1_slice(Rw0 + rs, (gp + 1) & (kBZ - 1), yc0, wzv0, k0c);
+                        p1_slice(Rw1 + rs, (gp + 1) & (kBZ - 1), yc1, wzv1, k1c);
                     }
                     if (zi == kBZ - 1) next_brick();
                 }
-                MBP_STAMP(2);
-                lds_barrier();
+                wn::lds_barrier();
             }
         };
         using std::integral_constant;
@@ -492,17 +430,12 @@ __global__ __launch_bounds__(64 * kWaves) void grid3d_mbp_kernel(const MbArgs a)
         };
 
         x_weights(0, cur.bx);
-        lds_barrier();
-        lds_barrier();
+        wn::lds_barrier();
+        wn::lds_barrier();
         for (int gp = 0; gp < G + 2; ++gp) {
-            MBP_STAMP(0);
             const int zi = gp & (kBZ - 1);
             if (gp < G) {
-#ifdef WN_TUNE_ENV
-                if (a.debug != 11)
-#endif
                 phaseC(gp & 1, gp & (kRing - 1));
-                MBP_STAMP(1);
                 if (zi == kBZ - 1) {
                     const int tb1 = (tb == 2) ? 0 : tb + 1, tb2 = (tb1 == 2) ? 0 : tb1 + 1;
                     if (t + 2 < nb) fill_tables(tb2, nxt2); // tables of brick t+2
@@ -510,16 +443,8 @@ __global__ __launch_bounds__(64 * kWaves) void grid3d_mbp_kernel(const MbArgs a)
                     next_brick();
                 }
             }
-            MBP_STAMP(2);
-            lds_barrier();
+            wn::lds_barrier();
         }
-#ifdef WN_TUNE_ENV
-        if (a.debug == 12 && blockIdx.x == 0 && tid == 0) {
-            g_mbp_stamps[2] = __builtin_amdgcn_s_memtime();
-            g_mbp_stamps[3] = __builtin_amdgcn_s_memrealtime();
-        }
-        if (a.debug == 13 && tid == 0 && blockIdx.x < 256) g_mbp_stamps[blockIdx.x * 3 + 1] = __builtin_amdgcn_s_memrealtime();
-#endif
     } else {
         // ---- store waves ---------------------------------------------------------------------------------------------
         const int sw = wave - (kWW + kPW);
@@ -603,26 +528,10 @@ __global__ __launch_bounds__(64 * kWaves) void grid3d_mbp_kernel(const MbArgs a)
         request_band(integral_constant<int, 3>{}, 0, 0, false, true);
         request_band(integral_constant<int, 4>{}, 0, 0, false, true);
         for (int b = sw; b < NB; b += kSW) derive_tables(b, 0, 0, false, true);
-#ifdef WN_TUNE_ENV
-        if (a.debug == 20 && blockIdx.x == 0) { // dump the derived tables of the first brick
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-            if (sw == 0) {
-                float *dump = reinterpret_cast<float *>(g_mbp_stamps);
-                for (int i = lane; i < NB * kMaxK * kBY; i += 64) dump[i] = (&s_wy[0][0][0])[i];
-                for (int i = lane; i < NB * 64; i += 64) dump[256 + i] = (&s_wz[0][0])[i];
-                for (int i = lane; i < NB * 4; i += 64) dump[640 + i] = (float)(&s_prep[0][0])[i];
-                for (int i = lane; i < NB * 4; i += 64) dump[680 + i] = (float)(&s_bandc[0][0])[i];
-            }
-            for (int gp = 0; gp < G + 2; ++gp) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-            return;
-        }
-#endif
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        lds_barrier();
-        lds_barrier();
+        wn::lds_barrier();
+        wn::lds_barrier();
         for (int gp = 0; gp < G + 2; ++gp) {
-            MBP_STAMP(0);
             const int zi = gp & (kBZ - 1);
             if (gp >= 2) store_plane(gp - 2);
             if (gp < G) {
@@ -652,13 +561,10 @@ __global__ __launch_bounds__(64 * kWaves) void grid3d_mbp_kernel(const MbArgs a)
                 }
                 if (zi == kBZ - 1) next_brick();
             }
-            MBP_STAMP(2);
-            lds_barrier();
+            wn::lds_barrier();
         }
     }
 }
-
-inline int pow2_mask(int n) { return (n > 0 && (n & (n - 1)) == 0) ? n - 1 : -1; }
 
 template <int NB>
 bool launch_mbp(const MbArgs &a, size_t lds, long long bricks, hipStream_t s)
@@ -673,13 +579,6 @@ bool launch_mbp(const MbArgs &a, size_t lds, long long bricks, hipStream_t s)
 
 } // namespace
 
-#ifdef WN_TUNE_ENV
-extern "C" __attribute__((visibility("default"))) int wn_debug_mbp_stamps(long long *out, int count)
-{
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_mbp_stamps), sizeof(long long) * (size_t)count);
-}
-#endif
-
 namespace wn {
 
 // Plans and launches the plane-pipeline kernel when the lattice is in its regime (else *launched = false and the
@@ -689,15 +588,10 @@ int multiband_try(const wn_tile *tile, const GridArgs &g, int nbands, const floa
                   float out_div, float *out_dev, hipStream_t stream, bool *launched, int min_bricks_per_cu)
 {
     *launched = false;
-#ifdef WN_TUNE_ENV
-    if (getenv("WN_NO_MBP")) return WN_OK;
-    if (nbands == 1 && getenv("WN_NO_MBP1")) return WN_OK;
-#endif
-    if (nbands < 1 || nbands > kMaxNB || tile->n == 0 || pow2_mask(tile->n) < 0) return WN_OK;
+    if (nbands < 1 || nbands > kMaxNB || tile->n == 0 || wn::pow2_mask(tile->n) < 0) return WN_OK;
     if (g.nx <= 256 || (g.nx & 3) || g.ny <= 0 || g.nz <= 0 || g.z_const_mode || g.z0 < 0) return WN_OK;
     if (reinterpret_cast<uintptr_t>(out_dev) & 15) return WN_OK;
     MbArgs a{};
-    a.even_permille = 500;
     const double imax = std::max<double>(std::max(g.nx, g.ny), (double)g.z0 + g.nz);
     int passes = 0, box_off = 0;
     for (int w = 0; w < kPasses; ++w) a.pass_band[w] = -1;
@@ -725,18 +619,13 @@ int multiband_try(const wn_tile *tile, const GridArgs &g, int nbands, const floa
         box_off += K * K * a.band[b].rowlen;
     }
     if (box_off > kBoxFloats) return WN_OK;
-#ifdef WN_TUNE_ENV
-    if (const char *e = getenv("WN_MBP_DEBUG")) a.debug = atoi(e);
-    if (const char *e = getenv("WN_MBP_EVEN_SHARE")) a.even_permille = atoi(e);
-    if (const char *e = getenv("WN_MBP_PERMUTE")) a.permute = atoi(e);
-#endif
     const size_t lds = (size_t)(2 * kRPlane + kRingFloats) * sizeof(float);
     a.coef = tile->dev;
     a.out = out_dev;
     a.n = tile->n;
-    a.nmask = pow2_mask(tile->n);
+    a.nmask = wn::pow2_mask(tile->n);
     a.g = g;
-    a.inv_den = ((g.den & (g.den - 1)) == 0) ? 1.0f / (float)g.den : 0.0f;
+    a.inv_den = wn::inv_den_of(g.den);
     a.nbx = (g.nx + kBX - 1) / kBX;
     a.nby = (g.ny + kBY - 1) / kBY;
     a.nbz = (g.nz + kBZ - 1) / kBZ;

@@ -12,7 +12,6 @@
 #include "wn_texture_eval.hpp"
 
 #include <cmath>
-#include <cstdlib>
 
 namespace {
 
@@ -364,9 +363,6 @@ struct TextureOps {
     }
     __device__ const float *padded_tile() const { return a.coef; }
     __device__ int tile_n() const { return a.n; }
-#ifdef WN_TUNE_ENV
-    int tune_share = 3;
-#endif
     __device__ void store(size_t i, float v) const { a.grey[i] = v; }
     __device__ float stored(size_t i) const { return a.grey[i]; }
 };
@@ -393,9 +389,6 @@ struct Eval3dOps {
     }
     __device__ const float *padded_tile() const { return a.coef; }
     __device__ int tile_n() const { return a.n; }
-#ifdef WN_TUNE_ENV
-    int tune_share = 3;
-#endif
     __device__ float eval(size_t i) const
     {
         const float *p = a.pts + 3 * i;
@@ -546,19 +539,15 @@ __global__ __launch_bounds__(kSlabThreads) void row_slab_points_kernel(const Ops
             third_ok = false;
             __syncthreads();
         }
-        // stream order when the stream is coherent already, or when most of the chunk reads from the slab (what is left to
-        // gather then is one row of every plane, 66 KB: the plane order buys little)
-        int slab_share_min = 3;
-#ifdef WN_TUNE_ENV
-        slab_share_min = ops.tune_share;
-#endif
+        // stream order when the stream is coherent already, or when at least three quarters of the chunk read from the slab (what
+        // is left to gather then is one row of every plane, 66 KB: the plane order buys little)
         if (s_changes < 128) { // coherent already: neighbours share their lines, plain gathers in stream order are the fastest form
             for (int i = tid; i < count; i += kSlabThreads)
                 if (ops.active(begin + i)) ops.store(begin + i, ops.eval(begin + i));
             trusted_plain = kSlabTrust;
             continue;
         }
-        if (best_row == slab_row && best_count * 4 >= sampled * slab_share_min) {
+        if (best_row == slab_row && best_count * 4 >= sampled * 3) {
             if (!third_ok && slab_row >= 0) { // (the scratch's last users passed the barrier at the loop's top)
                 const int r2 = (slab_row + 1) & (kSlabTile - 1);
                 const float *tile = ops.padded_tile();
@@ -570,7 +559,7 @@ __global__ __launch_bounds__(kSlabThreads) void row_slab_points_kernel(const Ops
                 __syncthreads();
             }
             stream_order(begin, count);
-            if (best_row == slab_row && best_count * 4 >= sampled * slab_share_min) trusted = kSlabTrust;
+            if (best_row == slab_row && best_count * 4 >= sampled * 3) trusted = kSlabTrust;
             continue;
         }
         // pass 1: bin and rank of every point (the scratch becomes the histogram: zeroed here)
@@ -630,13 +619,9 @@ __global__ __launch_bounds__(kSlabThreads) void row_slab_points_kernel(const Ops
 // the slab kernel) and leaves the others, marked, to row_slab_points_kernel, which follows on the same stream.
 // false: not in this regime (the caller launches plane_sorted_points_kernel alone).
 template <typename Ops>
-bool launch_row_slab(Ops ops, int n, bool masked, hipStream_t stream)
+bool launch_row_slab(const Ops &ops, int n, bool masked, hipStream_t stream)
 {
     if (n != kSlabTile || masked || ops.count < kSlabMinPoints) return false;
-#ifdef WN_TUNE_ENV
-    if (getenv("WN_NO_ROW_SLAB")) return false;
-    if (const char *e = getenv("WN_ROW_SLAB_SHARE")) ops.tune_share = atoi(e); // quarters of a chunk; 5: never
-#endif
     const size_t chunks = (ops.count + kSortChunk - 1) / kSortChunk;
     if (chunks > 0x7fffffffull) return false;
     const void *fn = reinterpret_cast<const void *>(&row_slab_points_kernel<Ops>);
@@ -644,9 +629,6 @@ bool launch_row_slab(Ops ops, int n, bool masked, hipStream_t stream)
     if (!wn::ensure_dynamic_lds(fn, dev, kSlabLdsBytes)) return false; // the runtime refused the LDS opt-in
     const int grid = (int)std::min<size_t>(chunks, (size_t)wn::device_compute_units(dev));
     hipLaunchKernelGGL((plane_sorted_points_kernel<Ops, true>), dim3((unsigned)chunks), dim3(256), 0, stream, ops);
-#ifdef WN_TUNE_ENV
-    if (getenv("WN_ROW_SLAB_FIRST_ONLY")) return true; // experiment: the marks stay in the output
-#endif
     hipLaunchKernelGGL((row_slab_points_kernel<Ops>), dim3((unsigned)grid), dim3(kSlabThreads), kSlabLdsBytes, stream, ops, (int)chunks, 1);
     return true;
 }
@@ -660,15 +642,6 @@ int launch_sorted(const Ops &ops, hipStream_t stream)
     return WN_OK;
 }
 
-inline bool sort_enabled()
-{
-#ifdef WN_TUNE_ENV
-    if (getenv("WN_NO_POINT_SORT")) return false;
-#endif
-    return true;
-}
-
-inline int pow2_mask(int n) { return (n > 0 && (n & (n - 1)) == 0) ? n - 1 : -1; }
 inline int point_blocks(size_t total)
 {
     size_t b = (total + 255) / 256;
@@ -689,7 +662,7 @@ int fill_common(const wn_tile *tile, int dims, const void *pts, size_t n, const 
     if (n && (!pts || !out)) return wn::fail(WN_ERR_INVALID, "points/out pointer is NULL");
     a->coef = (dims == 3 && tile->dev_padded) ? tile->dev_padded : tile->dev;
     a->n = tile->n;
-    a->nmask = pow2_mask(tile->n);
+    a->nmask = wn::pow2_mask(tile->n);
     a->count = n;
     return WN_OK;
 }
@@ -711,7 +684,7 @@ int wn_eval3d_points(const wn_tile *tile, const float *xyz_dev, size_t n, float 
     if (rc || n == 0) return rc;
     a.pts = xyz_dev;
     a.out = out_dev;
-    if (n >= kSortMinPoints && a.n > 0 && sort_enabled()) { // long lists: chunks in z-plane order (plane_sorted_points_kernel)
+    if (n >= kSortMinPoints && a.n > 0) { // long lists: chunks in z-plane order (plane_sorted_points_kernel)
         if (tile->dev_padded && launch_row_slab(Eval3dOps<true, false>{a, n}, a.n, false, as_stream(stream))) {
             WN_LAUNCH_CHECK("row_slab_points_kernel(evaluate3D)");
             return WN_OK;
@@ -792,7 +765,7 @@ int wn_multiband3d_points(const wn_tile *tile, const float *xyz_dev, size_t n, f
     }
     a.apply_div = variance != 0.0f;
     a.out_div = a.apply_div ? sqrtf(variance * var_per_band) : 1.0f;
-    if (n >= kSortMinPoints && a.n > 0 && a.nbands >= 1 && sort_enabled()) { // long lists: chunks in the finest band's z-plane order
+    if (n >= kSortMinPoints && a.n > 0 && a.nbands >= 1) { // long lists: chunks in the finest band's z-plane order
         const int lrc = tile->dev_padded ? launch_sorted(Eval3dOps<true, true>{a, n}, as_stream(stream))
                                          : launch_sorted(Eval3dOps<false, true>{a, n}, as_stream(stream));
         if (lrc) return fail(lrc, "too many points");
@@ -874,18 +847,11 @@ int wn_wavelet_texture_points(const wn_tile *tile, int use_3d, double scale, int
     const size_t waves = (n + a.points_per_wave - 1) / a.points_per_wave;
     const size_t blocks = (waves + 3) / 4;
     if (blocks > 0x7fffffffull) return fail(WN_ERR_INVALID, "too many points");
-    bool padded = has_tile && use_3d && tile->dev_padded;
-#ifdef WN_TUNE_ENV
-    if (getenv("WN_POINTS_UNPADDED")) padded = false; // 27 dword gathers per point instead of 9 dwordx3
-#endif
+    const bool padded = has_tile && use_3d && tile->dev_padded;
     if (padded) a.coef = tile->dev_padded;
     const dim3 grid((unsigned)blocks), block(256);
     // 3-D tile and enough points: chunks taken in z-plane order (see plane_sorted_points_kernel)
-    bool sorted = a.mode == 3 && n >= kSortMinPoints;
-#ifdef WN_TUNE_ENV
-    if (getenv("WN_NO_POINT_SORT")) sorted = false;
-#endif
-    if (sorted) {
+    if (a.mode == 3 && n >= kSortMinPoints) {
         int lrc;
         if (padded && launch_row_slab(TextureOps<false, true>{a, n}, a.n, active_dev != nullptr, as_stream(stream))) {
             WN_LAUNCH_CHECK("row_slab_points_kernel(texture)");

@@ -41,10 +41,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
-#ifdef WN_STRIP_STAMPS
-#include <cstdio>
-#endif
 
 namespace {
 
@@ -55,13 +51,9 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 constexpr int kCW = 4;          // compute waves per workgroup = rows per item
 constexpr int kSW = kCW;        // store waves per workgroup (one per compute wave)
 constexpr int kCols = 96;       // coefficient columns an item may touch (host: 255*step + 7 <= 96)
-#ifndef WN_STRIP_PLANES
-#define WN_STRIP_PLANES 37
-#define WN_STRIP_CHUNK 128
-#endif
-constexpr int kPlanes = WN_STRIP_PLANES;     // coefficient planes an item may touch (host: (chunk_len-1)*step + 5 <= 37)
+constexpr int kPlanes = 37;     // coefficient planes an item may touch (host: (chunk_len-1)*step + 5 <= 37)
 constexpr int kRowFloats = 96;  // table row = kCols
-constexpr int kMaxChunk = WN_STRIP_CHUNK;  // planes per item (z table: 16 B per plane)
+constexpr int kMaxChunk = 128;  // planes per item (z table: 16 B per plane)
 constexpr int kRRow = 100;      // one R row (96 columns + pad)
 constexpr int kTableFloats = kPlanes * kCW * kRowFloats; // the item's coefficient table [plane][tile row 0..3][96]
 constexpr int kStageFloats = 4 * kCW * 256; // two pairs of steps x one 1-KiB output row per compute wave and step
@@ -80,30 +72,13 @@ struct StripArgs {
     int range_len;    // planes of one owner range: a workgroup takes (group, range) pairs ...
     int owners;       // ... total_groups * number of ranges of them
     int chunk_len;    // and walks a range in items of at most this many planes
-    int split_fill;   // request the later planes of an item's table while its march starts
-#ifdef WN_STRIP_STAMPS
-    unsigned long long *stamps; // debug build: phase time stamps of a few workgroups
-#endif
 };
-
-__device__ __forceinline__ float coord(int i, float den, float inv_den, float range, float oscale, float post)
-{
-    const float fi = (float)i;
-    float c = ((inv_den != 0.0f) ? fi * inv_den : fi / den) * range;
-    c = c * oscale;
-    c = c * post;
-    return c;
-}
 
 // LDS byte address of a pointer into the dynamic shared array
 __device__ __forceinline__ unsigned lds_address(const float *p)
 {
     return (unsigned)(unsigned long long)(__attribute__((address_space(3))) const char *)(const char *)p;
 }
-
-// Workgroup barrier that orders LDS traffic only.  __syncthreads() would also drain vmcnt, i.e. make a
-// store wave wait for its outstanding global stores.
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // The first half of the grid (dispatched first, one workgroup per CU) and the second half share the CUs; they
 // take turns at the higher wave priority, kPrioPeriod planes at a time.
@@ -151,10 +126,10 @@ __global__ __launch_bounds__(64 * (kCW + kSW)) void grid3d_strip_kernel(const St
             for (int zb = z_lo; zb < z_hi;) {
                 const int zn = min(a.chunk_len, z_hi - zb);
                 float *dst = a.out + ((size_t)zb * plane_stride + (size_t)row * g.nx + xs * 256 + lane * 4);
-                lds_barrier(); // set-up
+                wn::lds_barrier(); // set-up
                 for (int t = 0; t < zn; t += 2, gt += 2) { // a pair of planes per hand-over
                     if ((gt & (kPrioPeriod - 1)) <= 1) set_turn_priority(gt / kPrioPeriod);
-                    lds_barrier();
+                    wn::lds_barrier();
                     if (row < g.ny) {
                         *reinterpret_cast<v4f *>(dst) = *reinterpret_cast<const v4f *>(src + (t & 3) * (kCW * 256));
                         if (t + 1 < zn)
@@ -163,7 +138,7 @@ __global__ __launch_bounds__(64 * (kCW + kSW)) void grid3d_strip_kernel(const St
                     }
                 }
                 if (zn & 1) --gt; // planes, not pairs
-                lds_barrier(); // item closed: stage, tables may be rewritten
+                wn::lds_barrier(); // item closed: stage, tables may be rewritten
                 zb += zn;
             }
         }
@@ -171,13 +146,6 @@ __global__ __launch_bounds__(64 * (kCW + kSW)) void grid3d_strip_kernel(const St
     }
 
     // ---- compute waves ---------------------------------------------------------------------------------
-#ifdef WN_STRIP_STAMPS
-    int sidx = 0;
-    auto stamp = [&]() { if (a.stamps && tid == 0 && (blockIdx.x % 65) == 0 && sidx < 16) a.stamps[(blockIdx.x / 65) * 16 + sidx] = wall_clock64(); ++sidx; };
-#else
-    auto stamp = [] {};
-#endif
-    stamp();
     float *const rb0 = rrows + wave * 2 * kRRow;
     const v4f *const zt = reinterpret_cast<const v4f *>(ztab);
     const float den = (float)g.den;
@@ -192,7 +160,7 @@ __global__ __launch_bounds__(64 * (kCW + kSW)) void grid3d_strip_kernel(const St
         int mx_first;
         {
             float t0, t1, t2;
-            wn::bspline(coord(x_first, den, a.inv_den, g.base_range, g.octave_scale, g.post_scale), mx_first, t0, t1, t2);
+            wn::bspline(wn::lattice_coord_fast(x_first, den, a.inv_den, g.base_range, g.octave_scale, g.post_scale), mx_first, t0, t1, t2);
             mx_first = __builtin_amdgcn_readfirstlane(mx_first);
         }
         const int ix0 = (mx_first - 1) & ~3; // coefficient column of table/R column 0, aligned for 16-byte loads
@@ -203,7 +171,7 @@ __global__ __launch_bounds__(64 * (kCW + kSW)) void grid3d_strip_kernel(const St
             float w[4][3];
 #pragma unroll
             for (int q = 0; q < 4; ++q)
-                wn::bspline(coord(x0 + q, den, a.inv_den, g.base_range, g.octave_scale, g.post_scale), m[q], w[q][0], w[q][1], w[q][2]);
+                wn::bspline(wn::lattice_coord_fast(x0 + q, den, a.inv_den, g.base_range, g.octave_scale, g.post_scale), m[q], w[q][0], w[q][1], w[q][2]);
             wbase = min(m[0] - 1 - ix0, kCols - 4); // the host guarantees m[0] + 2 - ix0 < kCols
             // column quads the block touches: lane 63 holds the last window
             nquads = min(__builtin_amdgcn_readlane(wbase, 63) / 4 + 2, kCols / 4);
@@ -222,9 +190,9 @@ __global__ __launch_bounds__(64 * (kCW + kSW)) void grid3d_strip_kernel(const St
         float wy0, wy1, wy2;
         {
             float t0, t1, t2;
-            wn::bspline(coord(yg * kCW, den, a.inv_den, g.base_range, g.octave_scale, g.post_scale), my_first, t0, t1, t2);
+            wn::bspline(wn::lattice_coord_fast(yg * kCW, den, a.inv_den, g.base_range, g.octave_scale, g.post_scale), my_first, t0, t1, t2);
         }
-        wn::bspline(coord(y, den, a.inv_den, g.base_range, g.octave_scale, g.post_scale), my_v, wy0, wy1, wy2);
+        wn::bspline(wn::lattice_coord_fast(y, den, a.inv_den, g.base_range, g.octave_scale, g.post_scale), my_v, wy0, wy1, wy2);
         my_first = __builtin_amdgcn_readfirstlane(my_first);
         const int d = min(max(__builtin_amdgcn_readfirstlane(my_v) - my_first, 0), 1);
 
@@ -234,13 +202,13 @@ __global__ __launch_bounds__(64 * (kCW + kSW)) void grid3d_strip_kernel(const St
             for (int i = tid; i < zn + 3; i += 64 * kCW) {
                 int m;
                 float w0, w1, w2;
-                wn::bspline(coord(g.z0 + zb + min(i, zn - 1), den, a.inv_den, g.base_range, g.octave_scale, g.post_scale), m, w0, w1, w2);
+                wn::bspline(wn::lattice_coord_fast(g.z0 + zb + min(i, zn - 1), den, a.inv_den, g.base_range, g.octave_scale, g.post_scale), m, w0, w1, w2);
                 *reinterpret_cast<v4f *>(ztab + 4 * i) = v4f{__int_as_float(m), w0 * g.out_scale, w1 * g.out_scale, w2 * g.out_scale};
             }
             int m0;
             {
                 float t0, t1, t2;
-                wn::bspline(coord(g.z0 + zb, den, a.inv_den, g.base_range, g.octave_scale, g.post_scale), m0, t0, t1, t2);
+                wn::bspline(wn::lattice_coord_fast(g.z0 + zb, den, a.inv_den, g.base_range, g.octave_scale, g.post_scale), m0, t0, t1, t2);
                 m0 = __builtin_amdgcn_readfirstlane(m0);
             }
 
@@ -250,7 +218,7 @@ __global__ __launch_bounds__(64 * (kCW + kSW)) void grid3d_strip_kernel(const St
             int m_last;
             {
                 float t0, t1, t2;
-                wn::bspline(coord(g.z0 + zb + zn - 1, den, a.inv_den, g.base_range, g.octave_scale, g.post_scale), m_last, t0, t1, t2);
+                wn::bspline(wn::lattice_coord_fast(g.z0 + zb + zn - 1, den, a.inv_den, g.base_range, g.octave_scale, g.post_scale), m_last, t0, t1, t2);
                 m_last = __builtin_amdgcn_readfirstlane(m_last);
             }
             const int planes = min(m_last - m0 + 3, kPlanes); // the host guarantees the bound
@@ -267,7 +235,7 @@ __global__ __launch_bounds__(64 * (kCW + kSW)) void grid3d_strip_kernel(const St
                 return (size_t)((m0 - 1 + p) & mask) * n * n + (size_t)((my_first - 1 + row) & mask) * n + (size_t)((ix0 + 4 * quad) & mask);
             };
             // late part: at most kLate triples per lane, and only when the item is long enough to reach the commit point
-            const int late = (a.split_fill && zn >= 2 * kCommitAt + 2 && planes > kEarlyPlanes)
+            const int late = (zn >= 2 * kCommitAt + 2 && planes > kEarlyPlanes)
                                  ? min(total - kEarlyPlanes * kCW * nquads, kLate * 64 * kCW) : 0;
             const int early = total - late;
             {
@@ -307,7 +275,7 @@ __global__ __launch_bounds__(64 * (kCW + kSW)) void grid3d_strip_kernel(const St
                 yv[0] = __builtin_fmaf(wy2, ca[s + 2 * kRowFloats], __builtin_fmaf(wy1, ca[s + kRowFloats], wy0 * ca[s]));
                 yv[1] = __builtin_fmaf(wy2, cb[s + 2 * kRowFloats], __builtin_fmaf(wy1, cb[s + kRowFloats], wy0 * cb[s]));
             };
-            lds_barrier(); // set-up: z table and coefficient table written
+            wn::lds_barrier(); // set-up: z table and coefficient table written
             int cur_mid = m0;
             float Y0[2], Y1[2], Y2[2], Y3[2]; // planes cur_mid-1 .. cur_mid+2 (Y3: the prefetched next one)
             collapse(m0 - 1, Y0);
@@ -355,7 +323,6 @@ __global__ __launch_bounds__(64 * (kCW + kSW)) void grid3d_strip_kernel(const St
                              : "memory");
             };
 
-            stamp();
             write_r(0, zt[0]);
             write_r(1, zt[1]);
             float *const park = stage + wave * 256 + lane * 4;
@@ -394,16 +361,13 @@ __global__ __launch_bounds__(64 * (kCW + kSW)) void grid3d_strip_kernel(const St
                 step(z + 1, wb, wa, eb, ea, 0, false);
             }
             if (z < zn) step(z, wa, wb, ea, eb, 1, true);
-            lds_barrier(); // hands over the last pair of rows
-            stamp();
-            lds_barrier(); // item closed: stage, tables may be rewritten
+            wn::lds_barrier(); // hands over the last pair of rows
+            wn::lds_barrier(); // item closed: stage, tables may be rewritten
             gt += zn;
             zb += zn;
         }
     }
 }
-
-inline int pow2_mask(int n) { return (n > 0 && (n & (n - 1)) == 0) ? n - 1 : -1; }
 
 } // namespace
 
@@ -413,9 +377,6 @@ namespace wn {
 int strip_try(const wn_tile *tile, const GridArgs &g, float *out_dev, hipStream_t stream, bool *launched)
 {
     *launched = false;
-#ifdef WN_TUNE_ENV
-    if (getenv("WN_NO_STRIP")) return WN_OK;
-#endif
     if (tile->n < 4 || pow2_mask(tile->n) < 0) return WN_OK;
     if (g.z_const_mode || g.nx <= 0 || g.ny <= 0 || g.nz <= 0) return WN_OK;
     if (g.z0 < 0) return WN_OK; // negative plane indices: the exact kernel (the bounds below assume indices >= 0)
@@ -441,20 +402,16 @@ int strip_try(const wn_tile *tile, const GridArgs &g, float *out_dev, hipStream_
     if (step > 0.0) chunk_max = (int)std::min<double>(kMaxChunk, std::floor((kPlanes - 5 - slack) / step) + 1.0);
     if (chunk_max < 8) return WN_OK;
     // owner ranges: every workgroup slot of the chip (two per CU) should get one, as long as a range keeps >= 32 planes
-    long long wgs = 2LL * cus;
+    const long long wgs = 2LL * cus;
     int nranges = 1;
     while (groups * nranges < wgs && (g.nz + 2 * nranges - 1) / (2 * nranges) >= 32) nranges *= 2;
-#ifdef WN_TUNE_ENV
-    if (const char *e = getenv("WN_STRIP_WGS")) wgs = (long long)atoi(e) * cus;
-    if (const char *e = getenv("WN_STRIP_RANGES")) nranges = atoi(e);
-#endif
     StripArgs a{};
     a.coef = tile->dev;
     a.out = out_dev;
     a.n = tile->n;
     a.nmask = pow2_mask(tile->n);
     a.g = g;
-    a.inv_den = ((g.den & (g.den - 1)) == 0) ? 1.0f / (float)g.den : 0.0f;
+    a.inv_den = inv_den_of(g.den);
     a.segs_per_row = g.nx / 256;
     a.total_groups = (int)groups;
     a.range_len = (g.nz + nranges - 1) / nranges;
@@ -464,33 +421,11 @@ int strip_try(const wn_tile *tile, const GridArgs &g, float *out_dev, hipStream_
     // a range is walked in equal items of at most chunk_max planes
     const int per_range = (a.range_len + chunk_max - 1) / chunk_max;
     a.chunk_len = (a.range_len + per_range - 1) / per_range;
-    a.split_fill = 1;
-#ifdef WN_TUNE_ENV
-    if (getenv("WN_STRIP_NO_SPLIT")) a.split_fill = 0;
-#endif
     // dynamic LDS beyond 64 KiB needs a per-(kernel, device) opt-in; refused -> the brick kernel serves the lattice
     if (!ensure_dynamic_lds(reinterpret_cast<const void *>(&grid3d_strip_kernel), dev, kLdsBytes)) return WN_OK;
     const int blocks = (int)std::min<long long>(owners, wgs);
-#ifdef WN_STRIP_STAMPS
-    static unsigned long long *dbg = nullptr;
-    static int dbg_calls = 0;
-    if (!dbg) { (void)hipMalloc(&dbg, 16 * 16 * 8); (void)hipMemset(dbg, 0, 16 * 16 * 8); }
-    a.stamps = dbg;
-#endif
     hipLaunchKernelGGL(grid3d_strip_kernel, dim3(blocks), dim3(64 * (kCW + kSW)), kLdsBytes, stream, a);
     WN_LAUNCH_CHECK("grid3d_strip_kernel");
-#ifdef WN_STRIP_STAMPS
-    if (++dbg_calls == 5) {
-        unsigned long long h[256];
-        (void)hipDeviceSynchronize();
-        (void)hipMemcpy(h, dbg, sizeof h, hipMemcpyDeviceToHost);
-        for (int b = 0; b < 8; ++b) {
-            fprintf(stderr, "stamps wg %d:", b * 65);
-            for (int i = 1; i < 8; ++i) fprintf(stderr, " %.2f", (double)(h[b * 16 + i] - h[b * 16]) / 100.0);
-            fprintf(stderr, " us\n");
-        }
-    }
-#endif
     *launched = true;
     return WN_OK;
 }
