@@ -1,0 +1,369 @@
+"""Which dense-grid kernel serves which lattice, and is its answer right there.
+
+wn_eval3d_grid and wn_multiband3d_grid offer a lattice to five kernels in turn (csrc/wn_wavelet_grid.hip:3-11): the
+plane pipeline grid3d_mbp_kernel<NB>, the strip march grid3d_strip_kernel, the brick kernel grid3d_sep_kernel<NB, XW>,
+grid3d_exact_lds_kernel and grid3d_direct_kernel.  The fast ones agree with the exact ones to 1e-5, so a value test
+passes whichever kernel ran.  ROUTES pins the kernel: each row is one call and the kernel the regime checks
+(multiband_try, strip_try, plan_sep, exact_lds_try) give it, derived from those checks and stated beside the row.
+The rows sit on both sides of every edge of those checks.
+
+test_routes_reach_the_kernels_they_name runs every row once in a child process under `rocprofv3 --kernel-trace` and
+compares the grid3d_* kernels of the trace, in dispatch order, with the table.  test_route_values checks each row's
+default-path result on the whole lattice against WN_GRID_EXACT and against the float64 reference (tests/_ref64.py),
+and two planes against the oracle.
+
+Run as `python tests/test_gpu_dispatch.py --child` it is that child: the calls of ROUTES, one after the other.
+"""
+import csv
+import glob
+import importlib
+import os
+import re
+import shutil
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+for p in (ROOT, HERE):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import _ref64  # noqa: E402
+
+TOL = 1e-5
+REF64_TOL = 1e-5
+SEED32 = 4242  # the 32^3 tile is generated on the device (and checked against the oracle's)
+
+MBP, STRIP, EXACT_LDS, DIRECT = "grid3d_mbp_kernel<{}>", "grid3d_strip_kernel", "grid3d_exact_lds_kernel", "grid3d_direct_kernel"
+
+
+def SEP(nb, xw):
+    return f"grid3d_sep_kernel<{nb},{xw}>"
+
+
+W5 = [1.0, 0.5, 2.0, 1.0, 0.25]
+
+# Calls: ("v", tile, den, nx, ny, z0, z1, octave)           wavelet_volume: step 8 * 2^octave / den
+#        ("m", tile, den, nx, ny, z0, z1, s, first, nb, w)  multiband_volume: band b has step 8 * 2^(first + b) / den
+#        ("vc", tile, size, octave)                         generate3DSlicedOctaveBandNoise: WN_Z_CONST, one band
+#        ("mc", tile, den, nx, ny, z_const, s, first, nb, w) wn_multiband3d_grid with WN_Z_CONST
+# exact = WN_GRID_EXACT.  Tiles: t128 (128^3, seed 12345), t32 (generated here), t8 / t16 / t6 (tests/golden; 6 is not a
+# power of two).  Edges (the host checks): mbp -- step < 2/7 (K <= 5), nx > 256, nx % 4 == 0, last 512-wide brick <= 10 %
+# padding (nx >= 931 for two bricks, >= 1397 for three), box floats <= 6144, power-of-two tile, z0 >= 0, no WN_Z_CONST;
+# strip -- 0.18 <= step, 3 * step < 1, nx % 256 == 0; sep -- 3 * step < 1, 512-wide bricks (XW 2) unless 256-wide ones
+# pad 10 % less, 16 planes per brick for one band on 256-wide bricks with nz >= 16; exact_lds -- its box fits 48 KiB.
+ROUTES = [
+    # -- single band: the plane pipeline's K <= 5 (step < 2/7), then the strip kernel
+    ("step_2_7_below", ("v", "t128", 449, 512, 6, 0, 9, 4), False, MBP.format(1)),      # step .2851: K = 5
+    ("step_2_7_at", ("v", "t128", 448, 512, 6, 0, 9, 4), False, STRIP),                  # step 2/7: K = 6
+    # the strip kernel's step range (rows of 768: the pipeline pads the second brick by 25 %)
+    ("step_018_in", ("v", "t128", 711, 768, 5, 0, 9, 4), False, STRIP),                  # step .18003
+    ("step_018_out", ("v", "t128", 712, 768, 5, 0, 9, 4), False, SEP(1, 1)),             # step .17978; 256-wide bricks
+    ("step_1_3_in", ("v", "t128", 385, 256, 5, 0, 9, 4), False, STRIP),                  # step .3325
+    ("step_1_3_at", ("v", "t128", 384, 256, 5, 0, 9, 4), False, EXACT_LDS),              # step 1/3: 4 samples span 3 mids
+    # row widths
+    ("nx_256", ("v", "t128", 512, 256, 5, 0, 9, 4), False, STRIP),                       # nx <= 256: no pipeline
+    ("nx_260", ("v", "t128", 512, 260, 5, 0, 9, 4), False, SEP(1, 2)),                   # nx % 256 != 0, one 512 brick
+    ("nx_1000", ("v", "t128", 512, 1000, 5, 0, 9, 4), False, MBP.format(1)),             # partial second brick
+    ("nx_998", ("v", "t128", 512, 998, 5, 0, 9, 4), False, SEP(1, 2)),                   # nx % 4 != 0
+    ("nx_768", ("v", "t128", 512, 768, 5, 0, 9, 4), False, STRIP),                       # nx % 256 == 0
+    ("nx_772", ("v", "t128", 512, 772, 5, 0, 9, 4), False, SEP(1, 2)),                   # 1024 padded either way: XW 2
+    # the pipeline's 10 % padding rule
+    ("pad_928", ("v", "t128", 512, 928, 5, 0, 9, 4), False, SEP(1, 2)),
+    ("pad_932", ("v", "t128", 512, 932, 5, 0, 9, 4), False, MBP.format(1)),
+    ("pad_1396", ("v", "t128", 512, 1396, 3, 0, 9, 4), False, SEP(1, 2)),
+    ("pad_1400", ("v", "t128", 512, 1400, 3, 0, 9, 4), False, MBP.format(1)),
+    # plane indices, tiles
+    ("z0_neg", ("v", "t128", 512, 512, 8, -3, 5, 4), False, EXACT_LDS),
+    ("z0_zero", ("v", "t128", 512, 512, 8, 0, 5, 4), False, MBP.format(1)),
+    ("tile6", ("v", "t6", 512, 512, 10, 0, 5, 4), False, EXACT_LDS),                      # mask-wrapped kernels need 2^k
+    ("tile8", ("v", "t8", 512, 512, 10, 0, 5, 4), False, MBP.format(1)),
+    # the brick kernel's brick shapes: 256 wide, 16 planes (nz >= 16) or 8; 512 wide, 8 planes
+    ("sep_bz16", ("v", "t128", 768, 768, 9, 3, 40, 4), False, SEP(1, 1)),
+    ("sep_bz8", ("v", "t128", 768, 768, 9, 3, 14, 4), False, SEP(1, 1)),
+    ("sep_xw2_bz8", ("v", "t128", 512, 998, 9, 0, 20, 4), False, SEP(1, 2)),             # nz >= 16 but 512-wide: 8
+    # WN_Z_CONST: the pipeline and the strip kernel index planes; the brick kernel models a constant z
+    ("zconst", ("vc", "t128", 512, 4), False, SEP(1, 2)),
+    ("zconst_exact", ("vc", "t128", 512, 4), True, EXACT_LDS),
+    # WN_GRID_EXACT, and a coarse lattice (step 2) whose box does not fit the exact kernel's LDS
+    ("exact_flag", ("v", "t128", 512, 1000, 5, 0, 9, 4), True, EXACT_LDS),
+    ("coarse", ("v", "t128", 64, 64, 8, 0, 9, 4), False, DIRECT),
+    ("coarse_exact", ("v", "t128", 64, 64, 8, 0, 9, 4), True, DIRECT),
+
+    # -- several bands: the pipeline's K <= 5 on the top band, its LDS box budget (8 passes of 64 columns is the most
+    #    five consecutive octaves below step 2/7 can need: the pass budget cannot bind)
+    ("mb_step_2_7_below", ("m", "t128", 449, 512, 8, 0, 9, -16.0, 2, 3, [1.0, 1.0, 1.0]), False, MBP.format(3)),
+    ("mb_step_2_7_at", ("m", "t128", 448, 512, 8, 0, 9, -16.0, 2, 3, [1.0, 1.0, 1.0]), False, SEP(3, 2)),
+    ("mb_box_6144_in", ("m", "t128", 492, 512, 8, 0, 9, -16.0, 0, 5, W5), False, MBP.format(5)),   # 6136 floats, 8 passes
+    ("mb_box_6144_out", ("m", "t128", 491, 512, 8, 0, 9, -16.0, 0, 5, W5), False, SEP(5, 2)),      # 6148 floats
+    ("mb_z0_neg", ("m", "t128", 512, 512, 8, -2, 6, -16.0, 0, 5, W5), False, DIRECT),
+    ("mb_tile6", ("m", "t6", 512, 512, 10, 0, 9, -16.0, 0, 5, W5), False, DIRECT),
+    ("mb_zconst", ("mc", "t128", 512, 512, 24, 0.37, -16.0, 0, 5, W5), False, DIRECT),
+    ("mb_exact", ("m", "t128", 512, 512, 8, 0, 9, -16.0, 0, 5, W5), True, DIRECT),
+    # the multiband shapes of test_gpu_parity that the pipeline's padding rule sends to the brick kernel
+    ("mb_516", ("m", "t128", 512, 516, 13, 0, 11, -16.0, 0, 5, W5), False, SEP(5, 1)),
+    ("mb_1028", ("m", "t128", 512, 1028, 8, 0, 8, -16.0, 1, 3, [1.0, 0.5, 2.0]), False, SEP(3, 1)),
+    ("mb_768", ("m", "t128", 768, 768, 16, 60, 70, -16.0, 0, 5, W5), False, SEP(5, 1)),
+    # six to eight bands: the brick kernel (steps <= 1/4), else the direct kernel
+    ("mb8_sep", ("m", "t128", 4096, 1000, 8, 0, 9, -16.0, 0, 8, [1.0] * 8), False, SEP(8, 2)),   # steps 1/512 .. 1/4
+    ("mb8_sep_256", ("m", "t128", 4096, 768, 11, 2, 13, -16.0, 0, 8,
+                     [0.5, 1.0, 2.0, 1.0, 0.7, 1.0, 1.5, 1.0]), False, SEP(8, 1)),
+    ("mb7_sep", ("m", "t128", 2048, 1000, 8, 0, 9, -16.0, 0, 7, [1.0] * 7), False, SEP(7, 2)),
+    ("mb7_sep_256", ("m", "t16", 2048, 768, 9, 5, 14, -16.0, -1, 7, [1.0, 2.0, 1.0, 0.5, 1.0, 1.0, 3.0]), False, SEP(7, 1)),
+    ("mb6_sep", ("m", "t128", 1024, 1000, 8, 3, 12, -16.0, 0, 6, [1.0] * 6), False, SEP(6, 2)),
+    ("mb6_sep_cut", ("m", "t8", 1024, 516, 9, 1, 10, -6.0, 0, 8, [1.0, 0.5, 2.0, 1.0, 1.0, 0.25, 1.0, 1.0]),
+     False, SEP(6, 1)),                                                                  # s stops after 6 of 8 bands
+    ("mb6_direct", ("m", "t128", 512, 512, 8, 0, 9, -16.0, 0, 6, [1.0] * 6), False, DIRECT),     # top step 1/2
+    ("mb7_direct", ("m", "t128", 512, 512, 8, 0, 9, -16.0, 0, 7, [1.0] * 7), False, DIRECT),
+    ("mb8_direct", ("m", "t128", 1024, 512, 8, 0, 9, -16.0, 0, 8, [1.0] * 8), False, DIRECT),    # top step 1
+]
+
+# The plane pipeline with NB = 1..5 on partial x-bricks: nx in {960, 1000, 1500, 2000} (last brick 448, 488, 476,
+# 464 samples wide), ragged ny and nz, slabs from z0 > 0, negative first bands, `s` cut-offs (the variance still sums
+# every requested band) and unequal weights.
+for _i, (_nx, _nb) in enumerate([(nx, nb) for nx in (960, 1000, 1500, 2000) for nb in range(1, 6)]):
+    _first = -(_i % 3)
+    _cut = _i % 2 == 1                          # ask for two bands more and stop after _nb with s
+    _req = _nb + 2 if _cut else _nb
+    _s = float(-(_first + _nb)) if _cut else -16.0
+    _w = [1.0 + 0.25 * ((_i + b) % 5) - 0.5 * (b % 2) for b in range(_req)]
+    ROUTES.append((f"mbp_partial_x_{_nx}_nb{_nb}",
+                   ("m", "t128", _nx, _nx, 9 + _i % 5, 1 + _i % 7, 1 + _i % 7 + 9 + _i % 4, _s, _first, _req, _w),
+                   False, MBP.format(_nb)))
+# ... and NB = 2..5 on small power-of-two tiles (the box wraps several times around the tile)
+for _t in ("t8", "t16", "t32"):
+    for _nb in range(2, 6):
+        ROUTES.append((f"mbp_{_t}_nb{_nb}", ("m", _t, 512, 512, 10, 3, 12, -16.0, 0, _nb, W5[:_nb]), False, MBP.format(_nb)))
+
+
+def load_tiles(wn):
+    """The noise objects of the table's tiles, and their coefficients for the host checkers."""
+    gold = np.load(os.path.join(HERE, "golden", "ref_vectors.npz"))
+    objs, coefs = {}, {}
+    n128 = wn.WaveletNoise(128, 12345)
+    n128.generateNoiseTile3D()
+    n32 = wn.WaveletNoise(32, SEED32)
+    n32.generateNoiseTile3D()
+    objs["t128"], objs["t32"] = n128, n32
+    coefs["t128"], coefs["t32"] = n128.getNoiseCoefficients(), n32.getNoiseCoefficients()
+    for name, key in (("t8", "tile3d_8_7"), ("t16", "tile3d_16_12345"), ("t6", "tile3d_5odd_11")):
+        coefs[name] = gold[key]
+        objs[name] = wn.WaveletNoise.from_coefficients(gold[key], 3)
+    return objs, coefs
+
+
+def run_call(wn, objs, call, exact):
+    """One call of the table: a (nz, ny, nx) tensor; exactly one grid3d_* kernel launch."""
+    import ctypes as C
+    import torch
+    nm = importlib.import_module("wavelet-noise-in-ray-tracing_amd.noise")
+    kind, tile = call[0], objs[call[1]]
+    if kind == "v":
+        den, nx, ny, z0, z1, octave = call[2:]
+        return wn.wavelet_volume(tile, den, nx, ny, z0, z1, octave, exact=exact)
+    if kind == "m":
+        den, nx, ny, z0, z1, s, first, nb, w = call[2:]
+        return wn.multiband_volume(tile, den, nx, ny, z0, z1, s, first, nb, w, exact=exact)
+    if kind == "vc":
+        size, octave = call[2:]
+        out = wn.generate3DSlicedOctaveBandNoise(size, octave, None, tile,
+                                                 flags=nm.WN_GRID_EXACT if exact else nm.WN_GRID_DEFAULT)
+        return out.view(1, size, size)
+    assert kind == "mc", kind
+    den, nx, ny, zc, s, first, nb, w = call[2:]
+    g = wn.GridSpec(den, nx, ny, z_mode=nm.WN_Z_CONST, z_const=zc, flags=nm.WN_GRID_EXACT if exact else nm.WN_GRID_DEFAULT)
+    out = g.empty()
+    gc = g.c()
+    wa = (C.c_float * nb)(*[float(x) for x in w])
+    nm.check(nm._lib.wn_multiband3d_grid(tile._handle(3), C.byref(gc), float(s), int(first), int(nb), wa, 0.18402,
+                                         nm._ptr(out), nm._stream()))
+    torch.cuda.current_stream().synchronize()
+    return out.view(1, ny, nx)
+
+
+def _child():
+    import torch
+    assert torch.cuda.is_available()
+    wn = importlib.import_module("wavelet-noise-in-ray-tracing_amd")
+    objs, _ = load_tiles(wn)
+    torch.cuda.synchronize()
+    for _name, call, exact, _kernel in ROUTES:
+        run_call(wn, objs, call, exact)
+        torch.cuda.synchronize()
+    print(f"dispatch child: {len(ROUTES)} calls")
+
+
+# ---- reading the trace ---------------------------------------------------------------------------------------------
+_DEMANGLED = re.compile(r"grid3d_([a-z_]+?)_kernel(?:<([^<>]*)>)?")
+_MANGLED = re.compile(r"grid3d_([a-z_]+?)_kernel(?:I((?:L[a-z]\d+E)+)E)?")
+
+
+def kernel_label(name):
+    """'grid3d_sep_kernel<1, 2>' / its mangled form -> 'grid3d_sep_kernel<1,2>'; None for other kernels.  The direct
+    kernel's template argument (padded tile copy or not) is not part of the routing: dropped."""
+    m = _MANGLED.search(name) if name.startswith("_Z") else _DEMANGLED.search(name)
+    if not m:
+        return None
+    base = f"grid3d_{m.group(1)}_kernel"
+    if m.group(1) == "direct" or not m.group(2):
+        return base
+    if name.startswith("_Z"):
+        args = re.findall(r"L[a-z](\d+)E", m.group(2))
+    else:
+        args = [a.strip() for a in m.group(2).split(",")]
+    return f"{base}<{','.join(args)}>"
+
+
+def test_kernel_label_parses_both_name_forms():
+    assert kernel_label("void (anonymous namespace)::grid3d_sep_kernel<8, 2>((anonymous namespace)::SepArgs)") == SEP(8, 2)
+    assert kernel_label("_ZN12_GLOBAL__N_117grid3d_sep_kernelILi8ELi2EEEvNS_7SepArgsE") == SEP(8, 2)
+    assert kernel_label("_ZN12_GLOBAL__N_117grid3d_mbp_kernelILi3EEEvNS_6MbArgsE") == MBP.format(3)
+    assert kernel_label("void (anonymous namespace)::grid3d_direct_kernel<true>((anonymous namespace)::DirectArgs)") == DIRECT
+    assert kernel_label("grid3d_exact_lds_kernel(wn::ExactArgs)") == EXACT_LDS
+    assert kernel_label("void (anonymous namespace)::tile_filter_kernel(float*)") is None
+
+
+def test_route_table_covers_every_kernel():
+    kernels = {k for _, _, _, k in ROUTES}
+    want = {MBP.format(nb) for nb in range(1, 6)} | {SEP(nb, xw) for nb in (1, 5, 6, 7, 8) for xw in (1, 2)} | \
+           {STRIP, EXACT_LDS, DIRECT}
+    assert want <= kernels, want - kernels
+    assert len({n for n, _, _, _ in ROUTES}) == len(ROUTES)
+
+
+# ---- GPU -----------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def wn():
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need a GPU (the product has no CPU path)"
+    return importlib.import_module("wavelet-noise-in-ray-tracing_amd")
+
+
+@pytest.fixture(scope="module")
+def tiles(wn):
+    return load_tiles(wn)
+
+
+@pytest.mark.gpu
+def test_routes_reach_the_kernels_they_name(tmp_path):
+    prof = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
+    assert os.path.exists(prof), "rocprofv3 is needed to observe which kernel ran"
+    out_dir = tmp_path / "trace"
+    cmd = ["timeout", "-k", "10", "300", prof, "--kernel-trace", "--output-format", "csv", "-d", str(out_dir),
+           "--", sys.executable, os.path.abspath(__file__), "--child"]
+    res = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True)
+    assert res.returncode == 0, f"exit {res.returncode}\n{res.stdout[-3000:]}\n{res.stderr[-3000:]}"
+    files = glob.glob(str(out_dir / "**" / "*kernel_trace.csv"), recursive=True)
+    assert len(files) == 1, (files, res.stdout[-2000:])
+    with open(files[0], newline="") as f:
+        rows = list(csv.DictReader(f))
+    rows.sort(key=lambda r: int(r["Dispatch_Id"]))
+    got = [lab for lab in (kernel_label(r["Kernel_Name"]) for r in rows) if lab is not None]
+    want = [k for _, _, _, k in ROUTES]
+    assert len(got) == len(want), (len(got), len(want), got)
+    wrong = [(name, k, g) for (name, _, _, k), g in zip(ROUTES, got) if k != g]
+    assert not wrong, "lattices served by another kernel than the table names (case, expected, ran): " + repr(wrong)
+
+
+@pytest.mark.gpu
+def test_generated_32_tile_matches_the_oracle(ora, tiles):
+    _, coefs = tiles
+    want = ora.tile3d(32, SEED32)
+    assert (coefs["t32"].view(np.uint32) == want.view(np.uint32)).all()
+
+
+def _host(t):
+    return t.detach().cpu().numpy()
+
+
+def _oracle_planes(ora, coef, call, zs):
+    """The oracle (float32 evaluate3D / WMultibandNoise) on planes zs (indices into the call's slab)."""
+    kind = call[0]
+    if kind == "v":
+        den, nx, ny, z0, z1, octave = call[2:]
+        return [ora.grid_wavelet3d_volume(coef, den, nx, ny, z0 + z, z0 + z + 1, octave)[0] for z in zs]
+    if kind == "m":
+        den, nx, ny, z0, z1, s, first, nb, w = call[2:]
+        return [ora.grid_multiband3d_volume(coef, den, nx, ny, z0 + z, z0 + z + 1, s, first, nb, w, 0.18402)[0]
+                for z in zs]
+    if kind == "vc":
+        size, octave = call[2:]
+        c = _ref64.lattice_coords(np.arange(size), size, 4.0, np.float32(2.0 ** octave), 2.0)
+        pts = np.stack(np.broadcast_arrays(c[None, :], c[:, None], np.float32(2.0)), -1).reshape(-1, 3)
+        inv = np.float32(1.0) / np.sqrt(np.float32(0.18402))
+        return [(ora.evaluate3d(coef, pts) * inv).astype(np.float32).reshape(size, size)]
+    den, nx, ny, zc, s, first, nb, w = call[2:]
+    cx, cy = _ref64.lattice_coords(np.arange(nx), den), _ref64.lattice_coords(np.arange(ny), den)
+    pts = np.stack(np.broadcast_arrays(cx[None, :], cy[:, None], np.float32(zc)), -1).reshape(-1, 3)
+    return [ora.multiband3d(coef, pts, s, first, nb, w, 0.18402).reshape(ny, nx)]
+
+
+def _ref64_volume(coef, call):
+    kind = call[0]
+    if kind == "v":
+        return _ref64.wavelet_volume(coef, *call[2:])
+    if kind == "m":
+        return _ref64.multiband_volume(coef, *call[2:], 0.18402)
+    if kind == "vc":
+        size, octave = call[2:]
+        c = _ref64.lattice_coords(np.arange(size), size, 4.0, np.float32(2.0 ** octave), 2.0)
+        return _ref64.evaluate_lattice(coef, c, c, np.float32([2.0])) / np.sqrt(np.float64(np.float32(0.18402)))
+    den, nx, ny, zc, s, first, nb, w = call[2:]
+    px, py = _ref64.lattice_coords(np.arange(nx), den), _ref64.lattice_coords(np.arange(ny), den)
+    return _ref64.multiband_lattice(coef, px, py, np.float32([zc]), s, first, nb, w, 0.18402)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,call,kernel", [pytest.param(n, c, k, id=n) for n, c, e, k in ROUTES if not e])
+def test_route_values(wn, ora, tiles, name, call, kernel):
+    """The default path on the whole lattice against WN_GRID_EXACT and the float64 reference (both <= 1e-5), two planes
+    against the oracle (<= 1e-5; bit-exact where an exact kernel serves); WN_GRID_EXACT bit-exact with the oracle there."""
+    import torch
+    objs, coefs = tiles
+    coef = coefs[call[1]]
+    fast = run_call(wn, objs, call, False)
+    exact = run_call(wn, objs, call, True)
+    torch.cuda.synchronize()
+    fast, exact = _host(fast).astype(np.float64), _host(exact).astype(np.float64)
+    assert np.isfinite(fast).all()
+    ref = _ref64_volume(coef, call)
+    assert fast.shape == ref.shape == exact.shape
+    e_fe = float(np.abs(fast - exact).max())
+    e_fr = float(np.abs(fast - ref).max())
+    e_er = float(np.abs(exact - ref).max())
+    assert e_fe <= TOL, (name, kernel, e_fe)
+    assert e_fr <= REF64_TOL, (name, kernel, e_fr)
+    assert e_er <= REF64_TOL, (name, kernel, e_er)
+    nz = fast.shape[0]
+    zs = sorted({0, nz - 1})
+    e_or = 0.0
+    for z, want in zip(zs, _oracle_planes(ora, coef, call, zs)):
+        f32 = np.float32
+        assert np.abs(fast[z] - want).max() <= TOL, (name, z)
+        assert (exact[z].astype(f32).view(np.uint32) == want.view(np.uint32)).all(), (name, z)
+        if kernel in (EXACT_LDS, DIRECT):
+            assert (fast[z].astype(f32).view(np.uint32) == want.view(np.uint32)).all(), (name, z)
+        e_or = max(e_or, float(np.abs(want - ref[z]).max()))
+    print(f"{name}: {kernel} |fast-exact| {e_fe:.3g} |fast-ref64| {e_fr:.3g} |exact-ref64| {e_er:.3g} |oracle-ref64| {e_or:.3g}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("nb", (6, 7, 8))
+def test_six_to_eight_band_points_bit_exact(wn, ora, tiles, nb):
+    """WMultibandNoise point lists above five bands (multiband3d_points_kernel) against the oracle's composition."""
+    objs, coefs = tiles
+    rng = np.random.default_rng(nb)
+    pts = rng.uniform(-6.0, 6.0, (4000, 3)).astype(np.float32)
+    w = rng.uniform(0.25, 2.0, nb).astype(np.float32)
+    for s, first in ((-16.0, -3), (-4.0, -5), (-16.0, 0)):
+        got = _host(objs["t128"].WMultibandNoise(pts, s, first, nb, w))
+        want = ora.multiband3d(coefs["t128"], pts, s, first, nb, w, 0.18402)
+        assert (got.view(np.uint32) == want.view(np.uint32)).all(), (nb, s, first)
+
+
+if __name__ == "__main__" and "--child" in sys.argv:
+    _child()

@@ -190,20 +190,26 @@ def test_volume_goldens(wn, gold, artefacts, noise3):
 
 
 @pytest.mark.parametrize("den,nx,ny,z0,z1,octave", [
-    (512, 512, 24, 0, 8, 4),        # config-2 step .25, full-width rows
-    (512, 512, 9, 505, 512, 4),     # last planes, ragged y
+    (512, 512, 24, 0, 8, 4),        # config-2 step .25, full-width rows (the plane pipeline takes it)
+    (512, 512, 9, 505, 512, 4),     # last planes, ragged y (plane pipeline)
     (512, 300, 17, 3, 6, 4),        # nx not a multiple of 256; thin slab (BZ=4)
     (512, 131, 5, 7, 8, 4),         # nx not a multiple of 4 -> scalar stores; one plane
-    (2048, 2048, 8, 1000, 1009, 4), # config-5 step 1/16, 9 planes
+    (2048, 2048, 8, 1000, 1009, 4), # config-5 step 1/16, 9 planes (plane pipeline)
     (1024, 515, 20, 0, 2, 4),       # step 1/8
-    (256, 256, 16, 0, 16, 3),       # step .25 at octave 3
-    (512, 512, 8, 4096, 4104, 4),   # z beyond one tile period (weak-scaling shards)
+    (256, 256, 16, 0, 16, 3),       # step .25 at octave 3 (rows of 256: the strip kernel takes it)
+    (512, 512, 8, 4096, 4104, 4),   # z beyond one tile period (weak-scaling shards) (plane pipeline)
     (768, 768, 8, 0, 8, 4),         # non power-of-two divisor, step 1/6
-    (1000, 1000, 8, 0, 8, 4),       # inexact float division in the lattice coordinate
+    (1000, 1000, 8, 0, 8, 4),       # inexact float division in the lattice coordinate (plane pipeline, partial x-brick)
     (768, 768, 9, 3, 40, 4),        # 256-wide bricks, 16 planes deep (37 planes: two full bricks and a ragged one in z)
     (1280, 640, 5, 0, 21, 4),       # step .1: 256-wide bricks with a half-empty last column, 16-plane bricks
+    (512, 998, 9, 0, 20, 4),        # 512-wide bricks, 8 planes deep, ragged in x, y and z (nx % 4: not the pipeline)
+    (712, 768, 5, 3, 12, 4),        # step .1798, just below the strip kernel's regime; inexact division
+    (512, 928, 7, 1, 10, 4),        # the pipeline would pad its last brick by more than 10 %
 ])
 def test_brick_path_vs_oracle(wn, ora, noise3, tile3d_128, den, nx, ny, z0, z1, octave):
+    """The default path against the oracle, the exact kernel bit-exact.  Named after the brick kernel, but the plane
+    pipeline and the strip kernel take the lattices marked so (the first fitting kernel serves: tests/test_gpu_dispatch.py
+    pins which kernel serves each of the last three)."""
     want = ora.grid_wavelet3d_volume(tile3d_128, den, nx, ny, z0, z1, octave)
     fast = host(wn.wavelet_volume(noise3, den, nx, ny, z0, z1, octave))
     assert fast.shape == want.shape
@@ -215,15 +221,19 @@ def test_brick_path_vs_oracle(wn, ora, noise3, tile3d_128, den, nx, ny, z0, z1, 
 
 @pytest.mark.parametrize("den,nx,ny,z0,z1,octave", [
     (512, 256, 4, 0, 300, 4),       # three z chunks of 100 planes, one column block
-    (512, 512, 3, 17, 18, 4),       # a single plane
+    (512, 512, 3, 17, 18, 4),       # a single plane (the plane pipeline takes it)
     (400, 512, 6, 0, 40, 4),        # step .32, close to the 1/3 limit of the window scheme
     (700, 768, 5, 0, 20, 4),        # step .183, just inside the regime; inexact division; 3 column blocks
-    (512, 1024, 3, 100, 140, 4),    # x beyond one lattice period
-    (512, 512, 2, 8190, 8200, 4),   # large z offset
+    (512, 1024, 3, 100, 140, 4),    # x beyond one lattice period (plane pipeline)
+    (512, 512, 2, 8190, 8200, 4),   # large z offset (plane pipeline)
+    (448, 512, 6, 0, 40, 4),        # step 2/7: too coarse for the plane pipeline (K = 6), strip kernel
+    (385, 256, 5, 9, 30, 4),        # step .3325, the largest step inside the regime
+    (711, 768, 7, 2, 40, 4),        # step .18003, the smallest
+    (512, 768, 5, 4000, 4033, 4),   # large z offset, 3 column blocks
 ])
 def test_strip_path_vs_oracle(wn, ora, noise3, tile3d_128, den, nx, ny, z0, z1, octave):
     """Lattices in the strip-march kernel's regime (rows of k*256 samples, 0.18 <= step <= 1/3):
-    chunk seams, single planes, the regime's edges."""
+    chunk seams, single planes, the regime's edges.  The plane pipeline comes first and takes the lattices marked so."""
     want = ora.grid_wavelet3d_volume(tile3d_128, den, nx, ny, z0, z1, octave)
     fast = host(wn.wavelet_volume(noise3, den, nx, ny, z0, z1, octave))
     assert fast.shape == want.shape
@@ -232,10 +242,12 @@ def test_strip_path_vs_oracle(wn, ora, noise3, tile3d_128, den, nx, ny, z0, z1, 
 
 
 @pytest.mark.parametrize("den,nx,ny,z0,z1", [
-    (512, 512, 300, 0, 512),        # 2400 items on 2048 wave slots: second-round items change segment
+    (512, 512, 300, 0, 512),        # (the plane pipeline takes it)
     (512, 768, 170, 3, 260),        # ragged last chunk, 3 column blocks, odd row count
-    (512, 512, 2048, 1, 255),       # 1024 groups: one range of 254 planes walked in two items of 127 (odd)
+    (512, 512, 2048, 1, 255),       # (the plane pipeline takes it)
     (400, 256, 2052, 0, 301),       # step .32: 513 groups, a range of 301 planes in items of 76, 75, 75, 75
+    (448, 512, 300, 0, 128),        # step 2/7 (not the pipeline's): 150 groups of 2-segment rows, 4 ranges of 32 planes
+    (416, 512, 2048, 1, 255),       # step .3077: 1024 groups, one range of 254 planes walked in 3 items of 85
 ])
 def test_strip_path_many_items_vs_exact_kernel(wn, ora, tile3d_128, noise3, den, nx, ny, z0, z1):
     """More items than resident compute waves.  Checker for the whole lattice: the exact kernel (bit-identical to the
@@ -833,19 +845,22 @@ def test_full_512_cubed_perlin_and_turb_planes_and_properties(wn, ora):
 
 # ---- WMultibandNoise on dense lattices: the plane-pipeline kernel (wn_wavelet_multiband.hip) ------------------------------
 def test_multiband_plane_pipeline_shapes_vs_exact_kernel_and_oracle(wn, ora, noise3, tile3d_128):
-    """Wide lattices of 2..5 bands go to grid3d_mbp_kernel (12-wave workgroups: compute waves + store waves around one
-    barrier per plane).  Edge bricks in x / y / z, slabs that do not start at plane 0, band counts, weights, first bands
+    """Wide lattices of 2..5 bands go to grid3d_mbp_kernel (16-wave workgroups: window, collapse and store waves around
+    one barrier per plane) -- except those whose last 512-wide brick would be more than 10 % padding (516, 1028, 768
+    below), which the brick kernel serves (tests/test_gpu_dispatch.py pins both).  Edge bricks in x / y / z, slabs that do not start at plane 0, band counts, weights, first bands
     and `s` cut-offs: every case against the bit-exact kernel (itself bit-identical to the oracle composition, checked
     in test_multiband_grid_and_points) on the whole lattice, and two planes per case against the oracle itself."""
     cases = [  # den, nx, ny, z0, z1, s, first, nbands, w
         (512, 512, 24, 3, 14, -16.0, 0, 5, [1.0, 1.0, 1.0, 1.0, 1.0]),
-        (512, 516, 13, 0, 11, -16.0, 0, 5, [1.0, 0.5, 2.0, 1.0, 0.25]),     # partial bricks in x, y and z
+        (512, 516, 13, 0, 11, -16.0, 0, 5, [1.0, 0.5, 2.0, 1.0, 0.25]),     # ragged in x, y and z: brick kernel <5, 1>
         (1024, 1024, 9, 5, 22, -16.0, 0, 5, [1.0, 1.0, 1.0, 1.0, 1.0]),    # two bricks in x, finer steps (K = 4 passes)
         (512, 512, 17, 100, 109, -16.0, 0, 4, [0.5, 2.0, 1.0, 1.0]),
-        (512, 1028, 8, 0, 8, -16.0, 1, 3, [1.0, 0.5, 2.0]),                 # three bricks in x, the last one 4 samples wide
+        (512, 1028, 8, 0, 8, -16.0, 1, 3, [1.0, 0.5, 2.0]),                 # 1028 wide: brick kernel <3, 1> (256-wide bricks)
         (512, 512, 8, 7, 9, -16.0, 2, 2, [1.0, 3.0]),
         (512, 512, 10, 0, 9, -3.0, 0, 5, [1.0, 1.0, 1.0, 1.0, 1.0]),        # s + b < 0 stops after 3 bands, variance over 5
-        (768, 768, 16, 60, 70, -16.0, 0, 5, [1.0, 1.0, 1.0, 1.0, 1.0]),     # den not a power of two (division kept)
+        (1000, 1000, 11, 3, 14, -16.0, -1, 5, [1.0, 0.5, 2.0, 1.0, 0.25]),  # partial x-brick (488 of 512) in the pipeline
+        (960, 960, 9, 9, 18, -4.0, -1, 6, [2.0, 1.0, 0.5, 1.0, 1.0, 1.0]),   # s stops after 5 of 6 bands, partial x-brick
+        (768, 768, 16, 60, 70, -16.0, 0, 5, [1.0, 1.0, 1.0, 1.0, 1.0]),     # den not a power of two: brick kernel <5, 1>
     ]
     for den, nx, ny, z0, z1, s, first, nb, w in cases:
         fast = wn.multiband_volume(noise3, den, nx, ny, z0, z1, s, first, nb, w)
