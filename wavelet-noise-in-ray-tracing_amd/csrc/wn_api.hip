@@ -103,6 +103,25 @@ int check_handle_device(int handle_device, const char *what)
     return WN_OK;
 }
 
+int check_tile(const wn_tile *tile, int dims, const char *entry)
+{
+    int rc = require_device();
+    if (rc) return rc;
+    if (!tile) return fail(WN_ERR_INVALID, "%s: tile is NULL", entry);
+    if (!tile->count) return WN_OK;
+    if ((rc = check_handle_device(tile->device, "tile")) != WN_OK) return rc;
+    if (tile->dims != dims) return fail(WN_ERR_INVALID, "%s needs a %d-D tile (got a %d-D one)", entry, dims, tile->dims);
+    return WN_OK;
+}
+
+int check_perm(const wn_perm *perm, const char *entry)
+{
+    const int rc = require_device();
+    if (rc) return rc;
+    if (!perm) return fail(WN_ERR_INVALID, "%s: perm is NULL", entry);
+    return check_handle_device(perm->device, "perm");
+}
+
 static thread_local char g_err[512] = "";
 
 void set_error(const char *fmt, ...)

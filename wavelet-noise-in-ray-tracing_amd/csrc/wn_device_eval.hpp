@@ -86,6 +86,20 @@ __device__ __forceinline__ float eval3d_exact(const float *coef, int n, int nmas
                       : eval3d_exact_impl<PADDED, false>(coef, n, nmask, px, py, pz);
 }
 
+// WMultibandNoise (paper Appendix 2, normal == NULL): sum_b w[b] * evaluate3D(2 * p * 2^(first_band+b)), divided by
+// out_div when apply_div.  `a` carries coef, n, nmask and the bands of wn::multiband_bands.
+template <bool PADDED, typename A>
+__device__ __forceinline__ float multiband3d_exact(const A &a, const float p[3])
+{
+    float v = 0.0f;
+    for (int b = 0; b < a.nbands; ++b) {
+        const float s = a.band_scale[b];
+        v += a.band_w[b] * eval3d_exact<PADDED>(a.coef, a.n, a.nmask, 2.0f * p[0] * s, 2.0f * p[1] * s, 2.0f * p[2] * s);
+    }
+    if (a.apply_div) v /= a.out_div;
+    return v;
+}
+
 // evaluate3D on the padded tile with two of its y rows held in LDS: `slab` = [z][2][n + 2], the rows (ry - 1) mod n and ry of
 // every z plane.  A point whose middle y row is ry takes its first two row triples (fy = 0, 1 of every fz) from the slab and
 // the third from memory -- 3 scattered 12-byte gathers instead of 9; any other point takes all nine from memory.  Same

@@ -5,6 +5,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdarg>
 #include <cstddef>
 #include <cstdint>
@@ -98,18 +99,87 @@ int device_compute_units(int dev);
 bool ensure_dynamic_lds(const void *kernel, int dev, size_t bytes);
 // WN_ERR_INVALID unless the handle (tile / perm) lives on the current device.
 int check_handle_device(int handle_device, const char *what);
+// The first checks of a batched entry point (`entry` names it in the message): a HIP device, then a handle that lives on
+// the current device; a tile that is not empty must also have `dims` dimensions.
+int check_tile(const wn_tile *tile, int dims, const char *entry);
+int check_perm(const wn_perm *perm, const char *entry);
 
-// wn_wavelet_strip.hip: launches the strip-march kernel when the lattice is in its regime.
-int strip_try(const wn_tile *tile, const GridArgs &g, float *out_dev, hipStream_t stream, bool *launched);
+// Rows of nx floats from `out` all start 16-byte aligned: float4 stores.
+inline bool vec4_ok(const float *out, int nx) { return nx % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0; }
 
-// wn_wavelet_multiband.hip: launches the plane-pipeline kernel when a lattice of 1..5 bands is in its regime (g carries the
-// bands' common post_scale; oscale / weights per band; out_div = sqrt(sum w^2 * variance)) and has at least
-// min_bricks_per_cu bricks of 512 x 8 x 8 samples per compute unit.
+// 256-lane workgroups for a grid-stride loop over `total` items: at least one, at most `cap`.
+inline int stride_blocks(size_t total, size_t cap)
+{
+    const size_t b = (total + 255) / 256;
+    return (int)(b < 1 ? 1 : (b > cap ? cap : b));
+}
+
+// One band's lattice step (cells per sample) and the bounds that the dense-grid planners derive from it.
+struct LatticeStep {
+    double step;  // base_range * oscale * post_scale / den
+    double pmax;  // bound on a coordinate, + 1
+    double slack; // fp32 rounding of a coordinate (4 ulp of pmax), + the planner's margin
+    // cells whose basis functions reach `samples` consecutive samples
+    long long extent(int samples) const { return (long long)floor((samples - 1) * step + slack) + 1 + 3; }
+    // 4 consecutive samples span <= 2 mids
+    bool two_mids() const { return 3.0 * step + slack <= 1.0; }
+};
+
+// false when the step of the band at `oscale` is not finite or negative (signed_step: its magnitude is used), or when a
+// coordinate could pass 1e6 cells (mids stay far inside the int / float-exact range).  pmax covers indices up to
+// max(nx, ny, |z0| + nz), and |z_const| on top when with_z_const; margin_cells is added to slack.
+inline bool lattice_step(const GridArgs &g, float oscale, bool with_z_const, bool signed_step, double margin_cells,
+                         LatticeStep *ls)
+{
+    double step = (double)g.base_range * (double)oscale * (double)g.post_scale / g.den;
+    if (signed_step) step = fabs(step);
+    if (!(step >= 0.0) || !std::isfinite(step)) return false;
+    const double imax = fmax(fmax((double)g.nx, (double)g.ny), fabs((double)g.z0) + g.nz);
+    const double pmax = step * imax + (with_z_const ? fabs((double)g.z_const) : 0.0) + 1.0;
+    if (pmax > 1.0e6) return false;
+    *ls = LatticeStep{step, pmax, pmax * 4.8e-7 + margin_cells};
+    return true;
+}
+
+// WMultibandNoise (Cook & DeRose, Appendix 2): bands run while s + first_band + b < 0, band b at 2^(first_band+b) with
+// weight w_host[b]; the variance sums ALL nbands.  Checks nbands / w_host, then fills a's nbands (the active bands),
+// band_scale, band_w, apply_div and out_div.
+constexpr int kMaxBands = 8;
+template <typename Args>
+int multiband_bands(float s, int first_band, int nbands, const float *w_host, float var_per_band, Args *a)
+{
+    if (nbands < 0 || nbands > kMaxBands)
+        return fail(WN_ERR_INVALID, "nbands must be in 0..%d (got %d)", kMaxBands, nbands);
+    if (nbands && !w_host) return fail(WN_ERR_INVALID, "w_host is NULL");
+    int active = 0;
+    while (active < nbands && s + (float)first_band + (float)active < 0.0f) ++active;
+    float variance = 0.0f;
+    for (int b = 0; b < nbands; ++b) variance += w_host[b] * w_host[b];
+    a->nbands = active;
+    for (int b = 0; b < active; ++b) {
+        a->band_scale[b] = ldexpf(1.0f, first_band + b);
+        a->band_w[b] = w_host[b];
+    }
+    a->apply_div = variance != 0.0f;
+    a->out_div = a->apply_div ? sqrtf(variance * var_per_band) : 1.0f;
+    return WN_OK;
+}
+
+// The *_try functions below launch their kernel when the lattice is in its regime and return WN_OK (or the launch's
+// error); outside it they launch nothing and return kDeclined, and the caller offers the lattice to the next kernel.
+constexpr int kDeclined = -1;
+
+// wn_wavelet_strip.hip: the strip-march kernel.
+int strip_try(const wn_tile *tile, const GridArgs &g, float *out_dev, hipStream_t stream);
+
+// wn_wavelet_multiband.hip: the plane-pipeline kernel, for lattices of 1..5 bands (g carries the bands' common
+// post_scale; oscale / weights per band; out_div = sqrt(sum w^2 * variance)) with at least min_bricks_per_cu bricks of
+// 512 x 8 x 8 samples per compute unit.
 int multiband_try(const wn_tile *tile, const GridArgs &g, int nbands, const float *oscale, const float *weights,
-                  float out_div, float *out_dev, hipStream_t stream, bool *launched, int min_bricks_per_cu);
+                  float out_div, float *out_dev, hipStream_t stream, int min_bricks_per_cu);
 
-// wn_wavelet_exact.hip: bit-exact dense 3-D grids with the coefficient box staged in LDS; *launched tells the caller.
-int exact_lds_try(const wn_tile *tile, const GridArgs &g, float *out_dev, hipStream_t stream, bool *launched);
+// wn_wavelet_exact.hip: bit-exact dense 3-D grids with the coefficient box staged in LDS.
+int exact_lds_try(const wn_tile *tile, const GridArgs &g, float *out_dev, hipStream_t stream);
 
 // wn_tilegen.hip: the filter half of generateNoiseTile2D/3D on the device.
 int tilegen_filter(wn_tile *t, const float *field_dev, hipStream_t stream);

@@ -403,20 +403,13 @@ __global__ __launch_bounds__(256) void noise_texture_kernel(const NoiseTexArgs a
     }
 }
 
-inline int blocks_for(size_t total)
-{
-    size_t b = (total + 255) / 256;
-    const size_t cap = 256u * 8u * 8u;
-    return (int)(b < 1 ? 1 : (b > cap ? cap : b));
-}
+constexpr size_t kBlockCap = 256u * 8u * 8u; // workgroups of a grid-stride launch (wn::stride_blocks)
 
 int perlin_grid(const wn_perm *perm, const wn_grid *grid, int kind, int depth, float *out_dev,
                 void *stream)
 {
-    int rc = wn::require_device();
+    int rc = wn::check_perm(perm, "perlin grid");
     if (rc) return rc;
-    if (!perm) return wn::fail(WN_ERR_INVALID, "perm is NULL");
-    if ((rc = wn::check_handle_device(perm->device, "perm")) != WN_OK) return rc;
     GridArgs g;
     rc = wn::check_grid(grid, true, &g);
     if (rc) return rc;
@@ -425,7 +418,7 @@ int perlin_grid(const wn_perm *perm, const wn_grid *grid, int kind, int depth, f
     if (!out_dev) return wn::fail(WN_ERR_INVALID, "out_dev is NULL");
     if ((size_t)g.nx * g.ny > 0xffffffffull) return wn::fail(WN_ERR_INVALID, "plane too large");
     PerlinGridArgs a{perm->dev, out_dev, g, kind, depth, 0};
-    a.vec4_ok = (g.nx % 4 == 0) && ((reinterpret_cast<uintptr_t>(out_dev) & 15) == 0);
+    a.vec4_ok = wn::vec4_ok(out_dev, g.nx);
     const int octaves = kind == kNoise ? 1 : (kind == kFractal ? 6 : depth);
     const dim3 rgrid((g.nx + kRunX - 1) / kRunX, (g.ny + kRunTY - 1) / kRunTY, (g.nz + kRunTZ - 1) / kRunTZ);
     // the run kernel: rows of >= 128 samples (a lane owns 8 consecutive x samples), 1..8 octaves
@@ -449,7 +442,7 @@ int perlin_grid(const wn_perm *perm, const wn_grid *grid, int kind, int depth, f
             return WN_OK;
         }
     }
-    hipLaunchKernelGGL(perlin_grid_generic_kernel, dim3(blocks_for(total)), dim3(256), 0,
+    hipLaunchKernelGGL(perlin_grid_generic_kernel, dim3(wn::stride_blocks(total, kBlockCap)), dim3(256), 0,
                        wn::as_stream(stream), a);
     WN_LAUNCH_CHECK("perlin_grid_generic_kernel");
     return WN_OK;
@@ -458,14 +451,11 @@ int perlin_grid(const wn_perm *perm, const wn_grid *grid, int kind, int depth, f
 int perlin_points(const wn_perm *perm, const double *p64, const float *p32, size_t n, int kind,
                   int depth, double *out_dev, void *stream)
 {
-    int rc = wn::require_device();
-    if (rc) return rc;
-    if (!perm) return wn::fail(WN_ERR_INVALID, "perm is NULL");
-    if ((rc = wn::check_handle_device(perm->device, "perm")) != WN_OK) return rc;
-    if (n == 0) return WN_OK;
+    const int rc = wn::check_perm(perm, "perlin points");
+    if (rc || n == 0) return rc;
     if ((!p64 && !p32) || !out_dev) return wn::fail(WN_ERR_INVALID, "points/out pointer is NULL");
     PerlinPointsArgs a{perm->dev, p64, p32, out_dev, n, kind, depth};
-    hipLaunchKernelGGL(perlin_points_kernel, dim3(blocks_for(n)), dim3(256), 0,
+    hipLaunchKernelGGL(perlin_points_kernel, dim3(wn::stride_blocks(n, kBlockCap)), dim3(256), 0,
                        wn::as_stream(stream), a);
     WN_LAUNCH_CHECK("perlin_points_kernel");
     return WN_OK;
@@ -522,11 +512,8 @@ int wn_noise_texture_points(const wn_perm *perm, double scale, int octave, const
                             const uint8_t *active_dev, size_t n, float *grey_dev, void *stream)
 {
     WN_ENTRY();
-    int rc = wn::require_device();
-    if (rc) return rc;
-    if (!perm) return wn::fail(WN_ERR_INVALID, "perm is NULL");
-    if ((rc = wn::check_handle_device(perm->device, "perm")) != WN_OK) return rc;
-    if (n == 0) return WN_OK;
+    const int rc = wn::check_perm(perm, "wn_noise_texture_points");
+    if (rc || n == 0) return rc;
     if (!xyz_dev || !grey_dev) return wn::fail(WN_ERR_INVALID, "points/grey pointer is NULL");
     NoiseTexArgs a{};
     a.perm = perm->dev;

@@ -129,22 +129,17 @@ __global__ __launch_bounds__(64 * kWaves) void grid3d_exact_lds_kernel(const Exa
 
 namespace wn {
 
-// Launches the LDS-staged exact kernel when every brick's coefficient box fits; *launched tells the caller.
-int exact_lds_try(const wn_tile *tile, const GridArgs &g, float *out_dev, hipStream_t stream, bool *launched)
+// Launches the LDS-staged exact kernel when every brick's coefficient box fits.  Steps of either sign are accepted (the
+// kernel bounds a box by the mids of its first and last samples), and slack has one cell of margin.
+int exact_lds_try(const wn_tile *tile, const GridArgs &g, float *out_dev, hipStream_t stream)
 {
-    *launched = false;
-    if (tile->n == 0 || g.nx <= 0 || g.ny <= 0 || g.nz <= 0) return WN_OK;
-    if (g.nx < 64) return WN_OK; // narrow grids: most of a 256-sample brick would idle
-    const double step = fabs((double)g.base_range * (double)g.octave_scale * (double)g.post_scale / g.den);
-    if (!std::isfinite(step)) return WN_OK;
-    const double imax = std::max(std::max((double)g.nx, (double)g.ny), fabs((double)g.z0) + g.nz);
-    const double pmax = step * imax + fabs((double)g.z_const) + 1.0;
-    if (pmax > 1.0e6) return WN_OK; // keep mids far inside int / float-exact range
-    const double slack = pmax * 4.8e-7 + 1.0; // rounding of a coordinate, and one cell of margin
-    auto extent = [&](int samples) { return (long long)floor((samples - 1) * step + slack) + 1 + 3; };
-    const long long ez = g.z_const_mode ? 3 : extent(kEZ);
-    const long long box_floats = extent(kEX) * extent(kEY) * ez;
-    if (box_floats > kMaxBoxFloats) return WN_OK; // coarse lattice: the gather kernel
+    if (tile->n == 0 || g.nx <= 0 || g.ny <= 0 || g.nz <= 0) return kDeclined;
+    if (g.nx < 64) return kDeclined; // narrow grids: most of a 256-sample brick would idle
+    LatticeStep ls;
+    if (!lattice_step(g, g.octave_scale, true, true, 1.0, &ls)) return kDeclined;
+    const long long ez = g.z_const_mode ? 3 : ls.extent(kEZ);
+    const long long box_floats = ls.extent(kEX) * ls.extent(kEY) * ez;
+    if (box_floats > kMaxBoxFloats) return kDeclined; // coarse lattice: the gather kernel
     ExactArgs a{};
     a.coef = tile->dev;
     a.out = out_dev;
@@ -154,13 +149,12 @@ int exact_lds_try(const wn_tile *tile, const GridArgs &g, float *out_dev, hipStr
     a.nbx = (g.nx + kEX - 1) / kEX;
     a.nby = (g.ny + kEY - 1) / kEY;
     a.nbz = (g.nz + kEZ - 1) / kEZ;
-    if (a.nby > 65535 || a.nbz > 65535) return WN_OK;
-    a.vec4_ok = (g.nx % 4 == 0) && ((reinterpret_cast<uintptr_t>(out_dev) & 15) == 0);
+    if (a.nby > 65535 || a.nbz > 65535) return kDeclined;
+    a.vec4_ok = vec4_ok(out_dev, g.nx);
     a.box_cap = (int)box_floats;
     const size_t lds = (size_t)box_floats * sizeof(float); // <= 48 KB: no opt-in needed
     hipLaunchKernelGGL(grid3d_exact_lds_kernel, dim3(a.nbx, a.nby, a.nbz), dim3(64 * kWaves), lds, stream, a);
     WN_LAUNCH_CHECK("grid3d_exact_lds_kernel");
-    *launched = true;
     return WN_OK;
 }
 

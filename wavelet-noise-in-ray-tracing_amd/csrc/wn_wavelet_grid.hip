@@ -37,7 +37,7 @@ using wn::GridArgs;
 
 typedef float v4f __attribute__((ext_vector_type(4)));
 
-constexpr int kMaxBands = 8;
+using wn::kMaxBands;
 constexpr int kBrickY = 8;    // sample rows per brick along y
 constexpr int kMaxBZ = 16;    // ... and along z (power of two: 16 for fine single-band lattices, 8, fewer for thin slabs)
 constexpr int kSlotZ = 8, kSlotX = kSlotZ + kMaxBZ; // table slots: 0..7 y samples, 8..23 z samples, 24/25 first/last x sample
@@ -577,12 +577,7 @@ __global__ __launch_bounds__(256) void grid3d_projected_kernel(const ProjGridArg
     }
 }
 
-inline int grid_blocks(size_t total)
-{
-    size_t b = (total + 255) / 256;
-    const size_t cap = 256u * 8u * 4u;
-    return (int)(b < 1 ? 1 : (b > cap ? cap : b));
-}
+constexpr size_t kBlockCap = 256u * 8u * 4u; // workgroups of a grid-stride launch (wn::stride_blocks)
 
 inline int ceil_pow2(int v)
 {
@@ -612,25 +607,18 @@ bool plan_sep_bz(const wn_tile *tile, const GridArgs &g, int nbands, const float
     if (!g.z_const_mode && g.z0 < 0) return false; // negative plane indices: the exact kernel (bounds below assume indices >= 0)
     const int BZ = g.nz >= bz_cap ? bz_cap : ceil_pow2(g.nz); // planes per brick
     const int rows = kBrickY * BZ;
-    const double zmax = g.z_const_mode ? 0.0 : (double)g.z0 + g.nz;
-    const double imax = fmax(fmax((double)g.nx, (double)g.ny), zmax);
     size_t box_total = 0, r_total = 0;
     int exs[kMaxBands];
     for (int b = 0; b < nbands; ++b) {
-        const double step = (double)g.base_range * (double)oscale[b] * (double)g.post_scale / g.den;
-        if (!(step >= 0.0) || !std::isfinite(step)) return false;
-        const double pmax = step * imax + fabs((double)g.z_const) + 1.0;
-        if (pmax > 1.0e6) return false; // keep mids far inside int / float-exact range
-        const double slack = pmax * 4.8e-7; // 4 ulp of the largest coordinate
-        if (3.0 * step + slack > 1.0) return false; // 4 consecutive samples span <= 2 mids
-        auto extent = [&](int samples) { return (int)floor((samples - 1) * step + slack) + 1 + 3; };
-        exs[b] = extent(kBrickX) + 1;
-        if (extent(kBrickY) > kBoxY || (!g.z_const_mode && extent(BZ) > kBoxZ)) return false;
-        {   // the kernel's compile-time bounds per band (bands of one call are consecutive octaves)
-            const int d = nbands - 1 - b;
-            const int ez = g.z_const_mode ? 3 : extent(BZ);
-            if (extent(kBrickY) * ez > box_rows_bound(d) || exs[b] > 64 * box_col_groups(d, kBrickX)) return false;
-        }
+        // pmax covers |z_const| even when z is a lattice index
+        wn::LatticeStep ls;
+        if (!wn::lattice_step(g, oscale[b], true, false, 0.0, &ls) || !ls.two_mids()) return false;
+        const int ey = (int)ls.extent(kBrickY), ez = g.z_const_mode ? 3 : (int)ls.extent(BZ);
+        exs[b] = (int)ls.extent(kBrickX) + 1;
+        if (ey > kBoxY || ez > kBoxZ) return false;
+        // the kernel's compile-time bounds per band (bands of one call are consecutive octaves)
+        const int d = nbands - 1 - b;
+        if (ey * ez > box_rows_bound(d) || exs[b] > 64 * box_col_groups(d, kBrickX)) return false;
         a->band[b].oscale = oscale[b];
         a->band[b].factor = (float)((double)(weights ? weights[b] : 1.0f) * (double)g.out_scale / (double)out_div);
         a->band[b].ex_cap = exs[b];
@@ -726,16 +714,15 @@ bool launch_sep(const SepArgs &a, size_t lds, hipStream_t s)
     return a.xw == 2 ? launch_sep2<NB, 2>(a, lds, s) : launch_sep2<NB, 1>(a, lds, s);
 }
 
-// Plans and launches the brick kernel when the lattice is in its regime and the runtime grants its LDS; *launched tells the caller.
+// Plans and launches the brick kernel when the lattice is in its regime and the runtime grants its LDS.
 int sep_try(const wn_tile *tile, const GridArgs &g, int nbands, const float *oscale, const float *weights, float out_div,
-            float *out_dev, hipStream_t stream, bool *launched)
+            float *out_dev, hipStream_t stream)
 {
-    *launched = false;
     SepArgs a{};
     size_t lds = 0;
-    if (!plan_sep(tile, g, nbands, oscale, weights, out_div, &a, &lds)) return WN_OK;
+    if (!plan_sep(tile, g, nbands, oscale, weights, out_div, &a, &lds)) return wn::kDeclined;
     a.out = out_dev;
-    a.vec4_ok = (g.nx % 4 == 0) && ((reinterpret_cast<uintptr_t>(out_dev) & 15) == 0);
+    a.vec4_ok = wn::vec4_ok(out_dev, g.nx);
     a.even_share_q10 = a.nbands == 1 ? 545 : 512;
     bool ok;
     switch (a.nbands) {
@@ -748,8 +735,7 @@ int sep_try(const wn_tile *tile, const GridArgs &g, int nbands, const float *osc
     case 7: ok = launch_sep<7>(a, lds, stream); break;
     default: ok = launch_sep<8>(a, lds, stream); break;
     }
-    if (!ok) return WN_OK;
-    *launched = true;
+    if (!ok) return wn::kDeclined;
     WN_LAUNCH_CHECK("grid3d_sep_kernel");
     return WN_OK;
 }
@@ -760,9 +746,9 @@ void launch_direct(const DirectArgs &d, const wn_tile *tile, size_t total, hipSt
     DirectArgs a = d;
     a.coef = tile->dev_padded ? tile->dev_padded : tile->dev;
     if (tile->dev_padded)
-        hipLaunchKernelGGL(grid3d_direct_kernel<true>, dim3(grid_blocks(total)), dim3(256), 0, stream, a);
+        hipLaunchKernelGGL(grid3d_direct_kernel<true>, dim3(wn::stride_blocks(total, kBlockCap)), dim3(256), 0, stream, a);
     else
-        hipLaunchKernelGGL(grid3d_direct_kernel<false>, dim3(grid_blocks(total)), dim3(256), 0, stream, a);
+        hipLaunchKernelGGL(grid3d_direct_kernel<false>, dim3(wn::stride_blocks(total, kBlockCap)), dim3(256), 0, stream, a);
 }
 
 } // namespace
@@ -774,11 +760,8 @@ extern "C" {
 int wn_eval3d_grid(const wn_tile *tile, const wn_grid *grid, float *out_dev, void *stream)
 {
     WN_ENTRY();
-    int rc = require_device();
+    int rc = check_tile(tile, 3, "wn_eval3d_grid");
     if (rc) return rc;
-    if (!tile) return fail(WN_ERR_INVALID, "tile is NULL");
-    if (tile->count && (rc = check_handle_device(tile->device, "tile")) != WN_OK) return rc;
-    if (tile->count && tile->dims != 3) return fail(WN_ERR_INVALID, "wn_eval3d_grid needs a 3-D tile");
     GridArgs g;
     rc = check_grid(grid, true, &g);
     if (rc) return rc;
@@ -786,8 +769,8 @@ int wn_eval3d_grid(const wn_tile *tile, const wn_grid *grid, float *out_dev, voi
     if (total == 0) return WN_OK;
     if (!out_dev) return fail(WN_ERR_INVALID, "out_dev is NULL");
 
+    const hipStream_t s = as_stream(stream);
     if (!(grid->flags & WN_GRID_EXACT)) {
-        bool launched = false;
         // The plane pipeline of wn_wavelet_multiband.hip with a single band (16-wave workgroups split into window / collapse /
         // store waves; the waves that store never compute or wait for a load): 512^3 91-93 us sustained against 101.9 for the
         // strip kernel, 1024^3 664 against 809 us and the 2048 x 2048 x 256 shard 646 against 710 us for the brick kernel
@@ -797,18 +780,12 @@ int wn_eval3d_grid(const wn_tile *tile, const wn_grid *grid, float *out_dev, voi
         // each sums in its own order).  The strip and brick kernels serve what the pipeline does not cover (rows of 256 or 768
         // samples, steps above 2/7 of a cell).
         const float os1 = g.octave_scale, w1 = 1.0f;
-        rc = multiband_try(tile, g, 1, &os1, &w1, 1.0f, out_dev, as_stream(stream), &launched, 0);
-        if (rc || launched) return rc;
-        rc = strip_try(tile, g, out_dev, as_stream(stream), &launched); // rows of k*256 samples, >= 0.18 planes per step
-        if (rc || launched) return rc;
-        rc = sep_try(tile, g, 1, &os1, nullptr, 1.0f, out_dev, as_stream(stream), &launched);
-        if (rc || launched) return rc;
+        if ((rc = multiband_try(tile, g, 1, &os1, &w1, 1.0f, out_dev, s, 0)) != kDeclined) return rc;
+        if ((rc = strip_try(tile, g, out_dev, s)) != kDeclined) return rc; // rows of k*256 samples, >= 0.18 planes per step
+        if ((rc = sep_try(tile, g, 1, &os1, nullptr, 1.0f, out_dev, s)) != kDeclined) return rc;
     }
-    {   // bit-exact: the reference's 27-tap loop on an LDS-staged coefficient box when the bricks' boxes fit ...
-        bool launched = false;
-        rc = exact_lds_try(tile, g, out_dev, as_stream(stream), &launched);
-        if (rc || launched) return rc;
-    }
+    // bit-exact: the reference's 27-tap loop on an LDS-staged coefficient box when the bricks' boxes fit ...
+    if ((rc = exact_lds_try(tile, g, out_dev, s)) != kDeclined) return rc;
     // ... else on gathers from the tile
     DirectArgs d{};
     d.out = out_dev;
@@ -816,7 +793,7 @@ int wn_eval3d_grid(const wn_tile *tile, const wn_grid *grid, float *out_dev, voi
     d.nmask = pow2_mask(tile->n);
     d.g = g;
     d.nbands = 0;
-    launch_direct(d, tile, total, as_stream(stream));
+    launch_direct(d, tile, total, s);
     WN_LAUNCH_CHECK("grid3d_direct_kernel");
     return WN_OK;
 }
@@ -826,63 +803,36 @@ int wn_multiband3d_grid(const wn_tile *tile, const wn_grid *grid, float s, int f
                         void *stream)
 {
     WN_ENTRY();
-    int rc = require_device();
+    int rc = check_tile(tile, 3, "wn_multiband3d_grid");
     if (rc) return rc;
-    if (!tile) return fail(WN_ERR_INVALID, "tile is NULL");
-    if (tile->count && (rc = check_handle_device(tile->device, "tile")) != WN_OK) return rc;
-    if (tile->count && tile->dims != 3) return fail(WN_ERR_INVALID, "wn_multiband3d_grid needs a 3-D tile");
-    if (nbands < 0 || nbands > kMaxBands)
-        return fail(WN_ERR_INVALID, "nbands must be in 0..%d (got %d)", kMaxBands, nbands);
-    if (nbands && !w_host) return fail(WN_ERR_INVALID, "w_host is NULL");
+    DirectArgs d{};
+    rc = multiband_bands(s, first_band, nbands, w_host, var_per_band, &d);
+    if (rc) return rc;
     GridArgs g;
     rc = check_grid(grid, true, &g);
     if (rc) return rc;
     const size_t total = (size_t)g.nx * g.ny * g.nz;
     if (total == 0) return WN_OK;
     if (!out_dev) return fail(WN_ERR_INVALID, "out_dev is NULL");
-
-    // Appendix 2: bands run while s + firstBand + b < 0; the variance sums ALL nbands.
-    int active = 0;
-    while (active < nbands && s + (float)first_band + (float)active < 0.0f) ++active;
-    float variance = 0.0f;
-    for (int b = 0; b < nbands; ++b) variance += w_host[b] * w_host[b];
-    const bool apply_div = variance != 0.0f;
-    const float out_div = apply_div ? sqrtf(variance * var_per_band) : 1.0f;
-
-    float bscale[kMaxBands], wts[kMaxBands], oscale[kMaxBands];
-    for (int b = 0; b < active; ++b) {
-        bscale[b] = ldexpf(1.0f, first_band + b);
-        wts[b] = w_host[b];
-        // q = 2*p*2^(first+b): in lattice form octave_scale*2^(first+b), post 2.
-        oscale[b] = g.octave_scale * bscale[b];
-    }
-
-    // z_mode == WN_Z_CONST: band b sits at 2*z_const*2^(first_band+b), which the brick kernel's per-band
-    // tables do not model (they scale lattice indices, not a constant) -> the direct kernel
-    if (!(grid->flags & WN_GRID_EXACT) && active >= 1 && g.post_scale == 1.0f && !g.z_const_mode) {
-        GridArgs gb = g;
-        gb.post_scale = 2.0f;
-        bool launched = false;
-        // the plane-pipeline kernel (wn_wavelet_multiband.hip) takes wide lattices of 1..5 bands ...
-        rc = multiband_try(tile, gb, active, oscale, wts, out_div, out_dev, as_stream(stream), &launched, 0);
-        if (rc || launched) return rc;
-        // ... the brick kernel the rest
-        rc = sep_try(tile, gb, active, oscale, wts, out_div, out_dev, as_stream(stream), &launched);
-        if (rc || launched) return rc;
-    }
-    DirectArgs d{};
     d.out = out_dev;
     d.n = tile->n;
     d.nmask = pow2_mask(tile->n);
     d.g = g;
-    d.nbands = active;
-    for (int b = 0; b < active; ++b) {
-        d.band_scale[b] = bscale[b];
-        d.band_w[b] = wts[b];
+
+    // z_mode == WN_Z_CONST: band b sits at 2*z_const*2^(first_band+b), which the brick kernel's per-band
+    // tables do not model (they scale lattice indices, not a constant) -> the direct kernel
+    if (!(grid->flags & WN_GRID_EXACT) && d.nbands >= 1 && g.post_scale == 1.0f && !g.z_const_mode) {
+        // q = 2*p*2^(first+b): in lattice form octave_scale*2^(first+b), post 2.
+        float oscale[kMaxBands];
+        for (int b = 0; b < d.nbands; ++b) oscale[b] = g.octave_scale * d.band_scale[b];
+        GridArgs gb = g;
+        gb.post_scale = 2.0f;
+        // the plane-pipeline kernel (wn_wavelet_multiband.hip) takes wide lattices of 1..5 bands, the brick kernel the rest
+        if ((rc = multiband_try(tile, gb, d.nbands, oscale, d.band_w, d.out_div, out_dev, as_stream(stream), 0)) != kDeclined)
+            return rc;
+        if ((rc = sep_try(tile, gb, d.nbands, oscale, d.band_w, d.out_div, out_dev, as_stream(stream))) != kDeclined) return rc;
     }
-    d.out_div = out_div;
-    d.apply_div = apply_div ? 1 : 0;
-    if (active == 0) {
+    if (d.nbands == 0) {
         // no band contributes: result = 0 (/ out_div) * out_scale, evaluated on the device
         d.nbands = 1;
         d.band_scale[0] = 1.0f;
@@ -896,11 +846,8 @@ int wn_multiband3d_grid(const wn_tile *tile, const wn_grid *grid, float s, int f
 int wn_eval2d_grid(const wn_tile *tile, const wn_grid *grid, float *out_dev, void *stream)
 {
     WN_ENTRY();
-    int rc = require_device();
+    int rc = check_tile(tile, 2, "wn_eval2d_grid");
     if (rc) return rc;
-    if (!tile) return fail(WN_ERR_INVALID, "tile is NULL");
-    if (tile->count && (rc = check_handle_device(tile->device, "tile")) != WN_OK) return rc;
-    if (tile->count && tile->dims != 2) return fail(WN_ERR_INVALID, "wn_eval2d_grid needs a 2-D tile");
     GridArgs g;
     rc = check_grid(grid, false, &g);
     if (rc) return rc;
@@ -913,7 +860,7 @@ int wn_eval2d_grid(const wn_tile *tile, const wn_grid *grid, float *out_dev, voi
     d.n = tile->n;
     d.nmask = pow2_mask(tile->n);
     d.g = g;
-    hipLaunchKernelGGL(grid2d_direct_kernel, dim3(grid_blocks(total)), dim3(256), 0,
+    hipLaunchKernelGGL(grid2d_direct_kernel, dim3(wn::stride_blocks(total, kBlockCap)), dim3(256), 0,
                        as_stream(stream), d);
     WN_LAUNCH_CHECK("grid2d_direct_kernel");
     return WN_OK;
@@ -923,12 +870,9 @@ int wn_eval3d_projected_grid(const wn_tile *tile, const wn_grid *grid, const flo
                              float *out_dev, void *stream)
 {
     WN_ENTRY();
-    int rc = require_device();
+    int rc = check_tile(tile, 3, "wn_eval3d_projected_grid");
     if (rc) return rc;
-    if (!tile || !normal) return fail(WN_ERR_INVALID, "tile/normal is NULL");
-    if (tile->count && (rc = check_handle_device(tile->device, "tile")) != WN_OK) return rc;
-    if (tile->count && tile->dims != 3)
-        return fail(WN_ERR_INVALID, "wn_eval3d_projected_grid needs a 3-D tile");
+    if (!normal) return fail(WN_ERR_INVALID, "normal is NULL");
     GridArgs g;
     rc = check_grid(grid, true, &g);
     if (rc) return rc;
@@ -942,7 +886,7 @@ int wn_eval3d_projected_grid(const wn_tile *tile, const wn_grid *grid, const flo
     a.nmask = pow2_mask(tile->n);
     a.g = g;
     for (int i = 0; i < 3; ++i) a.normal[i] = normal[i];
-    hipLaunchKernelGGL(grid3d_projected_kernel, dim3(grid_blocks(total)), dim3(256), 0,
+    hipLaunchKernelGGL(grid3d_projected_kernel, dim3(wn::stride_blocks(total, kBlockCap)), dim3(256), 0,
                        as_stream(stream), a);
     WN_LAUNCH_CHECK("grid3d_projected_kernel");
     return WN_OK;

@@ -581,44 +581,36 @@ bool launch_mbp(const MbArgs &a, size_t lds, long long bricks, hipStream_t s)
 
 namespace wn {
 
-// Plans and launches the plane-pipeline kernel when the lattice is in its regime (else *launched = false and the
-// caller goes on to the strip / brick kernels): 1..5 consecutive-octave bands, rows wider than 256 samples and a multiple of 4,
-// power-of-two tile, every band's (y, z) box of 8 samples at most 5 rows, at most 8 passes of 64 box columns.
+// Plans and launches the plane-pipeline kernel when the lattice is in its regime (else the caller goes on to the strip /
+// brick kernels): 1..5 consecutive-octave bands, rows wider than 256 samples and a multiple of 4, power-of-two tile, every
+// band's (y, z) box of 8 samples at most 5 rows, at most 8 passes of 64 box columns.
 int multiband_try(const wn_tile *tile, const GridArgs &g, int nbands, const float *oscale, const float *weights,
-                  float out_div, float *out_dev, hipStream_t stream, bool *launched, int min_bricks_per_cu)
+                  float out_div, float *out_dev, hipStream_t stream, int min_bricks_per_cu)
 {
-    *launched = false;
-    if (nbands < 1 || nbands > kMaxNB || tile->n == 0 || wn::pow2_mask(tile->n) < 0) return WN_OK;
-    if (g.nx <= 256 || (g.nx & 3) || g.ny <= 0 || g.nz <= 0 || g.z_const_mode || g.z0 < 0) return WN_OK;
-    if (reinterpret_cast<uintptr_t>(out_dev) & 15) return WN_OK;
+    if (nbands < 1 || nbands > kMaxNB || tile->n == 0 || wn::pow2_mask(tile->n) < 0) return kDeclined;
+    if (g.nx <= 256 || !vec4_ok(out_dev, g.nx) || g.ny <= 0 || g.nz <= 0 || g.z_const_mode || g.z0 < 0) return kDeclined;
     MbArgs a{};
-    const double imax = std::max<double>(std::max(g.nx, g.ny), (double)g.z0 + g.nz);
     int passes = 0, box_off = 0;
     for (int w = 0; w < kPasses; ++w) a.pass_band[w] = -1;
     for (int b = 0; b < nbands; ++b) {
-        const double step = (double)g.base_range * (double)oscale[b] * (double)g.post_scale / g.den;
-        if (!(step >= 0.0) || !std::isfinite(step)) return WN_OK;
-        const double pmax = step * imax + 1.0;
-        if (pmax > 1.0e6) return WN_OK; // mids stay far inside the int / float-exact range
-        const double slack = pmax * 4.8e-7; // 4 ulp of the largest coordinate
-        if (3.0 * step + slack > 1.0) return WN_OK; // 4 consecutive samples span <= 2 mids
-        auto extent = [&](int samples) { return (int)floor((samples - 1) * step + slack) + 1 + 3; };
-        const int K = std::max(4, std::max(extent(kBY), extent(kBZ)));
-        if (K > kMaxK) return WN_OK;
-        const int ex = extent(kBX) + 1;
+        LatticeStep ls;
+        if (!lattice_step(g, oscale[b], false, false, 0.0, &ls) || !ls.two_mids()) return kDeclined;
+        const int K = (int)std::max<long long>(4, std::max(ls.extent(kBY), ls.extent(kBZ)));
+        if (K > kMaxK) return kDeclined;
+        const int ex = (int)ls.extent(kBX) + 1;
         const int np = (ex + 63) / 64;
-        if (passes + np > kPasses) return WN_OK;
+        if (passes + np > kPasses) return kDeclined;
         a.band[b].first_pass = passes;
         for (int p = 0; p < np; ++p) a.pass_band[passes++] = b;
         a.band[b].oscale = oscale[b];
         a.band[b].factor = (float)((double)(weights ? weights[b] : 1.0f) * (double)g.out_scale / (double)out_div);
         a.band[b].K = K;
         a.band[b].rowlen = (ex + 3 + 3) & ~3; // the box's columns + the <= 3 columns before its first one, whole 16-byte chunks
-        if (a.band[b].rowlen > 256) return WN_OK; // one chunk per lane
+        if (a.band[b].rowlen > 256) return kDeclined; // one chunk per lane
         a.band[b].box_off = box_off;
         box_off += K * K * a.band[b].rowlen;
     }
-    if (box_off > kBoxFloats) return WN_OK;
+    if (box_off > kBoxFloats) return kDeclined;
     const size_t lds = (size_t)(2 * kRPlane + kRingFloats) * sizeof(float);
     a.coef = tile->dev;
     a.out = out_dev;
@@ -631,12 +623,12 @@ int multiband_try(const wn_tile *tile, const GridArgs &g, int nbands, const floa
     a.nbz = (g.nz + kBZ - 1) / kBZ;
     a.all_full = (g.nx % kBX == 0 && g.ny % kBY == 0 && g.nz % kBZ == 0) ? 1 : 0;
     const long long bricks = (long long)a.nbx * a.nby * a.nbz;
-    if (bricks > 0x7fffffffLL / kBZ) return WN_OK;
+    if (bricks > 0x7fffffffLL / kBZ) return kDeclined;
     // (min_bricks_per_cu: a caller may keep small lattices away; the product passes 0 -- the kernel of a sample must not depend
     // on the thickness of the slab it is computed in.)  Every caller keeps away lattices whose last 512-wide brick column is
     // mostly padding (768 = 512 + 256: 394 us here, 314 us on 256-wide bricks).
-    if (bricks < (long long)min_bricks_per_cu * wn::device_compute_units(wn::current_device())) return WN_OK;
-    if ((long long)a.nbx * kBX * 10 > (long long)g.nx * 11) return WN_OK;
+    if (bricks < (long long)min_bricks_per_cu * wn::device_compute_units(wn::current_device())) return kDeclined;
+    if ((long long)a.nbx * kBX * 10 > (long long)g.nx * 11) return kDeclined;
     bool ok;
     switch (nbands) {
     case 1: ok = launch_mbp<1>(a, lds, bricks, stream); break;
@@ -645,8 +637,7 @@ int multiband_try(const wn_tile *tile, const GridArgs &g, int nbands, const floa
     case 4: ok = launch_mbp<4>(a, lds, bricks, stream); break;
     default: ok = launch_mbp<5>(a, lds, bricks, stream); break;
     }
-    if (!ok) return WN_OK; // the runtime refused the LDS opt-in: the brick kernel takes the lattice
-    *launched = true;
+    if (!ok) return kDeclined; // the runtime refused the LDS opt-in: the brick kernel takes the lattice
     WN_LAUNCH_CHECK("grid3d_mbp_kernel");
     return WN_OK;
 }

@@ -15,7 +15,7 @@
 
 namespace {
 
-constexpr int kMaxBands = 8;
+using wn::kMaxBands;
 
 struct PointsArgs {
     const float *coef;
@@ -68,14 +68,7 @@ __global__ __launch_bounds__(256) void multiband3d_points_kernel(const PointsArg
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.count;
          i += (size_t)gridDim.x * blockDim.x) {
         const float *p = a.pts + 3 * i;
-        float v = 0.0f;
-        for (int b = 0; b < a.nbands; ++b) {
-            const float s = a.band_scale[b];
-            v += a.band_w[b] * wn::eval3d_exact<PADDED>(a.coef, a.n, a.nmask, 2.0f * p[0] * s,
-                                                2.0f * p[1] * s, 2.0f * p[2] * s);
-        }
-        if (a.apply_div) v /= a.out_div;
-        a.out[i] = v;
+        a.out[i] = wn::multiband3d_exact<PADDED>(a, p);
     }
 }
 
@@ -204,6 +197,24 @@ constexpr int kSortChunk = 4096, kSortPlanes = 128, kSortXBits = 3, kSortPerThre
 constexpr int kSortBins = kSortPlanes << kSortXBits;
 constexpr size_t kSortMinPoints = 16 * (size_t)kSortChunk; // shorter lists: the plain kernels
 
+// The sort key of point i: the plane of its z tap's middle, then the top kSortXBits bits of its x tap's 64-byte line.
+template <typename Ops>
+__device__ __forceinline__ int sort_bin(const Ops &ops, size_t i)
+{
+    return ((ops.mid_z(i) & (kSortPlanes - 1)) << kSortXBits) | ((ops.mid_x(i) & 127) >> (7 - kSortXBits));
+}
+
+// Is the chunk's stream order coherent already?  Thread tid (< 256) looks at point min(tid, count - 1) of the chunk; each
+// wave adds to *changes how many of its points lie in another plane than their predecessor.
+template <typename Ops>
+__device__ __forceinline__ void count_plane_changes(const Ops &ops, size_t begin, int count, int tid, unsigned *changes)
+{
+    const int k = ops.mid_z(begin + min(tid, count - 1));
+    const int prev = __shfl_up(k, 1, 64);
+    const unsigned long long diff = __ballot((tid & 63) != 0 && prev != k);
+    if ((tid & 63) == 0) atomicAdd(changes, (unsigned)__popcll(diff));
+}
+
 // The kernel is generic over what a point is (`Ops`): count; active(i); mid_z(i) / mid_x(i) = the coefficient index of the
 // z / x tap's middle (of the finest band, where there are several); eval(i); store(i, v).
 // A chunk left to row_slab_points_kernel is marked in the output itself: this value (a NaN no evaluation produces; if one
@@ -263,12 +274,7 @@ __global__ __launch_bounds__(256) void plane_sorted_points_kernel(const Ops ops)
     // sample (the chunk's first 256 points): do neighbours of the stream change plane?  (A second test, "... and share
     // rows", would spare lists scattered in all three dimensions the 5 % the sorting passes cost them -- 25.4 -> 24.1 G
     // points/s -- but it also turns away curved surfaces, which gain: the stand-in's sphere hits, 1.19 -> 1.34 ms.)
-    {
-        const int k = ops.mid_z(begin + min(tid, count - 1));
-        const int prev = __shfl_up(k, 1, 64);
-        const unsigned long long diff = __ballot(lane != 0 && prev != k);
-        if (lane == 0) atomicAdd(&s_changes, (unsigned)__popcll(diff));
-    }
+    count_plane_changes(ops, begin, count, tid, &s_changes);
     __syncthreads();
     if (s_changes < 128) { // coherent already: stream order, no sorting passes
         for (int i = tid; i < count; i += 256)
@@ -283,7 +289,7 @@ __global__ __launch_bounds__(256) void plane_sorted_points_kernel(const Ops ops)
         key[k] = 0xffff;
         rank[k] = 0;
         if (i < count && ops.active(begin + i)) {
-            const int bin = ((ops.mid_z(begin + i) & (kSortPlanes - 1)) << kSortXBits) | ((ops.mid_x(begin + i) & 127) >> (7 - kSortXBits));
+            const int bin = sort_bin(ops, begin + i);
             key[k] = (unsigned short)bin;
             rank[k] = (unsigned short)atomicAdd(&hist[bin], 1u);
         }
@@ -337,12 +343,7 @@ struct TextureOps {
     TexArgs a;
     size_t count;
     __device__ bool active(size_t i) const { return !MASKED || a.active[i] != 0; }
-    __device__ int mid(float c) const // texture.h:71-80
-    {
-        float p = (float)((double)c * a.scale);
-        p *= a.octave_mul;
-        return mid_of(p);
-    }
+    __device__ int mid(float c) const { return mid_of(wn::wavelet_texture_coord(a, c)); }
     __device__ int mid_z(size_t i) const { return mid(a.pts[3 * i + 2]); }
     __device__ int mid_y(size_t i) const { return mid(a.pts[3 * i + 1]); }
     __device__ int mid_x(size_t i) const { return mid(a.pts[3 * i]); }
@@ -392,14 +393,8 @@ struct Eval3dOps {
     __device__ float eval(size_t i) const
     {
         const float *p = a.pts + 3 * i;
-        if (!MULTIBAND) return wn::eval3d_exact<PADDED>(a.coef, a.n, a.nmask, p[0], p[1], p[2]);
-        float v = 0.0f;
-        for (int b = 0; b < a.nbands; ++b) {
-            const float s = a.band_scale[b];
-            v += a.band_w[b] * wn::eval3d_exact<PADDED>(a.coef, a.n, a.nmask, 2.0f * p[0] * s, 2.0f * p[1] * s, 2.0f * p[2] * s);
-        }
-        if (a.apply_div) v /= a.out_div;
-        return v;
+        return MULTIBAND ? wn::multiband3d_exact<PADDED>(a, p)
+                         : wn::eval3d_exact<PADDED>(a.coef, a.n, a.nmask, p[0], p[1], p[2]);
     }
     __device__ void store(size_t i, float v) const { a.out[i] = v; }
     __device__ float stored(size_t i) const { return a.out[i]; }
@@ -502,12 +497,7 @@ __global__ __launch_bounds__(kSlabThreads) void row_slab_points_kernel(const Ops
             s_best = 0;
         }
         __syncthreads();
-        if (tid < 256) { // is the stream already coherent?  (as in plane_sorted_points_kernel)
-            const int k = ops.mid_z(begin + min(tid, count - 1));
-            const int prev = __shfl_up(k, 1, 64);
-            const unsigned long long diff = __ballot(lane != 0 && prev != k);
-            if (lane == 0) atomicAdd(&s_changes, (unsigned)__popcll(diff));
-        }
+        if (tid < 256) count_plane_changes(ops, begin, count, tid, &s_changes); // is the stream already coherent?
         // the middle y rows of a sample of the chunk: every fourth point
         int sampled = 0;
         {
@@ -573,7 +563,7 @@ __global__ __launch_bounds__(kSlabThreads) void row_slab_points_kernel(const Ops
             key[k] = 0xffff;
             rank[k] = 0;
             if (i < count && ops.active(begin + i)) {
-                const int bin = ((ops.mid_z(begin + i) & (kSortPlanes - 1)) << kSortXBits) | ((ops.mid_x(begin + i) & 127) >> (7 - kSortXBits));
+                const int bin = sort_bin(ops, begin + i);
                 key[k] = (unsigned short)bin;
                 rank[k] = (unsigned short)atomicAdd(&hist[bin], 1u);
             }
@@ -642,29 +632,17 @@ int launch_sorted(const Ops &ops, hipStream_t stream)
     return WN_OK;
 }
 
-inline int point_blocks(size_t total)
-{
-    size_t b = (total + 255) / 256;
-    const size_t cap = 256u * 8u * 8u;
-    return (int)(b < 1 ? 1 : (b > cap ? cap : b));
-}
+constexpr size_t kBlockCap = 256u * 8u * 8u; // workgroups of a grid-stride launch (wn::stride_blocks)
 
-int fill_common(const wn_tile *tile, int dims, const void *pts, size_t n, const void *out,
-                PointsArgs *a)
+// The tile's fields of PointsArgs (its padded copy for 3-D tiles that have one) and the point count.
+PointsArgs points_args(const wn_tile *tile, int dims, size_t n)
 {
-    if (!tile) return wn::fail(WN_ERR_INVALID, "tile is NULL");
-    if (tile->count) {
-        const int rc = wn::check_handle_device(tile->device, "tile");
-        if (rc) return rc;
-    }
-    if (tile->count && tile->dims != dims)
-        return wn::fail(WN_ERR_INVALID, "tile is %d-D, this entry point needs %d-D", tile->dims, dims);
-    if (n && (!pts || !out)) return wn::fail(WN_ERR_INVALID, "points/out pointer is NULL");
-    a->coef = (dims == 3 && tile->dev_padded) ? tile->dev_padded : tile->dev;
-    a->n = tile->n;
-    a->nmask = wn::pow2_mask(tile->n);
-    a->count = n;
-    return WN_OK;
+    PointsArgs a{};
+    a.coef = (dims == 3 && tile->dev_padded) ? tile->dev_padded : tile->dev;
+    a.n = tile->n;
+    a.nmask = wn::pow2_mask(tile->n);
+    a.count = n;
+    return a;
 }
 
 } // namespace
@@ -677,11 +655,10 @@ int wn_eval3d_points(const wn_tile *tile, const float *xyz_dev, size_t n, float 
                      void *stream)
 {
     WN_ENTRY();
-    int rc = require_device();
-    if (rc) return rc;
-    PointsArgs a{};
-    rc = fill_common(tile, 3, xyz_dev, n, out_dev, &a);
+    const int rc = check_tile(tile, 3, "wn_eval3d_points");
     if (rc || n == 0) return rc;
+    if (!xyz_dev || !out_dev) return fail(WN_ERR_INVALID, "points/out pointer is NULL");
+    PointsArgs a = points_args(tile, 3, n);
     a.pts = xyz_dev;
     a.out = out_dev;
     if (n >= kSortMinPoints && a.n > 0) { // long lists: chunks in z-plane order (plane_sorted_points_kernel)
@@ -696,9 +673,9 @@ int wn_eval3d_points(const wn_tile *tile, const float *xyz_dev, size_t n, float 
         return WN_OK;
     }
     if (tile->dev_padded)
-        hipLaunchKernelGGL(eval3d_points_kernel<true>, dim3(point_blocks(n)), dim3(256), 0, as_stream(stream), a);
+        hipLaunchKernelGGL(eval3d_points_kernel<true>, dim3(wn::stride_blocks(n, kBlockCap)), dim3(256), 0, as_stream(stream), a);
     else
-        hipLaunchKernelGGL(eval3d_points_kernel<false>, dim3(point_blocks(n)), dim3(256), 0, as_stream(stream), a);
+        hipLaunchKernelGGL(eval3d_points_kernel<false>, dim3(wn::stride_blocks(n, kBlockCap)), dim3(256), 0, as_stream(stream), a);
     WN_LAUNCH_CHECK("eval3d_points_kernel");
     return WN_OK;
 }
@@ -707,14 +684,13 @@ int wn_eval2d_points(const wn_tile *tile, const float *xy_dev, size_t n, float *
                      void *stream)
 {
     WN_ENTRY();
-    int rc = require_device();
-    if (rc) return rc;
-    PointsArgs a{};
-    rc = fill_common(tile, 2, xy_dev, n, out_dev, &a);
+    const int rc = check_tile(tile, 2, "wn_eval2d_points");
     if (rc || n == 0) return rc;
+    if (!xy_dev || !out_dev) return fail(WN_ERR_INVALID, "points/out pointer is NULL");
+    PointsArgs a = points_args(tile, 2, n);
     a.pts = xy_dev;
     a.out = out_dev;
-    hipLaunchKernelGGL(eval2d_points_kernel, dim3(point_blocks(n)), dim3(256), 0, as_stream(stream), a);
+    hipLaunchKernelGGL(eval2d_points_kernel, dim3(wn::stride_blocks(n, kBlockCap)), dim3(256), 0, as_stream(stream), a);
     WN_LAUNCH_CHECK("eval2d_points_kernel");
     return WN_OK;
 }
@@ -723,17 +699,16 @@ int wn_eval3d_projected_points(const wn_tile *tile, const float *xyz_dev, const 
                                size_t n, float *out_dev, void *stream)
 {
     WN_ENTRY();
-    int rc = require_device();
-    if (rc) return rc;
-    PointsArgs a{};
-    rc = fill_common(tile, 3, xyz_dev, n, out_dev, &a);
+    const int rc = check_tile(tile, 3, "wn_eval3d_projected_points");
     if (rc || n == 0) return rc;
+    if (!xyz_dev || !out_dev) return fail(WN_ERR_INVALID, "points/out pointer is NULL");
     if (!normals_dev) return fail(WN_ERR_INVALID, "normals_dev is NULL");
+    PointsArgs a = points_args(tile, 3, n);
     a.coef = tile->dev; // the projected evaluator indexes the linear layout
     a.pts = xyz_dev;
     a.normals = normals_dev;
     a.out = out_dev;
-    hipLaunchKernelGGL(eval3d_projected_points_kernel, dim3(point_blocks(n)), dim3(256), 0,
+    hipLaunchKernelGGL(eval3d_projected_points_kernel, dim3(wn::stride_blocks(n, kBlockCap)), dim3(256), 0,
                        as_stream(stream), a);
     WN_LAUNCH_CHECK("eval3d_projected_points_kernel");
     return WN_OK;
@@ -744,27 +719,14 @@ int wn_multiband3d_points(const wn_tile *tile, const float *xyz_dev, size_t n, f
                           float *out_dev, void *stream)
 {
     WN_ENTRY();
-    int rc = require_device();
+    int rc = check_tile(tile, 3, "wn_multiband3d_points");
     if (rc) return rc;
-    if (nbands < 0 || nbands > kMaxBands)
-        return fail(WN_ERR_INVALID, "nbands must be in 0..%d (got %d)", kMaxBands, nbands);
-    if (nbands && !w_host) return fail(WN_ERR_INVALID, "w_host is NULL");
-    PointsArgs a{};
-    rc = fill_common(tile, 3, xyz_dev, n, out_dev, &a);
+    PointsArgs a = points_args(tile, 3, n);
+    rc = multiband_bands(s, first_band, nbands, w_host, var_per_band, &a);
     if (rc || n == 0) return rc;
+    if (!xyz_dev || !out_dev) return fail(WN_ERR_INVALID, "points/out pointer is NULL");
     a.pts = xyz_dev;
     a.out = out_dev;
-    int active = 0;
-    while (active < nbands && s + (float)first_band + (float)active < 0.0f) ++active;
-    float variance = 0.0f;
-    for (int b = 0; b < nbands; ++b) variance += w_host[b] * w_host[b];
-    a.nbands = active;
-    for (int b = 0; b < active; ++b) {
-        a.band_scale[b] = ldexpf(1.0f, first_band + b);
-        a.band_w[b] = w_host[b];
-    }
-    a.apply_div = variance != 0.0f;
-    a.out_div = a.apply_div ? sqrtf(variance * var_per_band) : 1.0f;
     if (n >= kSortMinPoints && a.n > 0 && a.nbands >= 1) { // long lists: chunks in the finest band's z-plane order
         const int lrc = tile->dev_padded ? launch_sorted(Eval3dOps<true, true>{a, n}, as_stream(stream))
                                          : launch_sorted(Eval3dOps<false, true>{a, n}, as_stream(stream));
@@ -773,10 +735,10 @@ int wn_multiband3d_points(const wn_tile *tile, const float *xyz_dev, size_t n, f
         return WN_OK;
     }
     if (tile->dev_padded)
-        hipLaunchKernelGGL(multiband3d_points_kernel<true>, dim3(point_blocks(n)), dim3(256), 0,
+        hipLaunchKernelGGL(multiband3d_points_kernel<true>, dim3(wn::stride_blocks(n, kBlockCap)), dim3(256), 0,
                            as_stream(stream), a);
     else
-        hipLaunchKernelGGL(multiband3d_points_kernel<false>, dim3(point_blocks(n)), dim3(256), 0,
+        hipLaunchKernelGGL(multiband3d_points_kernel<false>, dim3(wn::stride_blocks(n, kBlockCap)), dim3(256), 0,
                            as_stream(stream), a);
     WN_LAUNCH_CHECK("multiband3d_points_kernel");
     return WN_OK;
@@ -787,32 +749,19 @@ int wn_multiband3d_projected_points(const wn_tile *tile, const float *xyz_dev, c
                                     const float *w_host, float var_per_band, float *out_dev, void *stream)
 {
     WN_ENTRY();
-    int rc = require_device();
+    int rc = check_tile(tile, 3, "wn_multiband3d_projected_points");
     if (rc) return rc;
-    if (nbands < 0 || nbands > kMaxBands)
-        return fail(WN_ERR_INVALID, "nbands must be in 0..%d (got %d)", kMaxBands, nbands);
-    if (nbands && !w_host) return fail(WN_ERR_INVALID, "w_host is NULL");
-    PointsArgs a{};
-    rc = fill_common(tile, 3, xyz_dev, n, out_dev, &a);
+    PointsArgs a = points_args(tile, 3, n);
+    rc = multiband_bands(s, first_band, nbands, w_host, var_per_band, &a);
     if (rc || n == 0) return rc;
+    if (!xyz_dev || !out_dev) return fail(WN_ERR_INVALID, "points/out pointer is NULL");
     if (!normals_dev) return fail(WN_ERR_INVALID, "normals_dev is NULL");
     a.coef = tile->dev; // the projected evaluator indexes the linear layout
     a.pts = xyz_dev;
     a.normals = normals_dev;
     a.one_normal = one_normal ? 1 : 0;
     a.out = out_dev;
-    int active = 0;
-    while (active < nbands && s + (float)first_band + (float)active < 0.0f) ++active;
-    float variance = 0.0f;
-    for (int b = 0; b < nbands; ++b) variance += w_host[b] * w_host[b];
-    a.nbands = active;
-    for (int b = 0; b < active; ++b) {
-        a.band_scale[b] = ldexpf(1.0f, first_band + b);
-        a.band_w[b] = w_host[b];
-    }
-    a.apply_div = variance != 0.0f;
-    a.out_div = a.apply_div ? sqrtf(variance * var_per_band) : 1.0f;
-    hipLaunchKernelGGL(multiband3d_projected_points_kernel, dim3(point_blocks(n)), dim3(256), 0, as_stream(stream), a);
+    hipLaunchKernelGGL(multiband3d_projected_points_kernel, dim3(wn::stride_blocks(n, kBlockCap)), dim3(256), 0, as_stream(stream), a);
     WN_LAUNCH_CHECK("multiband3d_projected_points_kernel");
     return WN_OK;
 }
@@ -823,14 +772,12 @@ int wn_wavelet_texture_points(const wn_tile *tile, int use_3d, double scale, int
 {
     WN_ENTRY();
     int rc = require_device();
-    if (rc) return rc;
-    if (n == 0) return WN_OK;
+    if (rc || n == 0) return rc;
     if (!xyz_dev || !grey_dev) return fail(WN_ERR_INVALID, "points/grey pointer is NULL");
-    TexArgs a{};
+    // a NULL or empty tile is allowed: the reference's no-tile grey (texture.h:100-102)
+    if (tile && (rc = check_tile(tile, use_3d ? 3 : 2, "wn_wavelet_texture_points")) != WN_OK) return rc;
     const bool has_tile = tile && tile->count != 0;
-    if (has_tile && (rc = check_handle_device(tile->device, "tile")) != WN_OK) return rc;
-    if (has_tile && tile->dims != (use_3d ? 3 : 2))
-        return fail(WN_ERR_INVALID, "tile is %d-D but use_3d=%d", tile->dims, use_3d);
+    TexArgs a{};
     a.coef = has_tile ? tile->dev : nullptr;
     a.n = has_tile ? tile->n : 0;
     a.nmask = pow2_mask(a.n);

@@ -373,34 +373,30 @@ __global__ __launch_bounds__(64 * (kCW + kSW)) void grid3d_strip_kernel(const St
 
 namespace wn {
 
-// Launches the strip-march kernel when the lattice is in its regime; *launched tells the caller.
-int strip_try(const wn_tile *tile, const GridArgs &g, float *out_dev, hipStream_t stream, bool *launched)
+// Launches the strip-march kernel when the lattice is in its regime.
+int strip_try(const wn_tile *tile, const GridArgs &g, float *out_dev, hipStream_t stream)
 {
-    *launched = false;
-    if (tile->n < 4 || pow2_mask(tile->n) < 0) return WN_OK;
-    if (g.z_const_mode || g.nx <= 0 || g.ny <= 0 || g.nz <= 0) return WN_OK;
-    if (g.z0 < 0) return WN_OK; // negative plane indices: the exact kernel (the bounds below assume indices >= 0)
-    if (g.nx % 256 != 0 || (reinterpret_cast<uintptr_t>(out_dev) & 15) != 0) return WN_OK;
-    const double step = (double)g.base_range * (double)g.octave_scale * (double)g.post_scale / g.den;
-    if (!(step >= 0.0) || !std::isfinite(step)) return WN_OK;
-    const double imax = std::max(std::max((double)g.nx, (double)g.ny), (double)g.z0 + g.nz);
-    const double pmax = step * imax + 1.0;
-    if (pmax > 1.0e6) return WN_OK;
-    const double slack = pmax * 4.8e-7; // fp32 rounding of a coordinate, in planes
+    if (tile->n < 4 || pow2_mask(tile->n) < 0) return kDeclined;
+    if (g.z_const_mode || g.nx <= 0 || g.ny <= 0 || g.nz <= 0) return kDeclined;
+    if (g.z0 < 0) return kDeclined; // negative plane indices: the exact kernel (the bounds below assume indices >= 0)
+    if (g.nx % 256 != 0 || !vec4_ok(out_dev, g.nx)) return kDeclined;
+    LatticeStep ls;
+    if (!lattice_step(g, g.octave_scale, false, false, 0.0, &ls)) return kDeclined;
+    const double step = ls.step, slack = ls.slack;
     // 4 consecutive samples (x quad of a lane, y rows of an item) span <= 2 mids, and a plane change
     // advances the mid by exactly 1
-    if (step < 0.18) return WN_OK; // finer lattices: the brick kernel is faster
-    if (3.0 * step + slack > 1.0) return WN_OK;
-    if (255.0 * step + slack + 7.0 > (double)kCols) return WN_OK; // columns of a block (+3 of alignment)
+    if (step < 0.18) return kDeclined; // finer lattices: the brick kernel is faster
+    if (!ls.two_mids()) return kDeclined;
+    if (255.0 * step + slack + 7.0 > (double)kCols) return kDeclined; // columns of a block (+3 of alignment)
     const long long groups = (long long)(g.nx / 256) * ((g.ny + kCW - 1) / kCW);
-    if (groups > 0x3fffffffLL) return WN_OK;
+    if (groups > 0x3fffffffLL) return kDeclined;
 
     const int dev = current_device();
     const int cus = device_compute_units(dev);
     // items: the planes an item touches must fit its LDS table
     int chunk_max = kMaxChunk;
     if (step > 0.0) chunk_max = (int)std::min<double>(kMaxChunk, std::floor((kPlanes - 5 - slack) / step) + 1.0);
-    if (chunk_max < 8) return WN_OK;
+    if (chunk_max < 8) return kDeclined;
     // owner ranges: every workgroup slot of the chip (two per CU) should get one, as long as a range keeps >= 32 planes
     const long long wgs = 2LL * cus;
     int nranges = 1;
@@ -416,17 +412,16 @@ int strip_try(const wn_tile *tile, const GridArgs &g, float *out_dev, hipStream_
     a.total_groups = (int)groups;
     a.range_len = (g.nz + nranges - 1) / nranges;
     const long long owners = groups * ((g.nz + a.range_len - 1) / a.range_len);
-    if (owners > 0x3fffffffLL) return WN_OK;
+    if (owners > 0x3fffffffLL) return kDeclined;
     a.owners = (int)owners;
     // a range is walked in equal items of at most chunk_max planes
     const int per_range = (a.range_len + chunk_max - 1) / chunk_max;
     a.chunk_len = (a.range_len + per_range - 1) / per_range;
     // dynamic LDS beyond 64 KiB needs a per-(kernel, device) opt-in; refused -> the brick kernel serves the lattice
-    if (!ensure_dynamic_lds(reinterpret_cast<const void *>(&grid3d_strip_kernel), dev, kLdsBytes)) return WN_OK;
+    if (!ensure_dynamic_lds(reinterpret_cast<const void *>(&grid3d_strip_kernel), dev, kLdsBytes)) return kDeclined;
     const int blocks = (int)std::min<long long>(owners, wgs);
     hipLaunchKernelGGL(grid3d_strip_kernel, dim3(blocks), dim3(64 * (kCW + kSW)), kLdsBytes, stream, a);
     WN_LAUNCH_CHECK("grid3d_strip_kernel");
-    *launched = true;
     return WN_OK;
 }
 
