@@ -65,6 +65,9 @@ def lib():
     sig("wno_multiband3d_projected", f, vp, sz, _f32p, _f32p, f, i, i, _f32p, f)
     sig("wno_noise_texture_value", f, _i32p, d, i, _f32p)
     sig("wno_wavelet_texture_value", f, vp, sz, i, d, i, _f32p)
+    sig("wno_evaluate3d_n", None, vp, sz, vp, sz, vp)
+    sig("wno_multiband3d_n", None, vp, sz, vp, sz, f, i, i, _f32p, f, vp)
+    sig("wno_wavelet_texture_value_n", None, vp, sz, i, d, i, vp, sz, vp)
     sig("wno_grid_wavelet2d", None, _f32p, sz, i, i, _f32p)
     sig("wno_grid_wavelet3d_sliced", None, _f32p, sz, i, i, _f32p)
     sig("wno_grid_wavelet3d_projected", None, _f32p, sz, i, i, _f32p)
@@ -163,11 +166,29 @@ def evaluate2d(coef, pts):
     return np.array([L.wno_evaluate2d(_cptr(coef), cnt, p) for p in pts], np.float32)
 
 
-def evaluate3d(coef, pts):
+def _over_list(pts, call):
+    """call(pts_ptr, n, out_ptr) over an (N, 3) list, in slices on a few threads for long lists (ctypes releases the
+    GIL during the call; every point is evaluated on its own, so the slicing changes no value)."""
     pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 3)
-    L = lib()
+    out = np.empty(pts.shape[0], np.float32)
+    step = 1 << 18
+    if pts.shape[0] <= step:
+        if pts.shape[0]:
+            call(pts.ctypes.data_as(C.c_void_p), pts.shape[0], out.ctypes.data_as(C.c_void_p))
+        return out
+    from concurrent.futures import ThreadPoolExecutor
+
+    def piece(b):
+        e = min(b + step, pts.shape[0])
+        call(pts[b:e].ctypes.data_as(C.c_void_p), e - b, out[b:e].ctypes.data_as(C.c_void_p))
+    with ThreadPoolExecutor(min(8, os.cpu_count() or 1)) as ex:
+        list(ex.map(piece, range(0, pts.shape[0], step)))
+    return out
+
+
+def evaluate3d(coef, pts):
     cnt = 0 if coef is None else coef.size
-    return np.array([L.wno_evaluate3d(_cptr(coef), cnt, p) for p in pts], np.float32)
+    return _over_list(pts, lambda p, n, o: lib().wno_evaluate3d_n(_cptr(coef), cnt, p, n, o))
 
 
 def evaluate3d_projected(coef, pts, normals):
@@ -198,11 +219,9 @@ def perlin_turb(perm, pts, depth):
 
 
 def multiband3d(coef, pts, s, first_band, nbands, w, var):
-    pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 3)
     w = np.ascontiguousarray(w, np.float32)
-    L = lib()
-    return np.array([L.wno_multiband3d(_cptr(coef), coef.size, p, s, first_band, nbands, w, var)
-                     for p in pts], np.float32)
+    return _over_list(pts, lambda p, n, o: lib().wno_multiband3d_n(_cptr(coef), coef.size, p, n, s, first_band, nbands,
+                                                                     w, var, o))
 
 
 def multiband3d_projected(coef, pts, normals, s, first_band, nbands, w, var):
@@ -221,11 +240,9 @@ def noise_texture_value(perm, scale, octave, pts):
 
 
 def wavelet_texture_value(coef, use_3d, scale, octave, pts):
-    pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 3)
-    L = lib()
     cnt = 0 if coef is None else coef.size
-    return np.array([L.wno_wavelet_texture_value(_cptr(coef), cnt, int(use_3d), scale, octave, p)
-                     for p in pts], np.float32)
+    return _over_list(pts, lambda p, n, o: lib().wno_wavelet_texture_value_n(_cptr(coef), cnt, int(use_3d), scale,
+                                                                               octave, p, n, o))
 
 
 def grid_wavelet3d_volume(coef, den, nx, ny, z0, z1, octave):

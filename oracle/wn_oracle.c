@@ -489,6 +489,24 @@ float wno_wavelet_texture_value(const float *coef, size_t count, int use_3d, dou
     return (float)v;
 }
 
+void wno_evaluate3d_n(const float *coef, size_t count, const float *pts, size_t n, float *out)
+{
+    for (size_t i = 0; i < n; ++i) out[i] = wno_evaluate3d(coef, count, pts + 3 * i);
+}
+
+void wno_multiband3d_n(const float *coef, size_t count, const float *pts, size_t n, float s, int first_band,
+                       int nbands, const float *w, float var_per_band, float *out)
+{
+    for (size_t i = 0; i < n; ++i)
+        out[i] = wno_multiband3d(coef, count, pts + 3 * i, s, first_band, nbands, w, var_per_band);
+}
+
+void wno_wavelet_texture_value_n(const float *coef, size_t count, int use_3d, double scale, int octave,
+                                 const float *pts, size_t n, float *out)
+{
+    for (size_t i = 0; i < n; ++i) out[i] = wno_wavelet_texture_value(coef, count, use_3d, scale, octave, pts + 3 * i);
+}
+
 /* ============================================================================================
  * Dense grids
  * ========================================================================================== */

@@ -97,6 +97,14 @@ float wno_noise_texture_value(const int perm[512], double scale, int octave, con
 float wno_wavelet_texture_value(const float *coef, size_t count, int use_3d,
                                 double scale, int octave, const float p[3]);
 
+/* ---- the same functions over lists (pts: n points, xyz interleaved; out: n values) ------------ */
+
+void wno_evaluate3d_n(const float *coef, size_t count, const float *pts, size_t n, float *out);
+void wno_multiband3d_n(const float *coef, size_t count, const float *pts, size_t n, float s, int first_band,
+                       int nbands, const float *w, float var_per_band, float *out);
+void wno_wavelet_texture_value_n(const float *coef, size_t count, int use_3d, double scale, int octave,
+                                 const float *pts, size_t n, float *out);
+
 /* ---- dense-grid generators (experient/main.cpp) ---------------------------------------------- */
 
 /* :11-36   */ void wno_grid_wavelet2d(const float *coef2d, size_t count, int image, int octave, float *out);
