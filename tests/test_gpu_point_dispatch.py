@@ -13,8 +13,9 @@ test_point_routes_reach_the_kernels_they_name runs every row once in a child pro
 test_point_route_values compares every row's output with the oracle on every element.  test_row_slab_streams runs
 streams built to reach the row-slab kernel's edges (wrapped rows, a row boundary, the third-row plane limit, reloads
 and wrong guesses inside the trust window, interleaved kept and deferred chunks, partial last chunks, output that
-already holds the defer mark); defer_model, a numpy restatement of the DEFER predicate, proves on the CPU that each
-stream defers the chunks it is meant to.
+already holds the defer mark, kept chunks whose NaN inputs put the mark's bits into some of their 16 mark positions);
+defer_model, a numpy restatement of the DEFER predicate, proves on the CPU that each stream defers the chunks it is meant
+to.
 
 Run as `python tests/test_gpu_point_dispatch.py --child` it is that child: the calls of POINT_ROUTES, one after the other.
 """
@@ -139,15 +140,18 @@ def rows_by_visit(n, period=1, rows=(5.0, 90.0, 127.0), cus=256, salt=5, **_):
     return p
 
 
-def interleaved(n, row=64.0, salt=6, **_):
+def interleaved(n, row=64.0, salt=6, nan_bits=None, **_):
     """Chunks alternate: even ones coherent (a row of x in stream order, one plane per 512 points: kept and evaluated in
-    stream order by the plane-ordered kernel), odd ones scattered on the surface y = row (deferred)."""
+    stream order by the plane-ordered kernel), odd ones scattered on the surface y = row (deferred).  nan_bits: the even
+    chunks' points 64 w for the odd w < 16 (none of them in the DEFER sample) get NaN coordinates with these bits."""
     p = surface(n, row, salt)
     i = np.arange(n)
     even = (i // CHUNK) % 2 == 0
     k = i % CHUNK
     p[even, 0] = (-300.0 + 0.125 * k[even]).astype(np.float32)
     p[even, 2] = (np.float32(3.0) + (i[even] // 512) % 128).astype(np.float32)
+    if nan_bits is not None:
+        p[even & (k % 128 == 64) & (k < 16 * 64)] = np.uint32(nan_bits).view(np.float32)
     return p
 
 
@@ -240,6 +244,7 @@ SLAB_STREAMS = [
     ("interleaved_tail4095", "interleaved", SLAB_MIN + CHUNK - 1, None, "odd"),
     ("prefilled_mark", ("surface", {"row": 64.0}), SLAB_MIN + 2 * CHUNK + 5, DEFER_BITS, 0.9),
     ("prefilled_nan", ("surface", {"row": 64.0}), SLAB_MIN, 0x7fc00000, 0.9),
+    ("interleaved_nan_in", ("interleaved", {"nan_bits": DEFER_BITS}), SLAB_MIN, None, "odd"),  # marks in kept chunks
 ]
 
 
@@ -247,7 +252,8 @@ SLAB_STREAMS = [
 def mid_of(c):
     """The coefficient index of a coordinate's middle tap: (int)ceilf(c - 0.5f)."""
     c = np.asarray(c, np.float32)
-    return np.ceil(c - np.float32(0.5)).astype(np.int64)
+    with np.errstate(invalid="ignore"):  # (NaN coordinates: their middles are never sampled)
+        return np.ceil(c - np.float32(0.5)).astype(np.int64)
 
 
 def texture_mids(p):
@@ -378,10 +384,10 @@ def test_kernel_label_parses_both_name_forms():
     assert kernel_label(tex) == SORTED(TEX_OPS(False, True), True)
     assert kernel_label("void (anonymous namespace)::plane_sorted_points_kernel<(anonymous namespace)::TextureOps<false, "
                         "true>, true>((anonymous namespace)::TextureOps<false, true>)") == SORTED(TEX_OPS(False, True), True)
-    assert kernel_label("_ZN12_GLOBAL__N_122row_slab_points_kernelINS_9Eval3dOpsILb1ELb0EEEEEvT_ii") == \
+    assert kernel_label("_ZN12_GLOBAL__N_122row_slab_points_kernelINS_9Eval3dOpsILb1ELb0EEEEEvT_i") == \
         PAIR(EV_OPS(True, False))[1]
     assert kernel_label("void (anonymous namespace)::row_slab_points_kernel<(anonymous namespace)::Eval3dOps<true, false> >"
-                        "((anonymous namespace)::Eval3dOps<true, false>, int, int)") == PAIR(EV_OPS(True, False))[1]
+                        "((anonymous namespace)::Eval3dOps<true, false>, int)") == PAIR(EV_OPS(True, False))[1]
     assert kernel_label("_ZN12_GLOBAL__N_126plane_sorted_points_kernelINS_9Eval3dOpsILb1ELb1EEELb0EEEvT_") == \
         SORTED(EV_OPS(True, True))
     assert kernel_label("_ZN12_GLOBAL__N_122perlin_grid_run_kernelILi1ELi16EEEvNS_14PerlinGridArgsE") == RUN(1, 16)
@@ -469,6 +475,13 @@ def test_slab_streams_defer_the_chunks_they_are_meant_to(entry, name, spec, n, p
         assert np.unique(mids[:, 2]).tolist() == list(range(128))
     if name in ("row0", "row127"):
         assert (mids[:, 1] == (0 if name == "row0" else 127)).all()
+    if name == "interleaved_nan_in":
+        # NaN inputs with the mark's bits in the kept (even) chunks only, at the marks of the odd waves w < 16
+        pts = to_texture(cells) if entry == "tex" else cells
+        at = np.flatnonzero(np.isnan(pts).any(1))
+        assert at.size == 8 * (n // CHUNK // 2) and (at // CHUNK % 2 == 0).all(), at[:20]
+        assert ((at % CHUNK) // 64).tolist() == list(range(1, 16, 2)) * (n // CHUNK // 2), at[:20]
+        assert (pts[at].view(np.uint32) == DEFER_BITS).all()
 
 
 # ---- running a row ---------------------------------------------------------------------------------------------------
@@ -659,8 +672,13 @@ def _bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
-def _first_differences(got, want, k=5):
-    bad = np.flatnonzero(_bits(got) != _bits(want))
+def _first_differences(got, want, k=5, nan_at=None):
+    """Elements whose bits differ; where `nan_at` is set, elements that are not NaN in both (NaN payloads may differ
+    between the CPU and the GPU)."""
+    differ = _bits(got) != _bits(want)
+    if nan_at is not None:
+        differ[nan_at] = ~(np.isnan(got[nan_at]) & np.isnan(want[nan_at]))
+    bad = np.flatnonzero(differ)
     return bad.size, [(int(i), float(got[i]), float(want[i])) for i in bad[:k]]
 
 
@@ -711,7 +729,8 @@ def test_point_route_values(ctx, row):
 @pytest.mark.parametrize("name,spec,n,prefill,want", SLAB_STREAMS, ids=[s[0] for s in SLAB_STREAMS])
 def test_row_slab_streams(ctx, entry, name, spec, n, prefill, want):
     """Unmasked streams on t128 through the pair plane_sorted_points_kernel<Ops, true> + row_slab_points_kernel<Ops>,
-    every point against the oracle, from an output that holds `prefill` (by default a NaN no kernel writes)."""
+    every point against the oracle, from an output that holds `prefill` (by default a NaN no kernel writes); points with a
+    NaN coordinate must give a NaN, every other point the oracle's bits."""
     import torch
     row = (name, entry, "t128", spec, n, (True, False) if entry == "tex" else None)
     pts, _ = row_inputs(ctx, row)
@@ -719,7 +738,7 @@ def test_row_slab_streams(ctx, entry, name, spec, n, prefill, want):
     torch.cuda.synchronize()
     got = got.cpu().numpy()
     want = row_reference(ctx, row, pts, None)
-    count, first = _first_differences(got, want)
+    count, first = _first_differences(got, want, nan_at=np.isnan(pts).any(1))
     assert count == 0, f"{entry} {name}: {count} of {n} points differ from the oracle, first (index, got, want): {first}"
 
 

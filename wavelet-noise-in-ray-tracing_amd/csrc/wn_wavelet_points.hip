@@ -217,8 +217,9 @@ __device__ __forceinline__ void count_plane_changes(const Ops &ops, size_t begin
 
 // The kernel is generic over what a point is (`Ops`): count; active(i); mid_z(i) / mid_x(i) = the coefficient index of the
 // z / x tap's middle (of the finest band, where there are several); eval(i); store(i, v).
-// A chunk left to row_slab_points_kernel is marked in the output itself: this value (a NaN no evaluation produces; if one
-// ever did, the chunk would be evaluated twice to the same floats) in the chunk's first element.
+// A chunk left to row_slab_points_kernel is marked in the output itself: this value (a NaN no evaluation produces) in 16 of
+// its elements.  The slab kernel takes a chunk only when all 16 hold it; if evaluations ever produced them all, the chunk
+// would be evaluated twice to the same floats.
 constexpr unsigned kDeferredBits = 0xffc0de42u;
 constexpr int kDeferMarks = 16, kDeferMarkStride = 64; // row_slab_points_kernel: 16 waves, wave w stores element 64 w first
 
@@ -261,8 +262,7 @@ __global__ __launch_bounds__(256) void plane_sorted_points_kernel(const Ops ops)
             }
             __syncthreads();
             if (s_defer) {
-                // (one mark per wave of that kernel, where the wave's own first store goes: its waves run through such chunks
-                // without a barrier, and a mark one wave has overwritten must not tell another that the chunk is done)
+                // (one mark per wave of that kernel, the element that wave reads: it takes the chunk only when all 16 are there)
                 if (tid < kDeferMarks) ops.store(begin + kDeferMarkStride * tid, __uint_as_float(kDeferredBits));
                 return;
             }
@@ -421,7 +421,7 @@ constexpr size_t kSlabLdsBytes = kSlabFloats * sizeof(float) + kSlabScratchBytes
 constexpr size_t kSlabMinPoints = 16 * 256 * (size_t)kSortChunk;
 
 template <typename Ops>
-__global__ __launch_bounds__(kSlabThreads) void row_slab_points_kernel(const Ops ops, const int nchunks, const int deferred_only)
+__global__ __launch_bounds__(kSlabThreads) void row_slab_points_kernel(const Ops ops, const int nchunks)
 {
     static_assert(kSortBins == kSlabThreads, "one bin per thread in the prefix sum");
     static_assert(kDeferMarks * 64 == kSlabThreads && kDeferMarkStride == 64, "one mark per wave, at the wave's first element");
@@ -434,6 +434,7 @@ __global__ __launch_bounds__(kSlabThreads) void row_slab_points_kernel(const Ops
     float *const third = slab + kSlabFloats;
     __shared__ unsigned rowhist[kSlabTile];
     __shared__ unsigned s_changes, s_best, wave_total[kSlabThreads / 64];
+    __shared__ unsigned long long s_marked[2][kSlabThreads / 64]; // a group's marks as each wave found them, by group parity
     bool third_ok = false; // the scratch holds the third row of the resident pair
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = ops.tile_n(), stride = n + 2; // n == kSlabTile (host)
@@ -458,18 +459,26 @@ __global__ __launch_bounds__(kSlabThreads) void row_slab_points_kernel(const Ops
                 ops.store(begin + tid + kSlabThreads * k,
                           ops.eval_rowslab_at(xyz[k][0], xyz[k][1], xyz[k][2], slab, slab_row, third, third_ok ? kSlabThirdPlanes : 0));
     };
-    // The workgroup's chunks (blockIdx.x, + gridDim.x, ...) in groups of 64.  After plane_sorted_points_kernel<Ops, true> on
-    // the same stream only the chunks it left: a wave reads the marks of a group's chunks at once -- one load per lane, each
-    // wave the marks only it overwrites, all the same -- instead of paying a memory round trip per chunk to learn it is done.
-    for (int g0 = blockIdx.x; g0 < nchunks; g0 += 64 * (int)gridDim.x) {
-    unsigned long long todo = ~0ull;
-    if (deferred_only) {
+    // The workgroup's chunks (blockIdx.x, + gridDim.x, ...) in groups of 64, of which it evaluates those that
+    // plane_sorted_points_kernel<Ops, true> left.  Wave w reads its mark (element 64 w) of each of the group's chunks -- one
+    // load per lane instead of a memory round trip per chunk -- and stores the ballot in its own word; after one barrier every
+    // wave takes the chunks whose 16 marks are all there.  So `todo`, and every barrier below that depends on it, is the same
+    // for the whole workgroup whatever the output holds (a kept chunk's result may have a mark's bits: a NaN input carrying
+    // that payload), and no wave overwrites a mark before the others have read it.  Consecutive groups use alternate words: a
+    // wave writes group g's after passing group g - 1's barrier, which no wave reaches before it has read group g - 2's.
+    for (int g0 = blockIdx.x, parity = 0; g0 < nchunks; g0 += 64 * (int)gridDim.x, parity ^= 1) {
+    {
         const long long c = (long long)g0 + (long long)lane * gridDim.x;
-        bool left = false;
+        bool marked = false;
         if (c < nchunks && ((size_t)c + 1) * kSortChunk <= ops.count) // (only whole chunks are ever left)
-            left = __float_as_uint(ops.stored((size_t)c * kSortChunk + kDeferMarkStride * wave)) == kDeferredBits;
-        todo = __ballot(left);
+            marked = __float_as_uint(ops.stored((size_t)c * kSortChunk + kDeferMarkStride * wave)) == kDeferredBits;
+        const unsigned long long found = __ballot(marked);
+        if (lane == 0) s_marked[parity][wave] = found;
     }
+    __syncthreads();
+    unsigned long long todo = ~0ull;
+#pragma unroll
+    for (int w = 0; w < kSlabThreads / 64; ++w) todo &= s_marked[parity][w];
     for (int j = 0; j < 64; ++j) {
         const long long chunk = (long long)g0 + (long long)j * gridDim.x;
         if (chunk >= nchunks) break;
@@ -619,7 +628,7 @@ bool launch_row_slab(const Ops &ops, int n, bool masked, hipStream_t stream)
     if (!wn::ensure_dynamic_lds(fn, dev, kSlabLdsBytes)) return false; // the runtime refused the LDS opt-in
     const int grid = (int)std::min<size_t>(chunks, (size_t)wn::device_compute_units(dev));
     hipLaunchKernelGGL((plane_sorted_points_kernel<Ops, true>), dim3((unsigned)chunks), dim3(256), 0, stream, ops);
-    hipLaunchKernelGGL((row_slab_points_kernel<Ops>), dim3((unsigned)grid), dim3(kSlabThreads), kSlabLdsBytes, stream, ops, (int)chunks, 1);
+    hipLaunchKernelGGL((row_slab_points_kernel<Ops>), dim3((unsigned)grid), dim3(kSlabThreads), kSlabLdsBytes, stream, ops, (int)chunks);
     return true;
 }
 
