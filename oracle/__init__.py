@@ -66,6 +66,8 @@ def lib():
     sig("wno_noise_texture_value", f, _i32p, d, i, _f32p)
     sig("wno_wavelet_texture_value", f, vp, sz, i, d, i, _f32p)
     sig("wno_evaluate3d_n", None, vp, sz, vp, sz, vp)
+    sig("wno_evaluate2d_n", None, vp, sz, vp, sz, vp)
+    sig("wno_evaluate3d_projected_n", None, vp, sz, vp, vp, sz, sz, vp)
     sig("wno_multiband3d_n", None, vp, sz, vp, sz, f, i, i, _f32p, f, vp)
     sig("wno_wavelet_texture_value_n", None, vp, sz, i, d, i, vp, sz, vp)
     sig("wno_grid_wavelet2d", None, _f32p, sz, i, i, _f32p)
@@ -159,31 +161,33 @@ def _cptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
 
 
-def evaluate2d(coef, pts):
-    pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 2)
-    L = lib()
-    cnt = 0 if coef is None else coef.size
-    return np.array([L.wno_evaluate2d(_cptr(coef), cnt, p) for p in pts], np.float32)
-
-
-def _over_list(pts, call):
-    """call(pts_ptr, n, out_ptr) over an (N, 3) list, in slices on a few threads for long lists (ctypes releases the
-    GIL during the call; every point is evaluated on its own, so the slicing changes no value)."""
-    pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 3)
+def _over_list(pts, call, width=3, per_point=None):
+    """call(pts_ptr, n, out_ptr) over an (N, width) list, in slices on a few threads for long lists (ctypes releases
+    the GIL during the call; every point is evaluated on its own, so the slicing changes no value).  With `per_point`
+    (an (N, k) float32 array sliced along with the points) the call is call(pts_ptr, extra_ptr, n, out_ptr)."""
+    pts = np.ascontiguousarray(pts, np.float32).reshape(-1, width)
     out = np.empty(pts.shape[0], np.float32)
     step = 1 << 18
-    if pts.shape[0] <= step:
-        if pts.shape[0]:
-            call(pts.ctypes.data_as(C.c_void_p), pts.shape[0], out.ctypes.data_as(C.c_void_p))
-        return out
-    from concurrent.futures import ThreadPoolExecutor
 
     def piece(b):
         e = min(b + step, pts.shape[0])
-        call(pts[b:e].ctypes.data_as(C.c_void_p), e - b, out[b:e].ctypes.data_as(C.c_void_p))
+        args = [pts[b:e].ctypes.data_as(C.c_void_p)]
+        if per_point is not None:
+            args.append(per_point[b:e].ctypes.data_as(C.c_void_p))
+        call(*args, e - b, out[b:e].ctypes.data_as(C.c_void_p))
+    if pts.shape[0] <= step:
+        if pts.shape[0]:
+            piece(0)
+        return out
+    from concurrent.futures import ThreadPoolExecutor
     with ThreadPoolExecutor(min(8, os.cpu_count() or 1)) as ex:
         list(ex.map(piece, range(0, pts.shape[0], step)))
     return out
+
+
+def evaluate2d(coef, pts):
+    cnt = 0 if coef is None else coef.size
+    return _over_list(pts, lambda p, n, o: lib().wno_evaluate2d_n(_cptr(coef), cnt, p, n, o), width=2)
 
 
 def evaluate3d(coef, pts):
@@ -192,12 +196,26 @@ def evaluate3d(coef, pts):
 
 
 def evaluate3d_projected(coef, pts, normals):
+    """evaluate3DProjected at every point: `normals` holds one normal per point, or one normal for the whole list."""
     pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 3)
     normals = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
-    L = lib()
     cnt = 0 if coef is None else coef.size
-    return np.array([L.wno_evaluate3d_projected(_cptr(coef), cnt, p, n)
-                     for p, n in zip(pts, normals)], np.float32)
+    L = lib()
+    if normals.shape[0] == 1 and pts.shape[0] != 1:
+        nr = normals.ctypes.data_as(C.c_void_p)
+        return _over_list(pts, lambda p, n, o: L.wno_evaluate3d_projected_n(_cptr(coef), cnt, p, nr, 0, n, o))
+    assert normals.shape == pts.shape, (normals.shape, pts.shape)
+    return _over_list(pts, lambda p, nr, n, o: L.wno_evaluate3d_projected_n(_cptr(coef), cnt, p, nr, 3, n, o),
+                      per_point=normals)
+
+
+def filter_tile(field, n, dims):
+    """The filter half of generateNoiseTile2D/3D alone (wno_filter_tile2d/3d): field - lowpass(field), n^dims floats."""
+    field = np.ascontiguousarray(field, np.float32).ravel()
+    assert dims in (2, 3) and field.size == n ** dims, (field.size, n, dims)
+    out = np.empty_like(field)
+    (lib().wno_filter_tile2d if dims == 2 else lib().wno_filter_tile3d)(n, field, out)
+    return out
 
 
 def perlin_noise(perm, pts):

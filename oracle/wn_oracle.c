@@ -494,6 +494,18 @@ void wno_evaluate3d_n(const float *coef, size_t count, const float *pts, size_t 
     for (size_t i = 0; i < n; ++i) out[i] = wno_evaluate3d(coef, count, pts + 3 * i);
 }
 
+void wno_evaluate2d_n(const float *coef, size_t count, const float *pts, size_t n, float *out)
+{
+    for (size_t i = 0; i < n; ++i) out[i] = wno_evaluate2d(coef, count, pts + 2 * i);
+}
+
+void wno_evaluate3d_projected_n(const float *coef, size_t count, const float *pts, const float *normals,
+                                size_t normal_stride, size_t n, float *out)
+{
+    for (size_t i = 0; i < n; ++i)
+        out[i] = wno_evaluate3d_projected(coef, count, pts + 3 * i, normals + normal_stride * i);
+}
+
 void wno_multiband3d_n(const float *coef, size_t count, const float *pts, size_t n, float s, int first_band,
                        int nbands, const float *w, float var_per_band, float *out)
 {

@@ -100,6 +100,11 @@ float wno_wavelet_texture_value(const float *coef, size_t count, int use_3d,
 /* ---- the same functions over lists (pts: n points, xyz interleaved; out: n values) ------------ */
 
 void wno_evaluate3d_n(const float *coef, size_t count, const float *pts, size_t n, float *out);
+/* pts: n points, xy interleaved */
+void wno_evaluate2d_n(const float *coef, size_t count, const float *pts, size_t n, float *out);
+/* normals: one normal per point (normal_stride 3) or one normal for the whole list (normal_stride 0) */
+void wno_evaluate3d_projected_n(const float *coef, size_t count, const float *pts, const float *normals,
+                                size_t normal_stride, size_t n, float *out);
 void wno_multiband3d_n(const float *coef, size_t count, const float *pts, size_t n, float s, int first_band,
                        int nbands, const float *w, float var_per_band, float *out);
 void wno_wavelet_texture_value_n(const float *coef, size_t count, int use_3d, double scale, int octave,
