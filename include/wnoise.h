@@ -197,6 +197,33 @@ WN_API int wn_perlin_turb_points(const wn_perm *perm, const float *xyz_dev, size
 WN_API int wn_perlin_fractal_points(const wn_perm *perm, const float *xyz_dev, size_t n,
                                     double *out_dev, void *stream);
 
+/* ---- analytic gradients of evaluate3D and WMultibandNoise (absent from the reference) --------------
+ * evaluate3D is a tensor-product quadratic B-spline sum (WaveletNoise.cpp:185-215): per axis t = mid - (p - 0.5f) and
+ * the weights w0 = t^2/2, w2 = (1-t)^2/2, w1 = 1 - w0 - w2; their derivatives are d0 = -t, d1 = 2t - 1, d2 = 1 - t on
+ * the same three taps.  d/dx sums the 27 coefficients with tap weights (d_x*w_y)*w_z, d/dy with (w_x*d_y)*w_z and d/dz
+ * with (w_x*w_y)*d_z, each in evaluate3D's order (z outer, x inner), unfused, beside the value's own sum.  The spline
+ * is C1: the gradient is continuous, also at the half-integers where mid flips.  An empty tile gives 0 in all four
+ * channels.  Multiband (normal == NULL branch, as wn_multiband3d_*): grad = sum_b w[b] * (2 * 2^(first_band+b)) *
+ * grad evaluate3D(q_b), q_b = 2 * p * 2^(first_band+b), with the value's bands, out_div and division.
+ *
+ * Points: `n` float4 records {value, d/dx, d/dy, d/dz}, one 16-byte store per point; out4_dev must be 16-byte aligned
+ * (else WN_ERR_INVALID).  The value channel has the bits of wn_eval3d_points / wn_multiband3d_points, and all four
+ * channels those of the host's scalar evaluator (evaluate3DGradient).
+ * Grids: four consecutive volumes -- value, d/dx, d/dy, d/dz -- each holding the samples the matching wn_eval3d_grid /
+ * wn_multiband3d_grid call writes, in its layout (a z-sharded caller gathers each channel with wn_gather_volume).  The
+ * gradient is taken with respect to the sample's noise-space coordinate (the value passed to evaluate3D; multiband:
+ * the lattice coordinate p), not per lattice index; out_scale multiplies all four channels last; under WN_Z_CONST d/dz
+ * is taken at z_const.  WN_GRID_EXACT: bit-identical to the point entry points at the lattice's float coordinates
+ * (channel 0: to the WN_GRID_EXACT value grid).  Default: a separable brick kernel, every channel within
+ * 1e-5 * |out_scale| (multiband: * sum_b |w_b| 2^(first_band+b+1) / out_div) of the exact tier; a sample's bits do
+ * not depend on how the volume is cut into z-slabs. */
+WN_API int wn_eval3d_grad_points(const wn_tile *tile3d, const float *xyz_dev, size_t n, float *out4_dev, void *stream);
+WN_API int wn_multiband3d_grad_points(const wn_tile *tile3d, const float *xyz_dev, size_t n, float s, int first_band,
+                                      int nbands, const float *w_host, float var_per_band, float *out4_dev, void *stream);
+WN_API int wn_eval3d_grad_grid(const wn_tile *tile3d, const wn_grid *g, float *out_dev, void *stream);
+WN_API int wn_multiband3d_grad_grid(const wn_tile *tile3d, const wn_grid *g, float s, int first_band, int nbands,
+                                    const float *w_host, float var_per_band, float *out_dev, void *stream);
+
 /* ---- texture adaptor (texture.h), batched over ray hit points -------------------------------- */
 /* `active_dev` (may be NULL = all active): one byte per point, 0 = this hit is not on a
  * noise-textured surface.  Inactive points are skipped (their output is left untouched); the

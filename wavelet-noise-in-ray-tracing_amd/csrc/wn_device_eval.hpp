@@ -86,6 +86,65 @@ __device__ __forceinline__ float eval3d_exact(const float *coef, int n, int nmas
                       : eval3d_exact_impl<PADDED, false>(coef, n, nmask, px, py, pz);
 }
 
+// evaluate3D and its gradient at p: the value is eval3d_exact_impl's sum, product for product and in its order (the same
+// bits); beside it the three derivative sums over the same 27 coefficients, tap weights (d_x*w_y)*w_z, (w_x*d_y)*w_z and
+// (w_x*w_y)*d_z, each accumulated f2 -> f1 -> f0, unfused.  Returns the value, writes the gradient to g.
+template <bool PADDED, bool POW2>
+__device__ __forceinline__ float eval3d_grad_exact_impl(const float *coef, int n, int nmask, float px, float py, float pz,
+                                                        float g[3])
+{
+    int mx, my, mz;
+    float wx[3], wy[3], wz[3], dx[3], dy[3], dz[3];
+    bspline_grad(px, mx, wx, dx);
+    bspline_grad(py, my, wy, dy);
+    bspline_grad(pz, mz, wz, dz);
+    const int stride = PADDED ? n + 2 : n;
+    int cx[3], cy[3], cz[3];
+#pragma unroll
+    for (int f = 0; f < 3; ++f) {
+        cx[f] = POW2 ? ((mx + f - 1) & nmask) : dmod(mx + f - 1, n, -1);
+        cy[f] = (POW2 ? ((my + f - 1) & nmask) : dmod(my + f - 1, n, -1)) * stride;
+        cz[f] = (POW2 ? ((mz + f - 1) & nmask) : dmod(mz + f - 1, n, -1)) * stride * n;
+    }
+    float result = 0.0f, gx = 0.0f, gy = 0.0f, gz = 0.0f;
+#pragma unroll
+    for (int fz = 0; fz < 3; ++fz)
+#pragma unroll
+        for (int fy = 0; fy < 3; ++fy) {
+            float c[3];
+            if (PADDED) {
+                __builtin_memcpy(c, coef + cx[0] + cy[fy] + cz[fz], sizeof(c)); // global_load_dwordx3
+            } else {
+#pragma unroll
+                for (int fx = 0; fx < 3; ++fx) c[fx] = coef[cx[fx] + cy[fy] + cz[fz]];
+            }
+#pragma unroll
+            for (int fx = 0; fx < 3; ++fx) {
+                const float weight = wx[fx] * wy[fy] * wz[fz];
+                result += weight * c[fx];
+                gx += dx[fx] * wy[fy] * wz[fz] * c[fx];
+                gy += wx[fx] * dy[fy] * wz[fz] * c[fx];
+                gz += wx[fx] * wy[fy] * dz[fz] * c[fx];
+            }
+        }
+    g[0] = gx;
+    g[1] = gy;
+    g[2] = gz;
+    return result;
+}
+
+template <bool PADDED = false>
+__device__ __forceinline__ float eval3d_grad_exact(const float *coef, int n, int nmask, float px, float py, float pz,
+                                                   float g[3])
+{
+    if (n == 0) { // the empty tile: 0 in all four channels
+        g[0] = g[1] = g[2] = 0.0f;
+        return 0.0f;
+    }
+    return nmask >= 0 ? eval3d_grad_exact_impl<PADDED, true>(coef, n, nmask, px, py, pz, g)
+                      : eval3d_grad_exact_impl<PADDED, false>(coef, n, nmask, px, py, pz, g);
+}
+
 // WMultibandNoise (paper Appendix 2, normal == NULL): sum_b w[b] * evaluate3D(2 * p * 2^(first_band+b)), divided by
 // out_div when apply_div.  `a` carries coef, n, nmask and the bands of wn::multiband_bands.
 template <bool PADDED, typename A>
@@ -97,6 +156,34 @@ __device__ __forceinline__ float multiband3d_exact(const A &a, const float p[3])
         v += a.band_w[b] * eval3d_exact<PADDED>(a.coef, a.n, a.nmask, 2.0f * p[0] * s, 2.0f * p[1] * s, 2.0f * p[2] * s);
     }
     if (a.apply_div) v /= a.out_div;
+    return v;
+}
+
+// multiband3d_exact and its gradient with respect to p: band b adds (w[b] * (2 * 2^(first_band+b))) * grad evaluate3D(q_b)
+// (the chain rule of q_b = 2 * p * 2^(first_band+b)); the value has multiband3d_exact's bits.
+template <bool PADDED, typename A>
+__device__ __forceinline__ float multiband3d_grad_exact(const A &a, const float p[3], float g[3])
+{
+    float v = 0.0f, gx = 0.0f, gy = 0.0f, gz = 0.0f;
+    for (int b = 0; b < a.nbands; ++b) {
+        const float s = a.band_scale[b];
+        float gb[3];
+        const float e = eval3d_grad_exact<PADDED>(a.coef, a.n, a.nmask, 2.0f * p[0] * s, 2.0f * p[1] * s, 2.0f * p[2] * s, gb);
+        v += a.band_w[b] * e;
+        const float f = a.band_w[b] * (2.0f * s);
+        gx += f * gb[0];
+        gy += f * gb[1];
+        gz += f * gb[2];
+    }
+    if (a.apply_div) {
+        v /= a.out_div;
+        gx /= a.out_div;
+        gy /= a.out_div;
+        gz /= a.out_div;
+    }
+    g[0] = gx;
+    g[1] = gy;
+    g[2] = gz;
     return v;
 }
 

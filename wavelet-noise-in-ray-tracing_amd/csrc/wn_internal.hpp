@@ -240,5 +240,15 @@ __device__ __forceinline__ void bspline(float p, int &mid, float &w0, float &w1,
     w1 = 1.0f - w0 - w2;
 }
 
+// bspline, and the derivatives of the three weights with respect to p (dt/dp = -1): d0 = -t, d1 = 2t - 1, d2 = 1 - t.
+__device__ __forceinline__ void bspline_grad(float p, int &mid, float w[3], float d[3])
+{
+    bspline(p, mid, w[0], w[1], w[2]);
+    const float t = (float)mid - (p - 0.5f);
+    d[0] = -t;
+    d[1] = 2.0f * t - 1.0f;
+    d[2] = 1.0f - t;
+}
+
 } // namespace wn
 #endif

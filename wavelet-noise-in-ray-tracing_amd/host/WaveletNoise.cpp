@@ -102,6 +102,51 @@ float WaveletNoise::WMultibandNoise(const float p[3], float sarg, const float *n
     return s.out_host()[0];
 }
 
+// ---- gradients: the scalar member on the host (bit-identical to the point kernel; WN_SCALAR_ON_DEVICE does not apply), the
+// multiband one a batch of one on the device; a 2-D tile goes to the C ABI, which reports it
+float WaveletNoise::evaluate3DGradient(const float p[3], float grad[3]) const
+{
+    if (tileDims != 2)
+        return wnhost_eval3d_grad(noiseCoefficients.empty() ? nullptr : noiseCoefficients.data(), tileSizeN, p, grad);
+    float out4[4];
+    evaluate3DGradient(p, 1, out4);
+    std::copy(out4 + 1, out4 + 4, grad);
+    return out4[0];
+}
+
+float WaveletNoise::WMultibandNoiseGradient(const float p[3], float sarg, int firstBand, int nbands, const float *w,
+                                            float grad[3], float variance) const
+{
+    auto &s = wnhost::Scratch::get();
+    std::copy(p, p + 3, s.in_host());
+    check(wn_multiband3d_grad_points(tile(3), static_cast<const float *>(s.in_dev()), 1, sarg, firstBand, nbands, w,
+                                     variance, static_cast<float *>(s.out_dev()), nullptr),
+          "wn_multiband3d_grad_points");
+    check(wn_stream_sync(nullptr), "wn_stream_sync");
+    std::copy(s.out_host() + 1, s.out_host() + 4, grad);
+    return s.out_host()[0];
+}
+
+void WaveletNoise::evaluate3DGradient(const float *xyz, size_t n, float *out4) const
+{
+    if (!n) return;
+    wnhost::DeviceBuffer in(3 * n * sizeof(float)), res(4 * n * sizeof(float));
+    in.upload(xyz);
+    check(wn_eval3d_grad_points(tile(3), in.as<float>(), n, res.as<float>(), nullptr), "wn_eval3d_grad_points");
+    res.download(out4);
+}
+
+void WaveletNoise::WMultibandNoiseGradient(const float *xyz, size_t n, float sarg, int firstBand, int nbands,
+                                           const float *w, float variance, float *out4) const
+{
+    if (!n) return;
+    wnhost::DeviceBuffer in(3 * n * sizeof(float)), res(4 * n * sizeof(float));
+    in.upload(xyz);
+    check(wn_multiband3d_grad_points(tile(3), in.as<float>(), n, sarg, firstBand, nbands, w, variance, res.as<float>(),
+                                     nullptr), "wn_multiband3d_grad_points");
+    res.download(out4);
+}
+
 // ---- batched members ----------------------------------------------------------------------------------
 void WaveletNoise::evaluate2D(const float *xy, size_t n, float *out) const
 {

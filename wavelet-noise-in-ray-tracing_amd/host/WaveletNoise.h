@@ -63,6 +63,16 @@ class WaveletNoise {
     // normalises with 0.296; normal == nullptr is the overload above with the paper's 0.210 replaced by `variance`.
     float WMultibandNoise(const float p[3], float s, const float *normal, int firstBand, int nbands,
                           const float *w, float variance = 0.296f) const;
+    // Analytic gradients (absent from the reference).  evaluate3DGradient returns evaluate3D(p) (the same bits) and writes
+    // its gradient to grad: on the host (scalar_eval.h), bit-identical to wn_eval3d_grad_points.  The batched forms write n
+    // records {value, d/dx, d/dy, d/dz} to out4.  WMultibandNoiseGradient: WMultibandNoise (normal == NULL) and its gradient
+    // with respect to p, one point as a batch of one on the device.
+    float evaluate3DGradient(const float p[3], float grad[3]) const;
+    void evaluate3DGradient(const float *xyz, size_t n, float *out4) const;
+    float WMultibandNoiseGradient(const float p[3], float s, int firstBand, int nbands, const float *w, float grad[3],
+                                  float variance = 0.18402f) const;
+    void WMultibandNoiseGradient(const float *xyz, size_t n, float s, int firstBand, int nbands, const float *w,
+                                 float variance, float *out4) const;
     // The device-resident tile (an empty tile before generate*); for the C-ABI grid entry points.
     const wn_tile *tile(int dims) const;
 

@@ -72,6 +72,36 @@ float wnhost_eval3d(const float *coef, int n, const float p[3])
     return result;
 }
 
+float wnhost_eval3d_grad(const float *coef, int n, const float p[3], float grad[3])
+{
+    grad[0] = grad[1] = grad[2] = 0.0f;
+    if (!coef || n <= 0) return 0.0f;
+    int mid[3];
+    float w[3][3], d[3][3];
+    for (int i = 0; i < 3; ++i) {
+        bspline(p[i], mid[i], w[i]);
+        const float t = (float)mid[i] - (p[i] - 0.5f); // bspline's t; dt/dp = -1
+        d[i][0] = -t;
+        d[i][1] = 2.0f * t - 1.0f;
+        d[i][2] = 1.0f - t;
+    }
+    float result = 0.0f, gx = 0.0f, gy = 0.0f, gz = 0.0f;
+    for (int f2 = -1; f2 <= 1; ++f2) // evaluate3D's order: z outermost, x innermost
+        for (int f1 = -1; f1 <= 1; ++f1)
+            for (int f0 = -1; f0 <= 1; ++f0) {
+                const float c = coef[wrap(mid[0] + f0, n) + wrap(mid[1] + f1, n) * n + wrap(mid[2] + f2, n) * n * n];
+                const float weight = w[0][f0 + 1] * w[1][f1 + 1] * w[2][f2 + 1];
+                result += weight * c;
+                gx += d[0][f0 + 1] * w[1][f1 + 1] * w[2][f2 + 1] * c;
+                gy += w[0][f0 + 1] * d[1][f1 + 1] * w[2][f2 + 1] * c;
+                gz += w[0][f0 + 1] * w[1][f1 + 1] * d[2][f2 + 1] * c;
+            }
+    grad[0] = gx;
+    grad[1] = gy;
+    grad[2] = gz;
+    return result;
+}
+
 float wnhost_eval3d_projected(const float *coef, int n, const float p[3], const float nrm[3])
 {
     if (!coef || n <= 0) return 0.0f; // :219-221

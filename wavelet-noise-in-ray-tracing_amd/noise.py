@@ -216,6 +216,24 @@ class WaveletNoise:
                                          _ptr(out), _stream()))
         return float(out.item()) if single else out
 
+    # -- analytic gradients (absent from the reference): (N, 4) CUDA tensors of {value, d/dx, d/dy, d/dz}
+    def evaluate3DGradient(self, p):
+        """evaluate3D and its gradient at one point or an (N, 3) batch (wn_eval3d_grad_points): the value column has the
+        bits of evaluate3D."""
+        pts = _dev(p, torch.float32).reshape(-1, 3)
+        out = torch.empty((pts.shape[0], 4), dtype=torch.float32, device="cuda")
+        check(_lib.wn_eval3d_grad_points(self._handle(3), _ptr(pts), pts.shape[0], _ptr(out), _stream()))
+        return out
+
+    def WMultibandNoiseGradient(self, p, s, firstBand, nbands, w, variance=0.18402):
+        """WMultibandNoise (normal == NULL) and its gradient with respect to p (wn_multiband3d_grad_points)."""
+        pts = _dev(p, torch.float32).reshape(-1, 3)
+        out = torch.empty((pts.shape[0], 4), dtype=torch.float32, device="cuda")
+        wa = (C.c_float * max(1, nbands))(*[float(x) for x in list(w)[:nbands]])
+        check(_lib.wn_multiband3d_grad_points(self._handle(3), _ptr(pts), pts.shape[0], float(s), int(firstBand),
+                                              int(nbands), wa, float(variance), _ptr(out), _stream()))
+        return out
+
 
 # ---- perlin / PerlinNoise (perlin.h:14-91, experient/PerlinNoise.hpp:9-61) -------------------
 class perlin:
@@ -501,6 +519,39 @@ def multiband_volume(noise, den, nx, ny, z0, z1, s=-16.0, firstBand=0, nbands=5,
     check(_lib.wn_multiband3d_grid(noise._handle(3), C.byref(gc), float(s), int(firstBand),
                                    int(nbands), wa, float(variance), _ptr(out), _stream()))
     return out[: g.nz * ny * nx].view(g.nz, ny, nx)
+
+
+def _grad_out(g, out):
+    n = 4 * g.nz * g.ny * g.nx
+    if out is None:
+        return torch.empty(n, dtype=torch.float32, device="cuda")
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= n
+    return out
+
+
+def wavelet_gradient_volume(noise, den, nx, ny, z0, z1, octave, exact=False, out=None):
+    """wavelet_volume's lattice with the gradient (wn_eval3d_grad_grid): [4, nz, ny, nx] -- value, d/dx, d/dy, d/dz
+    with respect to the coordinate passed to evaluate3D, all four times 1/sqrt(0.18402)."""
+    g = GridSpec(den, nx, ny, z0, z1, octave_scale=_octave_scale(octave), post_scale=2.0,
+                 out_scale=_inv_stddev(0.18402), flags=WN_GRID_EXACT if exact else WN_GRID_DEFAULT)
+    out = _grad_out(g, out)
+    gc = g.c()
+    check(_lib.wn_eval3d_grad_grid(noise._handle(3), C.byref(gc), _ptr(out), _stream()))
+    return out[: 4 * g.nz * ny * nx].view(4, g.nz, ny, nx)
+
+
+def multiband_gradient_volume(noise, den, nx, ny, z0, z1, s=-16.0, firstBand=0, nbands=5, w=None,
+                              variance=0.18402, exact=False, out=None):
+    """multiband_volume's lattice with the gradient with respect to p = (i/den)*4 (wn_multiband3d_grad_grid):
+    [4, nz, ny, nx]."""
+    w = [1.0] * nbands if w is None else list(w)
+    g = GridSpec(den, nx, ny, z0, z1, flags=WN_GRID_EXACT if exact else WN_GRID_DEFAULT)
+    out = _grad_out(g, out)
+    gc = g.c()
+    wa = (C.c_float * max(1, nbands))(*[float(x) for x in w[:nbands]])
+    check(_lib.wn_multiband3d_grad_grid(noise._handle(3), C.byref(gc), float(s), int(firstBand),
+                                        int(nbands), wa, float(variance), _ptr(out), _stream()))
+    return out[: 4 * g.nz * ny * nx].view(4, g.nz, ny, nx)
 
 
 def perlin_volume(perlin_obj, den, nx, ny, z0, z1, octave, out=None):
