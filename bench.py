@@ -1,16 +1,20 @@
 #!/usr/bin/env python3
 """bench.py -- Mnoise-samples/s of the hot path on N MI355X, with the roofline of the dominant
-kernel and the reference's CPU path timed beside it.
+kernel; with --full also the reference's CPU path and the other BASELINE workloads timed beside it.
 
-  python bench.py                       N=1: BASELINE configs[1], 512^3 dense 3-D wavelet grid.  The line also carries
-                                        `roofline.sustained` (>= 1 s of back-to-back headline launches) and `per_config`
-                                        (short legs of every other BASELINE workload: multiband5, turb7, perlin, both
-                                        texture stand-ins, the bit-exact grid), each with its kernel's roofline fraction
-                                        and the reference's CPU path on a bounded sample of the same workload
-  python bench.py --gpus 8              BASELINE configs[4]: ONE 2048^3 lattice in z-slabs of 2048/N planes.  Rank 0 also
-                                        times the SAME lattice alone in the same run (`strong_scaling`), the 512^3 lattice
-                                        of the north star sharded the same way (`strong_scaling_512`), and the one gather
-                                        of the slabs on rank 0 (`gather`)
+  python bench.py                       N=1: BASELINE configs[1], 512^3 dense 3-D wavelet grid: set-up, the in-run fill /
+                                        copy ceiling (the launches the warm-up has always followed), W warm-up and K timed
+                                        steps, and the line with the headline figure and the roofline of its launches
+  python bench.py --full                the same timed steps and headline, and every leg beside them: `roofline.sustained`
+                                        (>= 1 s of back-to-back headline launches), the reference's CPU path on a bounded
+                                        sample of the same workload (`cpu_baseline`) and `per_config` (short legs of every
+                                        other BASELINE workload: multiband5, turb7, perlin, both texture stand-ins, the
+                                        bit-exact grid), each with its kernel's roofline fraction and its CPU baseline.
+                                        --no-cpu-baseline, --no-per-config, --no-sustained leave legs out of it
+  python bench.py --gpus 8              BASELINE configs[4]: ONE 2048^3 lattice in z-slabs of 2048/N planes.  With --full
+                                        rank 0 also times the SAME lattice alone in the same run (`strong_scaling`), the
+                                        512^3 lattice of the north star sharded the same way (`strong_scaling_512`), and
+                                        the one gather of the slabs on rank 0 (`gather`)
   python bench.py --workload turb7      one of the other workloads as the timed workload, same evidence
   python bench.py --dump-outputs DIR    also write what the last timed step computed to DIR (inputs are seeded: two builds
                                         run with the same arguments can be compared output for output)
@@ -63,17 +67,22 @@ def parse(argv=None):
     ap.add_argument("--planes", type=int, default=0,
                     help="z-planes per GPU (default: the whole lattice on one GPU, lattice/N on N)")
     ap.add_argument("--workload", default="wavelet3d", choices=WORKLOADS)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every leg beside the headline: `roofline.sustained`, the CPU "
+                         "baseline, `per_config` (N = 1); the gather and `strong_scaling` (N > 1).  Off: the run does only "
+                         "what the headline figure needs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline time budget (1 thread)")
-    ap.add_argument("--no-gather", action="store_true", help="N > 1: skip the gather of the slabs on rank 0")
+    ap.add_argument("--no-gather", action="store_true", help="--full, N > 1: skip the gather of the slabs on rank 0")
     ap.add_argument("--no-measured-peak", action="store_true", help="skip the in-run fill / copy ceiling")
     ap.add_argument("--no-per-config", action="store_true",
-                    help="N = 1 default workload: skip the short legs of the other BASELINE workloads (`per_config`)")
+                    help="--full, N = 1 default workload: skip the short legs of the other BASELINE workloads (`per_config`)")
     ap.add_argument("--per-config-cpu-seconds", type=float, default=2.5)
-    ap.add_argument("--no-sustained", action="store_true", help="skip `roofline.sustained` (>= 1 s of back-to-back launches)")
+    ap.add_argument("--no-sustained", action="store_true",
+                    help="--full: skip `roofline.sustained` (>= 1 s of back-to-back launches)")
     ap.add_argument("--sustained-seconds", type=float, default=1.1)
     ap.add_argument("--no-strong-scaling", action="store_true",
-                    help="N > 1: skip rank 0's single-GPU run of the same lattice and the 512^3 variant")
+                    help="--full, N > 1: skip rank 0's single-GPU run of the same lattice and the 512^3 variant")
     ap.add_argument("--two-stream-probe", action="store_true",
                     help="also time the same launches alternating between two streams / two buffers (informational; off by "
                          "default so that a rocprofv3 trace of this command holds only the contract's launches)")
@@ -480,7 +489,8 @@ def main():
     # The store / copy ceiling of THIS box, same buffer, same run (torch's fill and copy kernels), measured BEFORE the warm-up:
     # ~8 ms of memory-bound launches after the idle gap of the set-up, so that the W warm-up and K timed steps that follow
     # are not the chip's first work after idling (the first ~20 launches after an idle gap run at a lower clock: 110 us per
-    # launch against 101.8 us from the 100th on, `roofline.sustained`).
+    # launch against 101.8 us from the 100th on, `roofline.sustained`).  So it runs without --full as well: the headline's
+    # warm-up and timed steps have always followed it.
     measured_peak = None
     if rank == 0 and not args.no_measured_peak:
         nbytes = out.numel() * 4
@@ -518,7 +528,7 @@ def main():
 
     # ---- the one exchange of the sharded path: collect the slabs on rank 0 (outside the timed steps) ----
     gather = None
-    if dist is not None and not args.no_gather and W.tex_pts is None:
+    if args.full and dist is not None and not args.no_gather and W.tex_pts is None:
         slab = out[: n * n * my_planes].view(my_planes, n, n)
         full = None
         if backend != "nccl":
@@ -547,7 +557,7 @@ def main():
     # (configs[1], strip kernel) -- two workloads.  So every N > 1 line carries its own single-GPU baseline: rank 0 computes
     # the whole lattice alone while the others wait, and both lattices are reported as {n1_ms, nN_ms, efficiency}.
     scaling = {}
-    if dist is not None and sharded_volume and wl == "wavelet3d" and not args.no_strong_scaling:
+    if args.full and dist is not None and sharded_volume and wl == "wavelet3d" and not args.no_strong_scaling:
         def scaling_leg(m, reps):
             zs = [min(r * -(-m // world), m) for r in range(world + 1)]
             a, b = zs[rank], zs[rank + 1]
@@ -603,7 +613,7 @@ def main():
                 roofline["two_stream_pipeline"] = {"ms_per_step": pdt * 1e3 / args.steps, "Msamples_per_s": samples_per_rank * args.steps / pdt / 1e6,
                                                    "how": "same launches alternating between 2 HIP streams / 2 output buffers; wall clock"}
                 del second, lanes
-        if world == 1 and not args.no_sustained and wl in ("wavelet3d", "multiband5", "wavelet3d_exact", "perlin", "turb7"):
+        if args.full and world == 1 and not args.no_sustained and wl in ("wavelet3d", "multiband5", "wavelet3d_exact", "perlin", "turb7"):
             # >= 1 s of back-to-back launches of the same step on the same stream, one HIP-event pair per segment of 100
             # launches: the mean, and the min / max of the per-segment means (does the figure hold beyond a 5 ms burst?)
             seg = 100 if launch_s < 5e-4 else 10
@@ -627,7 +637,7 @@ def main():
                                              (W.alg_flops / (mean_us * 1e-6) / 1e12 / FP64_VALU_PEAK_TF),
                                      "how": f"{nseg} segments of {seg} back-to-back launches, one HIP-event pair per segment, same stream / buffer"}
             del timers
-        if not args.no_measured_peak:
+        if args.full and not args.no_measured_peak:
             for _ in range(2):
                 step()  # the buffer holds the workload's output again for the CPU comparison below
             torch.cuda.synchronize()
@@ -647,9 +657,9 @@ def main():
             line["gather"] = gather
             line["step_plus_gather_ms"] = dt * 1e3 / args.steps + gather["ms"]
         line.update(scaling)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = W.cpu_baseline(args.cpu_seconds)
-        if world == 1 and wl == "wavelet3d" and not args.no_per_config:
+        if args.full and world == 1 and wl == "wavelet3d" and not args.no_per_config:
             # the other BASELINE workloads, each as a short leg of the same evidence (5 warm-up + 20 launches, HIP events)
             del W, out, step
             torch.cuda.empty_cache()

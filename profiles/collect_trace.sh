@@ -5,5 +5,5 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python3 $ROOT/bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-per-config > "$OUT/trace.json" 2> "$OUT/trace.err"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python3 $ROOT/bench.py --full --steps 50 --warmup 5 --no-cpu-baseline --no-per-config > "$OUT/trace.json" 2> "$OUT/trace.err"
 tail -c 600 "$OUT/trace.json"

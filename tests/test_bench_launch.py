@@ -88,6 +88,18 @@ def _bench_module():
     return bench
 
 
+def test_full_is_off_by_default_and_reaches_every_rank():
+    """A plain run does only what its headline needs; --full (the CPU baseline, per_config, sustained, gather and
+    strong-scaling legs) is asked for, and the self-launch passes it on to the ranks it starts."""
+    bench = _bench_module()
+    assert bench.parse(["--gpus", "1", "--steps", "3", "--warmup", "1"]).full is False
+    argv = ["--gpus", "2", "--full", "--steps", "3"]
+    args = bench.parse(argv)
+    assert args.full is True
+    cmd = bench.launch_command(args, argv, 29500)
+    assert cmd[cmd.index(os.path.join(ROOT, "bench.py")) + 1:] == argv
+
+
 def test_steps_below_one_are_refused_before_any_gpu_work():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True,

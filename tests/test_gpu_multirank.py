@@ -66,7 +66,7 @@ def _run_bench(args, env_extra):
 def test_bench_launches_its_own_ranks_two_gloo_ranks_on_one_gpu():
     """`python bench.py --gpus 2` started plainly: it starts two ranks itself; on a one-GPU box they share the GPU
     and exchange through gloo (WN_BENCH_BACKEND), exercising slabs + gather end to end."""
-    line = _run_bench(["--gpus", "2", "--lattice", "512", "--steps", "2", "--warmup", "1", "--no-measured-peak"],
+    line = _run_bench(["--full", "--gpus", "2", "--lattice", "512", "--steps", "2", "--warmup", "1", "--no-measured-peak"],
                       {"WN_BENCH_BACKEND": "gloo"})
     assert line["n_gpus"] == 2 and line["scaling"] == "strong"
     assert line["config"]["lattice_total"] == [512, 512, 512] and line["config"]["lattice_per_gpu"] == [512, 512, 256]
@@ -124,7 +124,7 @@ def test_gridgen_shards_a_lattice_over_one_rank_with_the_native_gather(tmp_path)
 def test_gather_volume_on_rccl_two_gpus():
     """Two ranks, one per GPU, nccl (= RCCL) backend: bench.py's sharded run gathers the slabs on rank 0 and checks
     a peer's plane against a local recompute."""
-    line = _run_bench(["--gpus", "2", "--lattice", "1024", "--steps", "2", "--warmup", "1"], {})
+    line = _run_bench(["--full", "--gpus", "2", "--lattice", "1024", "--steps", "2", "--warmup", "1"], {})
     assert line["n_gpus"] == 2
     assert line["gather"]["backend"] == "RCCL"
     assert line["gather"]["peer_plane_matches_local_recompute"] is True
