@@ -224,6 +224,45 @@ WN_API int wn_eval3d_grad_grid(const wn_tile *tile3d, const wn_grid *g, float *o
 WN_API int wn_multiband3d_grad_grid(const wn_tile *tile3d, const wn_grid *g, float s, int first_band, int nbands,
                                     const float *w_host, float var_per_band, float *out_dev, void *stream);
 
+/* ---- analytic gradients of evaluate2D, evaluate3DProjected and projected WMultibandNoise (absent from the reference) --
+ * evaluate2D (WaveletNoise.cpp:111-140) is a 3 x 3 quadratic B-spline sum: per axis t = mid - (p - 0.5f), weights
+ * (t^2/2, 1 - w0 - w2, (1-t)^2/2) and derivatives (-t, 2t - 1, 1 - t).  d/dx sums the 9 coefficients with tap weights
+ * d_x*w_y, d/dy with w_x*d_y, each in evaluate2D's order (y outer, x inner), unfused, beside the value's own sum.
+ *
+ * evaluate3DProjected (WaveletNoise.cpp:218-265), gradient with respect to p, the normal n held fixed.  A cell c of the
+ * support box has t_i = (c_i + n_i*dot/2) - (p_i - 1.5), dot = sum_k n_k (p_k - c_k), so dt_i/dp_j = n_i n_j / 2 - delta_ij,
+ * and weight prod_i B(t_i), B the quadratic B-spline on (0, 3) with B'(t) = t (t < 1), t2 - t1 (1 <= t < 2), -t3 (t >= 2).
+ * With G_i = B'(t_i) prod_{k!=i} B(t_k) and S = sum_i n_i G_i: d weight / dp_j = (n_j/2) S - G_j.  The value channel is
+ * evaluate3DProjected itself: the support box, the early exit per axis and the weight > 1e-6 cut.  The gradient channels
+ * do NOT apply the cut: every cell of the box with 0 < t < 3 on all three axes contributes, so the gradient is that of
+ * the uncut C1 sum and has no seams (a cut cell still has a derivative weight up to ~9e-4; a cut gradient would jump by
+ * ~1e-3 |c| wherever a cell crosses the threshold).  The value channel therefore differs from the function whose
+ * gradient is returned by at most 1e-6 * sum |c| over the cut cells.
+ * Multiband (normal != NULL branch, as wn_multiband3d_projected_points): band b adds
+ * w_b * (2 * 2^(first_band+b)) * grad evaluate3DProjected(q_b), q_b = 2 * p * 2^(first_band+b), with the value's bands,
+ * out_div and division; `normals_dev` holds one normal per point, or ONE for all points when one_normal != 0.
+ * An empty tile gives 0 in every channel.
+ *
+ * Points: 2-D: `n` records {value, d/dx, d/dy} of 3 floats.  Projected: `n` float4 records {value, d/dx, d/dy, d/dz},
+ * one 16-byte store per point; out4_dev must be 16-byte aligned (else WN_ERR_INVALID).  The value channel has the bits
+ * of wn_eval2d_points / wn_eval3d_projected_points / wn_multiband3d_projected_points, and every channel those of the
+ * host's scalar evaluator (evaluate2DGradient, evaluate3DProjectedGradient).
+ * Grids: three consecutive planes (2-D: value, d/dx, d/dy) in wn_eval2d_grid's layout, or four consecutive volumes
+ * (projected: value, d/dx, d/dy, d/dz) in wn_eval3d_projected_grid's layout.  The gradient is taken with respect to the
+ * sample's noise-space coordinate (the value passed to the evaluator), out_scale multiplies every channel last, and
+ * under WN_Z_CONST d/dz is taken at z_const.  One tier: `flags` is accepted and ignored, and every channel has the bits
+ * of the point entry point at the lattice's float coordinates (channel 0: of wn_eval2d_grid / wn_eval3d_projected_grid),
+ * so a sample's bits do not depend on how the volume is cut into z-slabs. */
+WN_API int wn_eval2d_grad_points(const wn_tile *tile2d, const float *xy_dev, size_t n, float *out3_dev, void *stream);
+WN_API int wn_eval2d_grad_grid(const wn_tile *tile2d, const wn_grid *g, float *out_dev, void *stream);
+WN_API int wn_eval3d_projected_grad_points(const wn_tile *tile3d, const float *xyz_dev, const float *normals_dev,
+                                           size_t n, float *out4_dev, void *stream);
+WN_API int wn_eval3d_projected_grad_grid(const wn_tile *tile3d, const wn_grid *g, const float normal[3],
+                                         float *out_dev, void *stream);
+WN_API int wn_multiband3d_projected_grad_points(const wn_tile *tile3d, const float *xyz_dev, const float *normals_dev,
+                                                int one_normal, size_t n, float s, int first_band, int nbands,
+                                                const float *w_host, float var_per_band, float *out4_dev, void *stream);
+
 /* ---- texture adaptor (texture.h), batched over ray hit points -------------------------------- */
 /* `active_dev` (may be NULL = all active): one byte per point, 0 = this hit is not on a
  * noise-textured surface.  Inactive points are skipped (their output is left untouched); the

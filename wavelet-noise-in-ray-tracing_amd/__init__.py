@@ -22,7 +22,7 @@ from .noise import (  # noqa: E402
     generate2DOctaveBandNoise, generate3DSlicedOctaveBandNoise,
     generate3DProjectedOctaveBandNoise, generatePerlinNoise2D, generatePerlinNoise3DSliced,
     wavelet_volume, wavelet_volume_launcher, multiband_volume, perlin_volume, turb_volume, device_info, HipTimer,
-    wavelet_gradient_volume, multiband_gradient_volume,
+    wavelet_gradient_volume, multiband_gradient_volume, wavelet2d_gradient_image, projected_gradient_volume,
 )
 from .shard import slab_bounds, gather_volume, NativeComm  # noqa: E402
 from . import formats  # noqa: E402
@@ -33,5 +33,6 @@ __all__ = [
     "generate2DOctaveBandNoise", "generate3DSlicedOctaveBandNoise",
     "generate3DProjectedOctaveBandNoise", "generatePerlinNoise2D", "generatePerlinNoise3DSliced",
     "wavelet_volume", "wavelet_volume_launcher", "multiband_volume", "perlin_volume", "turb_volume", "device_info",
-    "HipTimer", "wavelet_gradient_volume", "multiband_gradient_volume", "slab_bounds", "gather_volume", "NativeComm", "formats",
+    "HipTimer", "wavelet_gradient_volume", "multiband_gradient_volume", "wavelet2d_gradient_image",
+    "projected_gradient_volume", "slab_bounds", "gather_volume", "NativeComm", "formats",
 ]

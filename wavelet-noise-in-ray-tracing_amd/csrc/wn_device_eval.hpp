@@ -291,6 +291,136 @@ __device__ __forceinline__ float projected_exact(const float *coef, int n, int n
     return result;
 }
 
+// evaluate2D and its gradient at p: the value is eval2d_exact's sum, product for product and in its order (the same bits);
+// beside it the two derivative sums over the same 9 coefficients, tap weights d_x*w_y and w_x*d_y, each accumulated
+// f1 -> f0, unfused.  Returns the value, writes d/dx, d/dy to g.
+__device__ __forceinline__ float eval2d_grad_exact(const float *coef, int n, int nmask, float px, float py, float g[2])
+{
+    if (n == 0) { // the empty tile: 0 in all three channels
+        g[0] = g[1] = 0.0f;
+        return 0.0f;
+    }
+    int mx, my;
+    float wx[3], wy[3], dx[3], dy[3];
+    bspline_grad(px, mx, wx, dx);
+    bspline_grad(py, my, wy, dy);
+    int cx[3], cy[3];
+#pragma unroll
+    for (int f = 0; f < 3; ++f) {
+        cx[f] = dmod(mx + f - 1, n, nmask);
+        cy[f] = dmod(my + f - 1, n, nmask) * n;
+    }
+    float result = 0.0f, gx = 0.0f, gy = 0.0f;
+#pragma unroll
+    for (int fy = 0; fy < 3; ++fy)
+#pragma unroll
+        for (int fx = 0; fx < 3; ++fx) {
+            const float c = coef[cx[fx] + cy[fy]];
+            const float weight = wx[fx] * wy[fy];
+            result += weight * c;
+            gx += dx[fx] * wy[fy] * c;
+            gy += wx[fx] * dy[fy] * c;
+        }
+    g[0] = gx;
+    g[1] = gy;
+    return result;
+}
+
+// evaluate3DProjected and its gradient with respect to p, the normal held fixed.  One pass over projected_exact's support
+// box.  A cell with t_i = (c_i + n_i*dot/2) - (p_i - 1.5), dot = sum_k n_k (p_k - c_k), has weight prod_i B(t_i); with
+// B' = t, t2 - t1, -t3 on the three pieces, G_i = B'(t_i) prod_{k!=i} B(t_k) and S = sum_i n_i G_i, dt_i/dp_j =
+// n_i n_j / 2 - delta_ij gives d weight / dp_j = (n_j/2) S - G_j.
+//  - value: projected_exact's arithmetic, cell for cell (the same t, the same (B0*B1)*B2, the same weight > 1e-6 cut): its
+//    bits.  Its per-axis `break` only ends a product that is then 0 and cut, so every axis's t is formed here up front.
+//  - gradient: EVERY cell with 0 < t_i < 3 on all three axes, no 1e-6 cut (a cut sum would jump by up to ~1e-3 |c| when a
+//    cell crosses the threshold; the uncut sum is C1).  G_i = (B'0*B1)*B2, (B0*B'1)*B2, (B0*B1)*B'2; S = (n0 G0 + n1 G1) +
+//    n2 G2; each dweight_j * c accumulated in the box's order (c2 -> c1 -> c0), unfused.
+// The box is the value's: no cell outside it has 0 < t < 3 on all three axes (its half-width 3|n_i| + 3 sqrt((1-n_i^2)/2)
+// bounds |p_i - c_i| of every such cell).  Returns the value, writes the gradient to g.
+__device__ __forceinline__ float projected_grad_exact(const float *coef, int n, int nmask, const float p[3],
+                                                      const float nrm[3], float g[3])
+{
+    if (n == 0) { // the empty tile: 0 in all four channels
+        g[0] = g[1] = g[2] = 0.0f;
+        return 0.0f;
+    }
+    // per point, once: the box, p_i - 1.5f and n_j / 2
+    int lo[3], hi[3];
+    float pm[3], hn[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const float support = 3.0f * fabsf(nrm[i]) + 3.0f * sqrtf((1.0f - nrm[i] * nrm[i]) / 2.0f);
+        lo[i] = (int)ceilf(p[i] - support);
+        hi[i] = (int)floorf(p[i] + support);
+        pm[i] = p[i] - 1.5f;
+        hn[i] = nrm[i] / 2.0f;
+    }
+    float result = 0.0f, gx = 0.0f, gy = 0.0f, gz = 0.0f;
+    for (int c2 = lo[2]; c2 <= hi[2]; ++c2)
+        for (int c1 = lo[1]; c1 <= hi[1]; ++c1)
+            for (int c0 = lo[0]; c0 <= hi[0]; ++c0) {
+                const float cf[3] = {(float)c0, (float)c1, (float)c2};
+                float dot = 0.0f;
+#pragma unroll
+                for (int i = 0; i < 3; ++i) dot += nrm[i] * (p[i] - cf[i]);
+                float b[3], d[3];
+                bool inside = true;
+#pragma unroll
+                for (int i = 0; i < 3; ++i) {
+                    const float t = (cf[i] + nrm[i] * dot / 2.0f) - pm[i];
+                    inside = inside && t > 0.0f && t < 3.0f;
+                    const float t1 = t - 1.0f, t2 = 2.0f - t, t3 = 3.0f - t;
+                    b[i] = t < 1.0f ? (t * t / 2.0f) : (t < 2.0f ? (1.0f - (t1 * t1 + t2 * t2) / 2.0f) : (t3 * t3 / 2.0f));
+                    d[i] = t < 1.0f ? t : (t < 2.0f ? t2 - t1 : -t3);
+                }
+                if (inside) {
+                    const float c = coef[dmod(c0, n, nmask) + dmod(c1, n, nmask) * n + dmod(c2, n, nmask) * n * n];
+                    const float weight = b[0] * b[1] * b[2];
+                    if ((double)weight > 1e-6) result += weight * c;
+                    const float g0 = d[0] * b[1] * b[2], g1 = b[0] * d[1] * b[2], g2 = b[0] * b[1] * d[2];
+                    const float s = nrm[0] * g0 + nrm[1] * g1 + nrm[2] * g2;
+                    gx += (hn[0] * s - g0) * c;
+                    gy += (hn[1] * s - g1) * c;
+                    gz += (hn[2] * s - g2) * c;
+                }
+            }
+    g[0] = gx;
+    g[1] = gy;
+    g[2] = gz;
+    return result;
+}
+
+// WMultibandNoise, normal != NULL branch, and its gradient with respect to p: band b adds w[b] * evaluate3DProjected(q_b, n)
+// to the value and (w[b] * (2 * 2^(first_band+b))) * grad evaluate3DProjected(q_b, n) to the gradient, q_b = 2 * p *
+// 2^(first_band+b); all four divided by out_div when apply_div.  `a` carries coef, n, nmask and the bands of
+// wn::multiband_bands; the value has the bits of wn_multiband3d_projected_points.
+template <typename A>
+__device__ __forceinline__ float multiband3d_projected_grad_exact(const A &a, const float p[3], const float nrm[3], float g[3])
+{
+    float v = 0.0f, gx = 0.0f, gy = 0.0f, gz = 0.0f;
+    for (int b = 0; b < a.nbands; ++b) {
+        const float s = a.band_scale[b];
+        const float q[3] = {2.0f * p[0] * s, 2.0f * p[1] * s, 2.0f * p[2] * s};
+        float gb[3];
+        const float e = projected_grad_exact(a.coef, a.n, a.nmask, q, nrm, gb);
+        v += a.band_w[b] * e;
+        const float f = a.band_w[b] * (2.0f * s);
+        gx += f * gb[0];
+        gy += f * gb[1];
+        gz += f * gb[2];
+    }
+    if (a.apply_div) {
+        v /= a.out_div;
+        gx /= a.out_div;
+        gy /= a.out_div;
+        gz /= a.out_div;
+    }
+    g[0] = gx;
+    g[1] = gy;
+    g[2] = gz;
+    return v;
+}
+
 // ---- Perlin improved noise, fp64 (perlin.h:18-31, 42-62) ------------------------------------------
 __device__ __forceinline__ double pfade(double t) { return t * t * t * (t * (t * 6 - 15) + 10); }
 __device__ __forceinline__ double plerp(double t, double a, double b) { return a + t * (b - a); }

@@ -147,6 +147,78 @@ void WaveletNoise::WMultibandNoiseGradient(const float *xyz, size_t n, float sar
     res.download(out4);
 }
 
+float WaveletNoise::evaluate2DGradient(const float p[2], float grad[2]) const
+{
+    if (tileDims != 3)
+        return wnhost_eval2d_grad(noiseCoefficients.empty() ? nullptr : noiseCoefficients.data(), tileSizeN, p, grad);
+    float out3[3];
+    evaluate2DGradient(p, 1, out3);
+    std::copy(out3 + 1, out3 + 3, grad);
+    return out3[0];
+}
+
+float WaveletNoise::evaluate3DProjectedGradient(const float p[3], const float normal[3], float grad[3]) const
+{
+    if (tileDims != 2)
+        return wnhost_eval3d_projected_grad(noiseCoefficients.empty() ? nullptr : noiseCoefficients.data(), tileSizeN, p,
+                                            normal, grad);
+    float out4[4];
+    evaluate3DProjectedGradient(p, normal, 1, out4);
+    std::copy(out4 + 1, out4 + 4, grad);
+    return out4[0];
+}
+
+float WaveletNoise::WMultibandNoiseGradient(const float p[3], float sarg, const float *normal, int firstBand, int nbands,
+                                            const float *w, float grad[3], float variance) const
+{
+    if (!normal) return WMultibandNoiseGradient(p, sarg, firstBand, nbands, w, grad, variance);
+    auto &s = wnhost::Scratch::get();
+    std::copy(p, p + 3, s.in_host());
+    std::copy(normal, normal + 3, s.in_host() + 4);
+    const float *in = static_cast<const float *>(s.in_dev());
+    check(wn_multiband3d_projected_grad_points(tile(3), in, in + 4, 1, 1, sarg, firstBand, nbands, w, variance,
+                                               static_cast<float *>(s.out_dev()), nullptr),
+          "wn_multiband3d_projected_grad_points");
+    check(wn_stream_sync(nullptr), "wn_stream_sync");
+    std::copy(s.out_host() + 1, s.out_host() + 4, grad);
+    return s.out_host()[0];
+}
+
+void WaveletNoise::evaluate2DGradient(const float *xy, size_t n, float *out3) const
+{
+    if (!n) return;
+    wnhost::DeviceBuffer in(2 * n * sizeof(float)), res(3 * n * sizeof(float));
+    in.upload(xy);
+    check(wn_eval2d_grad_points(tile(2), in.as<float>(), n, res.as<float>(), nullptr), "wn_eval2d_grad_points");
+    res.download(out3);
+}
+
+void WaveletNoise::evaluate3DProjectedGradient(const float *xyz, const float *normals, size_t n, float *out4) const
+{
+    if (!n) return;
+    wnhost::DeviceBuffer in(3 * n * sizeof(float)), nr(3 * n * sizeof(float)), res(4 * n * sizeof(float));
+    in.upload(xyz);
+    nr.upload(normals);
+    check(wn_eval3d_projected_grad_points(tile(3), in.as<float>(), nr.as<float>(), n, res.as<float>(), nullptr),
+          "wn_eval3d_projected_grad_points");
+    res.download(out4);
+}
+
+void WaveletNoise::WMultibandNoiseGradient(const float *xyz, const float *normals, bool oneNormal, size_t n, float sarg,
+                                           int firstBand, int nbands, const float *w, float variance, float *out4) const
+{
+    if (!normals) return WMultibandNoiseGradient(xyz, n, sarg, firstBand, nbands, w, variance, out4);
+    if (!n) return;
+    const size_t nn = oneNormal ? 1 : n;
+    wnhost::DeviceBuffer in(3 * n * sizeof(float)), nr(3 * nn * sizeof(float)), res(4 * n * sizeof(float));
+    in.upload(xyz);
+    nr.upload(normals);
+    check(wn_multiband3d_projected_grad_points(tile(3), in.as<float>(), nr.as<float>(), oneNormal ? 1 : 0, n, sarg,
+                                               firstBand, nbands, w, variance, res.as<float>(), nullptr),
+          "wn_multiband3d_projected_grad_points");
+    res.download(out4);
+}
+
 // ---- batched members ----------------------------------------------------------------------------------
 void WaveletNoise::evaluate2D(const float *xy, size_t n, float *out) const
 {

@@ -73,6 +73,23 @@ class WaveletNoise {
                                   float variance = 0.18402f) const;
     void WMultibandNoiseGradient(const float *xyz, size_t n, float s, int firstBand, int nbands, const float *w,
                                  float variance, float *out4) const;
+    // evaluate2DGradient returns evaluate2D(p) and writes d/dx, d/dy to grad, on the host (bit-identical to
+    // wn_eval2d_grad_points); the batched form writes n records {value, d/dx, d/dy} to out3.  evaluate3DProjectedGradient:
+    // evaluate3DProjected(p, normal) and its gradient with respect to p, the normal held fixed (the gradient of the sum
+    // without the value's 1e-6 cut, include/wnoise.h), on the host (bit-identical to wn_eval3d_projected_grad_points); the
+    // batched form takes one normal per point and writes n records {value, d/dx, d/dy, d/dz} to out4.
+    float evaluate2DGradient(const float p[2], float grad[2]) const;
+    void evaluate2DGradient(const float *xy, size_t n, float *out3) const;
+    float evaluate3DProjectedGradient(const float p[3], const float normal[3], float grad[3]) const;
+    void evaluate3DProjectedGradient(const float *xyz, const float *normals, size_t n, float *out4) const;
+    // WMultibandNoise(p, s, normal, ...) and its gradient with respect to p: normal != nullptr makes every band
+    // evaluate3DProjected (wn_multiband3d_projected_grad_points, a batch of one on the device); normal == nullptr is the
+    // overload above with `variance` passed on.  The batched form takes one normal per point, or one for all points when
+    // oneNormal; normals == nullptr is the batched overload above.
+    float WMultibandNoiseGradient(const float p[3], float s, const float *normal, int firstBand, int nbands, const float *w,
+                                  float grad[3], float variance = 0.296f) const;
+    void WMultibandNoiseGradient(const float *xyz, const float *normals, bool oneNormal, size_t n, float s, int firstBand,
+                                 int nbands, const float *w, float variance, float *out4) const;
     // The device-resident tile (an empty tile before generate*); for the C-ABI grid entry points.
     const wn_tile *tile(int dims) const;
 

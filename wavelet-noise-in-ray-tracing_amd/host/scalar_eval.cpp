@@ -72,6 +72,33 @@ float wnhost_eval3d(const float *coef, int n, const float p[3])
     return result;
 }
 
+float wnhost_eval2d_grad(const float *coef, int n, const float p[2], float grad[2])
+{
+    grad[0] = grad[1] = 0.0f;
+    if (!coef || n <= 0) return 0.0f;
+    int mid[2];
+    float w[2][3], d[2][3];
+    for (int i = 0; i < 2; ++i) {
+        bspline(p[i], mid[i], w[i]);
+        const float t = (float)mid[i] - (p[i] - 0.5f); // bspline's t; dt/dp = -1
+        d[i][0] = -t;
+        d[i][1] = 2.0f * t - 1.0f;
+        d[i][2] = 1.0f - t;
+    }
+    float result = 0.0f, gx = 0.0f, gy = 0.0f;
+    for (int fy = -1; fy <= 1; ++fy) // evaluate2D's order: y outer, x inner
+        for (int fx = -1; fx <= 1; ++fx) {
+            const float c = coef[wrap(mid[0] + fx, n) + wrap(mid[1] + fy, n) * n];
+            const float weight = w[0][fx + 1] * w[1][fy + 1];
+            result += weight * c;
+            gx += d[0][fx + 1] * w[1][fy + 1] * c;
+            gy += w[0][fx + 1] * d[1][fy + 1] * c;
+        }
+    grad[0] = gx;
+    grad[1] = gy;
+    return result;
+}
+
 float wnhost_eval3d_grad(const float *coef, int n, const float p[3], float grad[3])
 {
     grad[0] = grad[1] = grad[2] = 0.0f;
@@ -133,6 +160,51 @@ float wnhost_eval3d_projected(const float *coef, int n, const float p[3], const 
                 if ((double)weight > 1e-6) // :257 compares with a double literal
                     result += weight * coef[wrap(c0, n) + wrap(c1, n) * n + wrap(c2, n) * n * n];
             }
+    return result;
+}
+
+float wnhost_eval3d_projected_grad(const float *coef, int n, const float p[3], const float nrm[3], float grad[3])
+{
+    grad[0] = grad[1] = grad[2] = 0.0f;
+    if (!coef || n <= 0) return 0.0f;
+    int lo[3], hi[3];
+    float pm[3], hn[3];
+    for (int i = 0; i < 3; ++i) { // wnhost_eval3d_projected's box; p - 1.5f and n / 2 once
+        const float support = 3.0f * std::fabs(nrm[i]) + 3.0f * std::sqrt((1.0f - nrm[i] * nrm[i]) / 2.0f);
+        lo[i] = (int)std::ceil(p[i] - support);
+        hi[i] = (int)std::floor(p[i] + support);
+        pm[i] = p[i] - 1.5f;
+        hn[i] = nrm[i] / 2.0f;
+    }
+    float result = 0.0f, gx = 0.0f, gy = 0.0f, gz = 0.0f;
+    for (int c2 = lo[2]; c2 <= hi[2]; ++c2)
+        for (int c1 = lo[1]; c1 <= hi[1]; ++c1)
+            for (int c0 = lo[0]; c0 <= hi[0]; ++c0) {
+                const float cf[3] = {(float)c0, (float)c1, (float)c2};
+                float dot = 0.0f;
+                for (int i = 0; i < 3; ++i) dot += nrm[i] * (p[i] - cf[i]);
+                float b[3], d[3];
+                bool inside = true;
+                for (int i = 0; i < 3; ++i) {
+                    const float t = (cf[i] + nrm[i] * dot / 2.0f) - pm[i];
+                    inside = inside && t > 0.0f && t < 3.0f;
+                    const float t1 = t - 1.0f, t2 = 2.0f - t, t3 = 3.0f - t;
+                    b[i] = t < 1.0f ? (t * t / 2.0f) : (t < 2.0f ? (1.0f - (t1 * t1 + t2 * t2) / 2.0f) : (t3 * t3 / 2.0f));
+                    d[i] = t < 1.0f ? t : (t < 2.0f ? t2 - t1 : -t3);
+                }
+                if (!inside) continue;
+                const float c = coef[wrap(c0, n) + wrap(c1, n) * n + wrap(c2, n) * n * n];
+                const float weight = b[0] * b[1] * b[2];
+                if ((double)weight > 1e-6) result += weight * c; // the value's cut; the gradient is uncut
+                const float g0 = d[0] * b[1] * b[2], g1 = b[0] * d[1] * b[2], g2 = b[0] * b[1] * d[2];
+                const float s = nrm[0] * g0 + nrm[1] * g1 + nrm[2] * g2;
+                gx += (hn[0] * s - g0) * c;
+                gy += (hn[1] * s - g1) * c;
+                gz += (hn[2] * s - g2) * c;
+            }
+    grad[0] = gx;
+    grad[1] = gy;
+    grad[2] = gz;
     return result;
 }
 

@@ -27,12 +27,21 @@ extern "C" {
 
 // `coef`: the tile's n^2 / n^3 coefficients, x fastest (WaveletNoise::getNoiseCoefficients()); n == 0 or coef == NULL -> 0.0f
 WNHOST_API float wnhost_eval2d(const float *coef, int n, const float p[2]);                                  // WaveletNoise.cpp:111-140
+// evaluate2D and its gradient (absent from the reference): returns the value (the bits of wnhost_eval2d), writes d/dx,
+// d/dy to grad -- tap weights d_x*w_y, w_x*d_y in evaluate2D's order, unfused: the bits of wn_eval2d_grad_points.
+// n == 0 or coef == NULL -> 0 in all three.
+WNHOST_API float wnhost_eval2d_grad(const float *coef, int n, const float p[2], float grad[2]);
 WNHOST_API float wnhost_eval3d(const float *coef, int n, const float p[3]);                                  // WaveletNoise.cpp:185-215
 // evaluate3D and its gradient (absent from the reference): returns the value (the bits of wnhost_eval3d), writes
 // d/dx, d/dy, d/dz to grad -- tap weights (d_x*w_y)*w_z, (w_x*d_y)*w_z, (w_x*w_y)*d_z in evaluate3D's order, unfused:
 // the bits of wn_eval3d_grad_points.  n == 0 or coef == NULL -> 0 in all four.
 WNHOST_API float wnhost_eval3d_grad(const float *coef, int n, const float p[3], float grad[3]);
 WNHOST_API float wnhost_eval3d_projected(const float *coef, int n, const float p[3], const float normal[3]); // WaveletNoise.cpp:218-265
+// evaluate3DProjected and its gradient with respect to p, the normal held fixed (absent from the reference): returns the
+// value (the bits of wnhost_eval3d_projected, its 1e-6 cut included), writes the gradient of the uncut sum over the same
+// box to grad (include/wnoise.h): the bits of wn_eval3d_projected_grad_points.  n == 0 or coef == NULL -> 0 in all four.
+WNHOST_API float wnhost_eval3d_projected_grad(const float *coef, int n, const float p[3], const float normal[3],
+                                              float grad[3]);
 // `perm`: the 512-entry table (perlin.h:34-39)
 WNHOST_API double wnhost_perlin(const int *perm, double x, double y, double z);      // perlin.h:42-62
 WNHOST_API double wnhost_perlin_fractal(const int *perm, const float q[3]);           // perlin.h:75-90

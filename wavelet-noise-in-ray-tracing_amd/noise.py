@@ -225,13 +225,49 @@ class WaveletNoise:
         check(_lib.wn_eval3d_grad_points(self._handle(3), _ptr(pts), pts.shape[0], _ptr(out), _stream()))
         return out
 
-    def WMultibandNoiseGradient(self, p, s, firstBand, nbands, w, variance=0.18402):
-        """WMultibandNoise (normal == NULL) and its gradient with respect to p (wn_multiband3d_grad_points)."""
+    def WMultibandNoiseGradient(self, p, s, firstBand, nbands, w, variance=None, normal=None):
+        """WMultibandNoise and its gradient with respect to p.  normal=None: bands are evaluate3D
+        (wn_multiband3d_grad_points; variance defaults to 0.18402); with a normal (one for all points, or one per point)
+        bands are evaluate3DProjected (wn_multiband3d_projected_grad_points; variance defaults to 0.296)."""
         pts = _dev(p, torch.float32).reshape(-1, 3)
         out = torch.empty((pts.shape[0], 4), dtype=torch.float32, device="cuda")
         wa = (C.c_float * max(1, nbands))(*[float(x) for x in list(w)[:nbands]])
+        if normal is not None:
+            nr = _dev(normal, torch.float32).reshape(-1, 3)
+            one = nr.shape[0] == 1
+            if not one and nr.shape[0] != pts.shape[0]:
+                raise ValueError("normal: one vector, or one per point")
+            check(_lib.wn_multiband3d_projected_grad_points(self._handle(3), _ptr(pts), _ptr(nr), int(one), pts.shape[0],
+                                                            float(s), int(firstBand), int(nbands), wa,
+                                                            float(0.296 if variance is None else variance), _ptr(out),
+                                                            _stream()))
+            return out
+        variance = 0.18402 if variance is None else variance
         check(_lib.wn_multiband3d_grad_points(self._handle(3), _ptr(pts), pts.shape[0], float(s), int(firstBand),
                                               int(nbands), wa, float(variance), _ptr(out), _stream()))
+        return out
+
+    def evaluate2DGradient(self, p):
+        """evaluate2D and its gradient at one point or an (N, 2) batch (wn_eval2d_grad_points): an (N, 3) CUDA tensor of
+        {value, d/dx, d/dy}; the value column has the bits of evaluate2D."""
+        pts = _dev(p, torch.float32).reshape(-1, 2)
+        out = torch.empty((pts.shape[0], 3), dtype=torch.float32, device="cuda")
+        check(_lib.wn_eval2d_grad_points(self._handle(2), _ptr(pts), pts.shape[0], _ptr(out), _stream()))
+        return out
+
+    def evaluate3DProjectedGradient(self, p, normal):
+        """evaluate3DProjected and its gradient with respect to p, the normal held fixed (wn_eval3d_projected_grad_points):
+        (N, 4).  `normal`: one for all points, or one per point.  The value column has the bits of evaluate3DProjected;
+        the gradient is that of the sum without the value's 1e-6 weight cut (include/wnoise.h)."""
+        pts = _dev(p, torch.float32).reshape(-1, 3)
+        nr = _dev(normal, torch.float32).reshape(-1, 3)
+        if nr.shape[0] == 1 and pts.shape[0] != 1:
+            nr = nr.expand(pts.shape[0], 3).contiguous()
+        if nr.shape[0] != pts.shape[0]:
+            raise ValueError("normal: one vector, or one per point")
+        out = torch.empty((pts.shape[0], 4), dtype=torch.float32, device="cuda")
+        check(_lib.wn_eval3d_projected_grad_points(self._handle(3), _ptr(pts), _ptr(nr), pts.shape[0], _ptr(out),
+                                                   _stream()))
         return out
 
 
@@ -551,6 +587,30 @@ def multiband_gradient_volume(noise, den, nx, ny, z0, z1, s=-16.0, firstBand=0, 
     wa = (C.c_float * max(1, nbands))(*[float(x) for x in w[:nbands]])
     check(_lib.wn_multiband3d_grad_grid(noise._handle(3), C.byref(gc), float(s), int(firstBand),
                                         int(nbands), wa, float(variance), _ptr(out), _stream()))
+    return out[: 4 * g.nz * ny * nx].view(4, g.nz, ny, nx)
+
+
+def wavelet2d_gradient_image(noise, den, nx, ny, octave, out=None):
+    """generate2DOctaveBandNoise's lattice with the gradient (wn_eval2d_grad_grid): [3, ny, nx] -- value, d/dx, d/dy
+    with respect to the coordinate passed to evaluate2D, all three times 1/sqrt(0.19686)."""
+    g = GridSpec(den, nx, ny, octave_scale=_octave_scale(octave), post_scale=2.0, out_scale=_inv_stddev(0.19686))
+    n = 3 * ny * nx
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device="cuda")
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= n
+    gc = g.c()
+    check(_lib.wn_eval2d_grad_grid(noise._handle(2), C.byref(gc), _ptr(out), _stream()))
+    return out[:n].view(3, ny, nx)
+
+
+def projected_gradient_volume(noise, den, nx, ny, z0, z1, octave, normal=(0.0, 0.0, 1.0), out=None):
+    """wavelet_volume's lattice through evaluate3DProjected with one normal, and the gradient with respect to the
+    coordinate passed to it (wn_eval3d_projected_grad_grid): [4, nz, ny, nx], all four times 1/sqrt(0.296)."""
+    g = GridSpec(den, nx, ny, z0, z1, octave_scale=_octave_scale(octave), post_scale=2.0, out_scale=_inv_stddev(0.296))
+    out = _grad_out(g, out)
+    gc = g.c()
+    nr = (C.c_float * 3)(*[float(v) for v in normal])
+    check(_lib.wn_eval3d_projected_grad_grid(noise._handle(3), C.byref(gc), nr, _ptr(out), _stream()))
     return out[: 4 * g.nz * ny * nx].view(4, g.nz, ny, nx)
 
 
