@@ -1,0 +1,445 @@
+// wn_eval.hpp -- the per-sample evaluators in the reference's exact operation order, each stated once for the HIP kernels
+// (csrc/) and for the host's wnhost_* functions (host/scalar_eval.cpp).  Both compilers build it with -ffp-contract=off:
+// every product and sum below rounds once, as on the reference's baseline x86-64 build, so host and device return the
+// same bits as the CPU classes.  Only <cmath> / <cstdint>: no HIP header, so that a plain C++ compiler can include it.
+#pragma once
+
+#include <cmath>
+#include <cstdint>
+
+#if defined(__HIPCC__)
+#define WN_EVAL_FN __host__ __device__ __forceinline__
+#define WN_UNROLL _Pragma("unroll")
+#else
+#define WN_EVAL_FN inline __attribute__((always_inline))
+#define WN_UNROLL
+#endif
+
+namespace wn {
+
+// n-1 when n is a power of two (indices wrap with a mask), else -1.
+WN_EVAL_FN int pow2_mask(int n) { return (n > 0 && (n & (n - 1)) == 0) ? n - 1 : -1; }
+
+// Non-negative modulo (WaveletNoise.cpp:31-34); `mask` = n-1 when n is a power of two, else -1.
+WN_EVAL_FN int dmod(int x, int n, int mask)
+{
+    if (mask >= 0) return x & mask;
+    int m = x % n;
+    return m < 0 ? m + n : m;
+}
+
+// Quadratic B-spline weights (WaveletNoise.cpp:194-200).
+WN_EVAL_FN void bspline(float p, int &mid, float &w0, float &w1, float &w2)
+{
+    const float pm = p - 0.5f;
+    const float cm = ceilf(pm);
+    mid = (int)cm;
+    const float t = cm - pm;
+    w0 = t * t / 2.0f;
+    w2 = (1.0f - t) * (1.0f - t) / 2.0f;
+    w1 = 1.0f - w0 - w2;
+}
+
+// bspline, and the derivatives of the three weights with respect to p (dt/dp = -1): d0 = -t, d1 = 2t - 1, d2 = 1 - t.
+WN_EVAL_FN void bspline_grad(float p, int &mid, float w[3], float d[3])
+{
+    bspline(p, mid, w[0], w[1], w[2]);
+    const float t = (float)mid - (p - 0.5f);
+    d[0] = -t;
+    d[1] = 2.0f * t - 1.0f;
+    d[2] = 1.0f - t;
+}
+
+// WaveletNoise::evaluate2D, WaveletNoise.cpp:111-140 (f1 outer, f0 inner; weight = w0*w1).
+// GRAD: beside the value's sum (unchanged: the same bits) the two derivative sums over the same 9 coefficients, tap
+// weights d_x*w_y and w_x*d_y, each accumulated f1 -> f0, unfused; d/dx, d/dy go to g.
+template <bool GRAD = false>
+WN_EVAL_FN float eval2d_exact(const float *coef, int n, int nmask, float px, float py, float *g = nullptr)
+{
+    if (n == 0) { // :112-114; the empty tile: 0 in every channel
+        if constexpr (GRAD) g[0] = g[1] = 0.0f;
+        return 0.0f;
+    }
+    int mx, my;
+    float wx[3], wy[3], dx[3], dy[3];
+    if constexpr (GRAD) {
+        bspline_grad(px, mx, wx, dx);
+        bspline_grad(py, my, wy, dy);
+    } else {
+        bspline(px, mx, wx[0], wx[1], wx[2]);
+        bspline(py, my, wy[0], wy[1], wy[2]);
+    }
+    int cx[3], cy[3];
+    WN_UNROLL
+    for (int f = 0; f < 3; ++f) {
+        cx[f] = dmod(mx + f - 1, n, nmask);
+        cy[f] = dmod(my + f - 1, n, nmask) * n;
+    }
+    float result = 0.0f, gx = 0.0f, gy = 0.0f;
+    WN_UNROLL
+    for (int fy = 0; fy < 3; ++fy)
+        WN_UNROLL
+        for (int fx = 0; fx < 3; ++fx) {
+            const float weight = wx[fx] * wy[fy];
+            const float c = coef[cx[fx] + cy[fy]];
+            result += weight * c;
+            if constexpr (GRAD) {
+                gx += dx[fx] * wy[fy] * c;
+                gy += wx[fx] * dy[fy] * c;
+            }
+        }
+    if constexpr (GRAD) {
+        g[0] = gx;
+        g[1] = gy;
+    }
+    return result;
+}
+
+// WaveletNoise::evaluate3D, WaveletNoise.cpp:185-215 (f2 outer, f0 inner; weight=(w0*w1)*w2).
+// PADDED: `coef` is wn_tile::dev_padded (row stride n+2 with two wrap-around columns), so the
+// three x taps of every (y,z) row are adjacent and fetched with one 12-byte load; the values, the
+// arithmetic and its order are those of the linear layout.
+// POW2: the tile size is a power of two and the wrap a mask.  The general modulo behind a run-time test per index splits the
+// nine loads into basic blocks (a branch per wrap); eval3d_exact tests once and calls the form that has none.
+// GRAD: beside the value's sum (unchanged: the same bits) the three derivative sums over the same 27 coefficients, tap
+// weights (d_x*w_y)*w_z, (w_x*d_y)*w_z and (w_x*w_y)*d_z, each accumulated f2 -> f1 -> f0, unfused; the gradient goes to g.
+template <bool PADDED, bool POW2, bool GRAD>
+WN_EVAL_FN float eval3d_exact_impl(const float *coef, int n, int nmask, float px, float py, float pz, float *g)
+{
+    int mx, my, mz;
+    float wx[3], wy[3], wz[3], dx[3], dy[3], dz[3];
+    if constexpr (GRAD) {
+        bspline_grad(px, mx, wx, dx);
+        bspline_grad(py, my, wy, dy);
+        bspline_grad(pz, mz, wz, dz);
+    } else {
+        bspline(px, mx, wx[0], wx[1], wx[2]);
+        bspline(py, my, wy[0], wy[1], wy[2]);
+        bspline(pz, mz, wz[0], wz[1], wz[2]);
+    }
+    const int stride = PADDED ? n + 2 : n;
+    int cx[3], cy[3], cz[3];
+    WN_UNROLL
+    for (int f = 0; f < 3; ++f) {
+        cx[f] = POW2 ? ((mx + f - 1) & nmask) : dmod(mx + f - 1, n, -1);
+        cy[f] = (POW2 ? ((my + f - 1) & nmask) : dmod(my + f - 1, n, -1)) * stride;
+        cz[f] = (POW2 ? ((mz + f - 1) & nmask) : dmod(mz + f - 1, n, -1)) * stride * n;
+    }
+    float result = 0.0f, gx = 0.0f, gy = 0.0f, gz = 0.0f;
+    WN_UNROLL
+    for (int fz = 0; fz < 3; ++fz)
+        WN_UNROLL
+        for (int fy = 0; fy < 3; ++fy) {
+            float c[3];
+            if (PADDED) {
+                __builtin_memcpy(c, coef + cx[0] + cy[fy] + cz[fz], sizeof(c)); // global_load_dwordx3
+            } else {
+                WN_UNROLL
+                for (int fx = 0; fx < 3; ++fx) c[fx] = coef[cx[fx] + cy[fy] + cz[fz]];
+            }
+            WN_UNROLL
+            for (int fx = 0; fx < 3; ++fx) {
+                const float weight = wx[fx] * wy[fy] * wz[fz];
+                result += weight * c[fx];
+                if constexpr (GRAD) {
+                    gx += dx[fx] * wy[fy] * wz[fz] * c[fx];
+                    gy += wx[fx] * dy[fy] * wz[fz] * c[fx];
+                    gz += wx[fx] * wy[fy] * dz[fz] * c[fx];
+                }
+            }
+        }
+    if constexpr (GRAD) {
+        g[0] = gx;
+        g[1] = gy;
+        g[2] = gz;
+    }
+    return result;
+}
+
+template <bool PADDED = false>
+WN_EVAL_FN float eval3d_exact(const float *coef, int n, int nmask, float px, float py, float pz)
+{
+    if (n == 0) return 0.0f; // :186-188
+    return nmask >= 0 ? eval3d_exact_impl<PADDED, true, false>(coef, n, nmask, px, py, pz, nullptr)
+                      : eval3d_exact_impl<PADDED, false, false>(coef, n, nmask, px, py, pz, nullptr);
+}
+
+// Returns the value, writes the gradient to g.
+template <bool PADDED = false>
+WN_EVAL_FN float eval3d_grad_exact(const float *coef, int n, int nmask, float px, float py, float pz, float g[3])
+{
+    if (n == 0) { // the empty tile: 0 in all four channels
+        g[0] = g[1] = g[2] = 0.0f;
+        return 0.0f;
+    }
+    return nmask >= 0 ? eval3d_exact_impl<PADDED, true, true>(coef, n, nmask, px, py, pz, g)
+                      : eval3d_exact_impl<PADDED, false, true>(coef, n, nmask, px, py, pz, g);
+}
+
+// ---- WaveletNoise::evaluate3DProjected, WaveletNoise.cpp:218-265 -------------------------------------------------------
+// Axis i of the data-dependent support box of the projected basis around p, :226-231.
+WN_EVAL_FN void projected_box(const float p[3], const float nrm[3], int i, int lo[3], int hi[3])
+{
+    const float support = 3.0f * fabsf(nrm[i]) + 3.0f * sqrtf((1.0f - nrm[i] * nrm[i]) / 2.0f);
+    lo[i] = (int)ceilf(p[i] - support);
+    hi[i] = (int)floorf(p[i] + support);
+}
+
+// One axis of the projected basis at 0 < t < 3, :249-253: B(t), and B'(t) = t, t2 - t1, -t3 on the three pieces to d.
+template <bool GRAD>
+WN_EVAL_FN float projected_piece(float t, float *d)
+{
+    const float t1 = t - 1.0f, t2 = 2.0f - t, t3 = 3.0f - t;
+    const float b = t < 1.0f ? (t * t / 2.0f) : (t < 2.0f ? (1.0f - (t1 * t1 + t2 * t2) / 2.0f) : (t3 * t3 / 2.0f));
+    if constexpr (GRAD) *d = t < 1.0f ? t : (t < 2.0f ? t2 - t1 : -t3);
+    return b;
+}
+
+// The value: `break` on the first axis outside the basis support, contributions <= 1e-6 skipped.
+WN_EVAL_FN float projected_exact(const float *coef, int n, int nmask, const float p[3], const float nrm[3])
+{
+    if (n == 0) return 0.0f; // :219-221
+    int lo[3], hi[3];
+    WN_UNROLL
+    for (int i = 0; i < 3; ++i) projected_box(p, nrm, i, lo, hi);
+    float result = 0.0f;
+    for (int c2 = lo[2]; c2 <= hi[2]; ++c2)
+        for (int c1 = lo[1]; c1 <= hi[1]; ++c1)
+            for (int c0 = lo[0]; c0 <= hi[0]; ++c0) {
+                const float cf[3] = {(float)c0, (float)c1, (float)c2};
+                float dot = 0.0f;
+                WN_UNROLL
+                for (int i = 0; i < 3; ++i) dot += nrm[i] * (p[i] - cf[i]);
+                float weight = 1.0f;
+                bool outside = false;
+                WN_UNROLL
+                for (int i = 0; i < 3; ++i) {
+                    if (!outside) {
+                        const float t = (cf[i] + nrm[i] * dot / 2.0f) - (p[i] - 1.5f);
+                        if (t <= 0.0f || t >= 3.0f) {
+                            weight = 0.0f;
+                            outside = true;
+                        } else {
+                            weight *= projected_piece<false>(t, nullptr);
+                        }
+                    }
+                }
+                if ((double)weight > 1e-6) { // :257 compares against a double literal
+                    const int idx = dmod(c0, n, nmask) + dmod(c1, n, nmask) * n + dmod(c2, n, nmask) * n * n;
+                    result += weight * coef[idx];
+                }
+            }
+    return result;
+}
+
+// evaluate3DProjected and its gradient with respect to p, the normal held fixed.  One pass over projected_exact's support
+// box.  A cell with t_i = (c_i + n_i*dot/2) - (p_i - 1.5), dot = sum_k n_k (p_k - c_k), has weight prod_i B(t_i); with
+// G_i = B'(t_i) prod_{k!=i} B(t_k) and S = sum_i n_i G_i, dt_i/dp_j = n_i n_j / 2 - delta_ij gives
+// d weight / dp_j = (n_j/2) S - G_j.
+//  - value: projected_exact's arithmetic, cell for cell (the same t, the same (B0*B1)*B2, the same weight > 1e-6 cut): its
+//    bits.  Its per-axis `break` only ends a product that is then 0 and cut, so every axis's t is formed here up front.
+//  - gradient: EVERY cell with 0 < t_i < 3 on all three axes, no 1e-6 cut (a cut sum would jump by up to ~1e-3 |c| when a
+//    cell crosses the threshold; the uncut sum is C1).  G_i = (B'0*B1)*B2, (B0*B'1)*B2, (B0*B1)*B'2; S = (n0 G0 + n1 G1) +
+//    n2 G2; each dweight_j * c accumulated in the box's order (c2 -> c1 -> c0), unfused.
+// The box is the value's: no cell outside it has 0 < t < 3 on all three axes (its half-width 3|n_i| + 3 sqrt((1-n_i^2)/2)
+// bounds |p_i - c_i| of every such cell).  Returns the value, writes the gradient to g.
+WN_EVAL_FN float projected_grad_exact(const float *coef, int n, int nmask, const float p[3], const float nrm[3], float g[3])
+{
+    if (n == 0) { // the empty tile: 0 in all four channels
+        g[0] = g[1] = g[2] = 0.0f;
+        return 0.0f;
+    }
+    // per point, once: the box, p_i - 1.5f and n_j / 2
+    int lo[3], hi[3];
+    float pm[3], hn[3];
+    WN_UNROLL
+    for (int i = 0; i < 3; ++i) {
+        projected_box(p, nrm, i, lo, hi);
+        pm[i] = p[i] - 1.5f;
+        hn[i] = nrm[i] / 2.0f;
+    }
+    float result = 0.0f, gx = 0.0f, gy = 0.0f, gz = 0.0f;
+    for (int c2 = lo[2]; c2 <= hi[2]; ++c2)
+        for (int c1 = lo[1]; c1 <= hi[1]; ++c1)
+            for (int c0 = lo[0]; c0 <= hi[0]; ++c0) {
+                const float cf[3] = {(float)c0, (float)c1, (float)c2};
+                float dot = 0.0f;
+                WN_UNROLL
+                for (int i = 0; i < 3; ++i) dot += nrm[i] * (p[i] - cf[i]);
+                float b[3], d[3];
+                bool inside = true;
+                WN_UNROLL
+                for (int i = 0; i < 3; ++i) {
+                    const float t = (cf[i] + nrm[i] * dot / 2.0f) - pm[i];
+                    inside = inside && t > 0.0f && t < 3.0f;
+                    b[i] = projected_piece<true>(t, &d[i]);
+                }
+                if (inside) {
+                    const float c = coef[dmod(c0, n, nmask) + dmod(c1, n, nmask) * n + dmod(c2, n, nmask) * n * n];
+                    const float weight = b[0] * b[1] * b[2];
+                    if ((double)weight > 1e-6) result += weight * c;
+                    const float g0 = d[0] * b[1] * b[2], g1 = b[0] * d[1] * b[2], g2 = b[0] * b[1] * d[2];
+                    const float s = nrm[0] * g0 + nrm[1] * g1 + nrm[2] * g2;
+                    gx += (hn[0] * s - g0) * c;
+                    gy += (hn[1] * s - g1) * c;
+                    gz += (hn[2] * s - g2) * c;
+                }
+            }
+    g[0] = gx;
+    g[1] = gy;
+    g[2] = gz;
+    return result;
+}
+
+// WMultibandNoise (paper Appendix 2): sum_b w[b] * f(q_b), q_b = 2 * p * 2^(first_band+b), divided by out_div when
+// apply_div.  f is evaluate3D (PROJECTED false: the normal == NULL branch, nrm unused) or evaluate3DProjected(q_b, nrm).
+// GRAD: also the gradient with respect to p to g: band b adds (w[b] * (2 * 2^(first_band+b))) * grad f(q_b) (the chain
+// rule of q_b), divided like the value, whose bits do not change.  `a` carries coef, n, nmask and the bands of
+// wn::multiband_bands.  (The value arm reads w[b] before f and the gradient arm after it: the kernels' code depends on that order.)
+template <bool PADDED, bool PROJECTED, bool GRAD, typename A>
+WN_EVAL_FN float multiband_exact(const A &a, const float p[3], const float *nrm, float *g)
+{
+    float v = 0.0f, gx = 0.0f, gy = 0.0f, gz = 0.0f;
+    for (int b = 0; b < a.nbands; ++b) {
+        const float s = a.band_scale[b];
+        const float q[3] = {2.0f * p[0] * s, 2.0f * p[1] * s, 2.0f * p[2] * s};
+        if constexpr (GRAD) {
+            float gb[3];
+            const float e = PROJECTED ? projected_grad_exact(a.coef, a.n, a.nmask, q, nrm, gb)
+                                      : eval3d_grad_exact<PADDED>(a.coef, a.n, a.nmask, q[0], q[1], q[2], gb);
+            v += a.band_w[b] * e;
+            const float f = a.band_w[b] * (2.0f * s);
+            gx += f * gb[0];
+            gy += f * gb[1];
+            gz += f * gb[2];
+        } else {
+            v += a.band_w[b] * (PROJECTED ? projected_exact(a.coef, a.n, a.nmask, q, nrm)
+                                          : eval3d_exact<PADDED>(a.coef, a.n, a.nmask, q[0], q[1], q[2]));
+        }
+    }
+    if (a.apply_div) {
+        v /= a.out_div;
+        if constexpr (GRAD) {
+            gx /= a.out_div;
+            gy /= a.out_div;
+            gz /= a.out_div;
+        }
+    }
+    if constexpr (GRAD) {
+        g[0] = gx;
+        g[1] = gy;
+        g[2] = gz;
+    }
+    return v;
+}
+
+// ---- Perlin improved noise, fp64 (perlin.h:18-31, 42-62) ------------------------------------------
+WN_EVAL_FN double pfade(double t) { return t * t * t * (t * (t * 6 - 15) + 10); }
+WN_EVAL_FN double plerp(double t, double a, double b) { return a + t * (b - a); }
+WN_EVAL_FN double pgrad(int hash, double x, double y, double z)
+{
+    const int h = hash & 15;
+    const double u = h < 8 ? x : y;
+    const double v = h < 4 ? y : ((h == 12 || h == 14) ? x : z);
+    return ((h & 1) == 0 ? u : -u) + ((h & 2) == 0 ? v : -v);
+}
+
+// `perm` is the 512-entry table (values 0..255; every index the algorithm forms is <= 511, perlin.h:55-61): bytes in LDS
+// or global memory on the device, the reference's `const int *` on the host.
+template <typename Table>
+WN_EVAL_FN double perlin_exact(const Table perm, double x, double y, double z)
+{
+    const double fx = floor(x), fy = floor(y), fz = floor(z);
+    const int X = (int)fx & 255, Y = (int)fy & 255, Z = (int)fz & 255;
+    x -= fx;
+    y -= fy;
+    z -= fz;
+    const double u = pfade(x), v = pfade(y), w = pfade(z);
+    const int A = perm[X] + Y, AA = perm[A] + Z, AB = perm[A + 1] + Z;
+    const int B = perm[X + 1] + Y, BA = perm[B] + Z, BB = perm[B + 1] + Z;
+    const double x00 = plerp(u, pgrad(perm[AA], x, y, z), pgrad(perm[BA], x - 1, y, z));
+    const double x10 = plerp(u, pgrad(perm[AB], x, y - 1, z), pgrad(perm[BB], x - 1, y - 1, z));
+    const double x01 = plerp(u, pgrad(perm[AA + 1], x, y, z - 1), pgrad(perm[BA + 1], x - 1, y, z - 1));
+    const double x11 = plerp(u, pgrad(perm[AB + 1], x, y - 1, z - 1), pgrad(perm[BB + 1], x - 1, y - 1, z - 1));
+    return plerp(w, plerp(v, x00, x10), plerp(v, x01, x11));
+}
+
+// RTOW turb on a float vec3 (absent from the reference): weight halves, point doubles in float.
+template <typename Table>
+WN_EVAL_FN double perlin_turb(const Table perm, float x, float y, float z, int depth)
+{
+    double accum = 0.0, weight = 1.0;
+    for (int i = 0; i < depth; ++i) {
+        accum += weight * perlin_exact(perm, (double)x, (double)y, (double)z);
+        weight *= 0.5;
+        x *= 2.0f;
+        y *= 2.0f;
+        z *= 2.0f;
+    }
+    return fabs(accum);
+}
+
+// perlin::fractal_noise, perlin.h:75-90 (float point times double frequency).
+template <typename Table>
+WN_EVAL_FN double perlin_fractal(const Table perm, float x, float y, float z)
+{
+    double result = 0.0, amplitude = 1.0, frequency = 1.0, max_value = 0.0;
+    for (int i = 0; i < 6; ++i) {
+        result += perlin_exact(perm, x * frequency, y * frequency, z * frequency) * amplitude;
+        max_value += amplitude;
+        amplitude *= 0.5;
+        frequency *= 2.0;
+    }
+    return result / max_value;
+}
+
+// ---- the texture adaptors' per-point arithmetic (texture.h:37-43, 67-107) ----------------------------------------------
+// wavelet_texture's coordinate scaling, texture.h:71-80: (float)(p * scale) * (octave_scale * 2.0f)
+template <typename A>
+WN_EVAL_FN float wavelet_texture_coord(const A &a, float p)
+{
+    float c = (float)((double)p * a.scale);
+    c *= a.octave_mul;
+    return c;
+}
+
+// wavelet_texture's grey level of a normalised noise value v, texture.h:104-106
+WN_EVAL_FN float wavelet_texture_grey(double v)
+{
+    const double q = v / 4.0;
+    const double c = (q < -1.0) ? -1.0 : ((1.0 < q) ? 1.0 : q); // std::clamp
+    return (float)(0.5 * (1.0 + c));
+}
+
+// wavelet_texture::value, texture.h:67-107.  `A` carries coef, n, nmask, mode (3: evaluate3D branch,
+// 2: evaluate2D branch, 0: no tile -> texture.h:100-102), scale (double), octave_mul (octave_scale * 2.0f,
+// :77-80) and inv_stddev (1/sqrt(0.18402f) or 1/sqrt(0.19686f), :84,98).
+template <bool PADDED, typename A>
+WN_EVAL_FN float wavelet_texture_value(const A &a, float px, float py, float pz)
+{
+    double v = 0.0;
+    if (a.mode == 3) {
+        v = (double)eval3d_exact<PADDED>(a.coef, a.n, a.nmask, wavelet_texture_coord(a, px), wavelet_texture_coord(a, py),
+                                         wavelet_texture_coord(a, pz));
+        v *= (double)a.inv_stddev;
+    } else if (a.mode == 2) {
+        v = (double)eval2d_exact(a.coef, a.n, a.nmask, wavelet_texture_coord(a, px), wavelet_texture_coord(a, py));
+        v *= (double)a.inv_stddev;
+    }
+    return wavelet_texture_grey(v);
+}
+
+// noise_texture::value, texture.h:37-43: scaled_p = p * scale * octave_scale in float (vec3 * float,
+// vec3.h:82-84), noise in fp64, 0.5 * (1 + n).
+template <typename Table>
+WN_EVAL_FN float noise_texture_value(const Table perm, float fscale, float octave_scale, float px, float py, float pz)
+{
+    const float sx = (fscale * px) * octave_scale;
+    const float sy = (fscale * py) * octave_scale;
+    const float sz = (fscale * pz) * octave_scale;
+    double v = perlin_exact(perm, (double)sx, (double)sy, (double)sz);
+    v = 0.5 * (1.0 + v);
+    return (float)v;
+}
+
+} // namespace wn

@@ -11,6 +11,7 @@
 #include <cstdint>
 #include <cstdio>
 
+#include "wn_eval.hpp" // dmod, pow2_mask, bspline and the exact evaluators, shared with host/scalar_eval.cpp
 #include "wnoise.h"
 
 struct wn_tile {
@@ -83,9 +84,6 @@ struct GridArgs {
 };
 
 int check_grid(const wn_grid *g, bool needs_z, GridArgs *out);
-
-// n-1 when n is a power of two (indices wrap with a mask), else -1.
-__host__ __device__ __forceinline__ int pow2_mask(int n) { return (n > 0 && (n & (n - 1)) == 0) ? n - 1 : -1; }
 
 // 1/den when den is a power of two (then i * (1/den) == i / den exactly), else 0: see lattice_coord_fast.
 inline float inv_den_of(int den) { return ((den & (den - 1)) == 0) ? 1.0f / (float)den : 0.0f; }
@@ -194,14 +192,6 @@ int tile_build_padded(wn_tile *t, hipStream_t stream);
 #if defined(__HIPCC__)
 namespace wn {
 
-// Non-negative modulo (WaveletNoise.cpp:31-34); `mask` = n-1 when n is a power of two, else -1.
-__device__ __forceinline__ int dmod(int x, int n, int mask)
-{
-    if (mask >= 0) return x & mask;
-    int m = x % n;
-    return m < 0 ? m + n : m;
-}
-
 // Lattice coordinate of index i (experient/main.cpp:20-26): ((float(i)/den)*range)*octave*post,
 // one float rounding per operation, division IEEE-correct (hipcc default
 // -fhip-fp32-correctly-rounded-divide-sqrt).
@@ -227,28 +217,6 @@ __device__ __forceinline__ float lattice_coord_fast(int i, float den, float inv_
 
 // Workgroup barrier that waits for the wave's LDS accesses only: no vmcnt drain of its outstanding global loads and stores.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// Quadratic B-spline weights (WaveletNoise.cpp:194-200).
-__device__ __forceinline__ void bspline(float p, int &mid, float &w0, float &w1, float &w2)
-{
-    const float pm = p - 0.5f;
-    const float cm = ceilf(pm);
-    mid = (int)cm;
-    const float t = cm - pm;
-    w0 = t * t / 2.0f;
-    w2 = (1.0f - t) * (1.0f - t) / 2.0f;
-    w1 = 1.0f - w0 - w2;
-}
-
-// bspline, and the derivatives of the three weights with respect to p (dt/dp = -1): d0 = -t, d1 = 2t - 1, d2 = 1 - t.
-__device__ __forceinline__ void bspline_grad(float p, int &mid, float w[3], float d[3])
-{
-    bspline(p, mid, w[0], w[1], w[2]);
-    const float t = (float)mid - (p - 0.5f);
-    d[0] = -t;
-    d[1] = 2.0f * t - 1.0f;
-    d[2] = 1.0f - t;
-}
 
 } // namespace wn
 #endif

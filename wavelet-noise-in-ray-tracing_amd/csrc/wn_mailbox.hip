@@ -5,7 +5,7 @@
 // calls (main.cpp:38-59 through material.h:72).  Here a RESIDENT one-wave kernel polls a mailbox in
 // pinned, device-mapped host memory: the host writes the request (one 64-byte line, sequence number
 // last), the wave picks it up, evaluates it with the same exact device functions the batched kernels
-// use (wn_device_eval.hpp / wn_texture_eval.hpp -> bit-identical results), and writes value and
+// use (wn_eval.hpp -> bit-identical results), and writes value and
 // sequence number back.  A call is two PCIe round trips plus the evaluation.
 //
 // The kernel is not immortal: after kIdleTicks (2 ms) without a request, or kLifeTicks (20 ms) after its start
@@ -16,8 +16,6 @@
 // posted while an instance is timing out is never lost: the host re-launches when it sees STOPPED with
 // its request unanswered, and an instance starts from the last ANSWERED sequence number.
 #include "wn_internal.hpp"
-#include "wn_device_eval.hpp"
-#include "wn_texture_eval.hpp"
 
 #include <chrono>
 #include <cmath>

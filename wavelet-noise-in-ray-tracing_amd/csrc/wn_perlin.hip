@@ -10,7 +10,6 @@
 #include "wn_internal.hpp"
 #include "wn_device_eval.hpp"
 #include "wn_perlin_run.hpp"
-#include "wn_texture_eval.hpp"
 
 #include <cmath>
 
@@ -333,7 +332,7 @@ struct NoiseTexArgs {
 __device__ __forceinline__ float noise_texture_value(const uint8_t *perm, const NoiseTexArgs &a, float px, float py,
                                                      float pz)
 {
-    return wn::noise_texture_value(perm, a.fscale, a.octave_scale, px, py, pz); // wn_texture_eval.hpp
+    return wn::noise_texture_value(perm, a.fscale, a.octave_scale, px, py, pz); // wn_eval.hpp
 }
 
 template <bool MASKED>

@@ -11,7 +11,6 @@
 // A workgroup (4 waves) owns 256 x 8 x 8 samples; a lane owns 4 consecutive x samples (one float4 store per row),
 // a wave 16 of the brick's 64 rows.  Lattices whose box does not fit (coarse steps) stay with the gather kernel.
 #include "wn_internal.hpp"
-#include "wn_device_eval.hpp"
 
 #include <algorithm>
 #include <cmath>

@@ -6,7 +6,7 @@
 // d0 = -t, d1 = 2t - 1, d2 = 1 - t on the same taps.  The spline is C1: the gradient is continuous, also where mid flips.
 // Each derivative reads the value's 27 coefficients; only the per-axis weights change.
 //
-//   grad3d_points_kernel<PADDED, MB>   one point per lane, wn::eval3d_grad_exact / multiband3d_grad_exact (the value
+//   grad3d_points_kernel<PADDED, MB>   one point per lane, wn::eval3d_grad_exact / multiband_exact (the value
 //                                      channel has the bits of wn_eval3d_points / wn_multiband3d_points), one 16-byte
 //                                      {value, d/dx, d/dy, d/dz} store per point.
 //   grad3d_grid_direct_kernel<PADDED>  WN_GRID_EXACT and every lattice the brick kernel declines: one sample per lane, the
@@ -18,7 +18,6 @@
 // The gradient is taken with respect to the coordinate the sample passes to evaluate3D (multiband: the lattice coordinate
 // p), and out_scale multiplies all four channels last.
 #include "wn_internal.hpp"
-#include "wn_device_eval.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -50,7 +49,7 @@ __global__ __launch_bounds__(256) void grad3d_points_kernel(const GradPointsArgs
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.count; i += (size_t)gridDim.x * blockDim.x) {
         const float p[3] = {a.pts[3 * i], a.pts[3 * i + 1], a.pts[3 * i + 2]};
         float g[3];
-        const float v = MB ? wn::multiband3d_grad_exact<PADDED>(a, p, g)
+        const float v = MB ? wn::multiband_exact<PADDED, false, true>(a, p, nullptr, g)
                            : wn::eval3d_grad_exact<PADDED>(a.coef, a.n, a.nmask, p[0], p[1], p[2], g);
         a.out[i] = v4f{v, g[0], g[1], g[2]};
     }
@@ -85,7 +84,7 @@ __global__ __launch_bounds__(256) void grad3d_grid_direct_kernel(const GradDirec
                                            : wn::lattice_coord(g.z0 + z, den, g.base_range, g.octave_scale, g.post_scale)};
         float gr[3];
         const float v = a.nbands == 0 ? wn::eval3d_grad_exact<PADDED>(a.coef, a.n, a.nmask, p[0], p[1], p[2], gr)
-                                      : wn::multiband3d_grad_exact<PADDED>(a, p, gr);
+                                      : wn::multiband_exact<PADDED, false, true>(a, p, nullptr, gr);
         a.out[e] = v * g.out_scale;
         a.out[e + a.vol] = gr[0] * g.out_scale;
         a.out[e + 2 * a.vol] = gr[1] * g.out_scale;

@@ -8,13 +8,13 @@
 // fixed) is sum_cells ((n_j/2) S - G_j) c, G_i = B'(t_i) prod_{k!=i} B(t_k), S = sum_i n_i G_i, over EVERY cell with
 // 0 < t < 3 on all three axes -- the value's 1e-6 weight cut is not applied to the gradient (wn::projected_grad_exact).
 //
-//   grad2d_points_kernel                  one point per lane, wn::eval2d_grad_exact (the value has the bits of
+//   grad2d_points_kernel                  one point per lane, wn::eval2d_exact<true> (the value has the bits of
 //                                         wn_eval2d_points), one {value, d/dx, d/dy} record of 3 floats per point.
 //   grad2d_grid_kernel                    one sample per lane at lattice_coord's coordinates; three planes.
 //   grad_projected_points_kernel          one point and its normal per lane, wn::projected_grad_exact (the value has the
 //                                         bits of wn_eval3d_projected_points), one 16-byte {value, d/dx, d/dy, d/dz} store.
 //   grad_projected_grid_kernel            one sample per lane, one normal for the lattice; four volumes.
-//   grad_multiband_projected_points_kernel  wn::multiband3d_projected_grad_exact, one normal for all points or one each.
+//   grad_multiband_projected_points_kernel  wn::multiband_exact, one normal for all points or one each.
 //
 // The projected loop is bound by VALU work (about 40 operations per cell, 175-343 cells per sample), not by its gathers:
 // the value and the gradient come from one pass, and the box, p - 1.5 and n/2 are formed once per sample.  Grids write
@@ -22,7 +22,6 @@
 // gradient is taken with respect to the coordinate the sample passes to the evaluator, and out_scale multiplies every
 // channel last.  There is one tier: every sample has the bits of the point kernel at the lattice's float coordinates.
 #include "wn_internal.hpp"
-#include "wn_device_eval.hpp"
 
 #include <cmath>
 
@@ -55,7 +54,7 @@ __global__ __launch_bounds__(256) void grad2d_points_kernel(const SurfPointsArgs
 {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.count; i += (size_t)gridDim.x * blockDim.x) {
         float g[2];
-        const float v = wn::eval2d_grad_exact(a.coef, a.n, a.nmask, a.pts[2 * i], a.pts[2 * i + 1], g);
+        const float v = wn::eval2d_exact<true>(a.coef, a.n, a.nmask, a.pts[2 * i], a.pts[2 * i + 1], g);
         float *o = a.out + 3 * i;
         o[0] = v;
         o[1] = g[0];
@@ -83,7 +82,7 @@ __global__ __launch_bounds__(256) void grad_multiband_projected_points_kernel(co
         const float *nrp = a.normals + (a.one_normal ? 0 : 3 * i);
         const float nr[3] = {nrp[0], nrp[1], nrp[2]};
         float g[3];
-        const float v = wn::multiband3d_projected_grad_exact(a, p, nr, g);
+        const float v = wn::multiband_exact<false, true, true>(a, p, nr, g);
         out[i] = v4f{v, g[0], g[1], g[2]};
     }
 }
@@ -107,7 +106,7 @@ __global__ __launch_bounds__(256) void grad2d_grid_kernel(const SurfGridArgs a)
         const float px = wn::lattice_coord(x, den, g.base_range, g.octave_scale, g.post_scale);
         const float py = wn::lattice_coord(y, den, g.base_range, g.octave_scale, g.post_scale);
         float gr[2];
-        const float v = wn::eval2d_grad_exact(a.coef, a.n, a.nmask, px, py, gr);
+        const float v = wn::eval2d_exact<true>(a.coef, a.n, a.nmask, px, py, gr);
         a.out[e] = v * g.out_scale;
         a.out[e + a.vol] = gr[0] * g.out_scale;
         a.out[e + 2 * a.vol] = gr[1] * g.out_scale;

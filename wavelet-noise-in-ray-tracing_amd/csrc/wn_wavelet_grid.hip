@@ -25,7 +25,6 @@
 //
 // 2-D and projected grids use direct kernels (bit-identical to evaluate2D / evaluate3DProjected).
 #include "wn_internal.hpp"
-#include "wn_device_eval.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -492,6 +491,8 @@ struct DirectArgs {
     int apply_div;
 };
 
+// (The band sum is wn::multiband_exact's, written out here with the coordinates in both arms: through the helper, or with the
+// coordinates ahead of the branch, the compiler emits other code for this kernel.)
 template <bool PADDED>
 __global__ __launch_bounds__(256) void grid3d_direct_kernel(const DirectArgs a)
 {

@@ -9,7 +9,6 @@
 // batches, so rays that missed the noise-textured surfaces cost no gather slots.
 #include "wn_internal.hpp"
 #include "wn_device_eval.hpp"
-#include "wn_texture_eval.hpp"
 
 #include <cmath>
 
@@ -68,7 +67,7 @@ __global__ __launch_bounds__(256) void multiband3d_points_kernel(const PointsArg
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.count;
          i += (size_t)gridDim.x * blockDim.x) {
         const float *p = a.pts + 3 * i;
-        a.out[i] = wn::multiband3d_exact<PADDED>(a, p);
+        a.out[i] = wn::multiband_exact<PADDED, false, false>(a, p, nullptr, nullptr);
     }
 }
 
@@ -80,14 +79,7 @@ __global__ __launch_bounds__(256) void multiband3d_projected_points_kernel(const
         const float *p = a.pts + 3 * i;
         const float *nrp = a.normals + (a.one_normal ? 0 : 3 * i);
         const float nr[3] = {nrp[0], nrp[1], nrp[2]};
-        float v = 0.0f;
-        for (int b = 0; b < a.nbands; ++b) {
-            const float s = a.band_scale[b];
-            const float q[3] = {2.0f * p[0] * s, 2.0f * p[1] * s, 2.0f * p[2] * s};
-            v += a.band_w[b] * wn::projected_exact(a.coef, a.n, a.nmask, q, nr);
-        }
-        if (a.apply_div) v /= a.out_div;
-        a.out[i] = v;
+        a.out[i] = wn::multiband_exact<false, true, false>(a, p, nr, nullptr);
     }
 }
 
@@ -106,7 +98,7 @@ struct TexArgs {
     int points_per_wave;
 };
 
-using wn::wavelet_texture_value; // wn_texture_eval.hpp
+using wn::wavelet_texture_value; // wn_eval.hpp
 
 template <bool MASKED, bool PADDED>
 __global__ __launch_bounds__(256) void wavelet_texture_kernel(const TexArgs a)
@@ -393,7 +385,7 @@ struct Eval3dOps {
     __device__ float eval(size_t i) const
     {
         const float *p = a.pts + 3 * i;
-        return MULTIBAND ? wn::multiband3d_exact<PADDED>(a, p)
+        return MULTIBAND ? wn::multiband_exact<PADDED, false, false>(a, p, nullptr, nullptr)
                          : wn::eval3d_exact<PADDED>(a.coef, a.n, a.nmask, p[0], p[1], p[2]);
     }
     __device__ void store(size_t i, float v) const { a.out[i] = v; }

@@ -45,7 +45,7 @@ const wn_tile *WaveletNoise::tile(int dims) const
     return tile_;
 }
 
-// ---- scalar members: evaluated on the host from the mirrored coefficients (scalar_eval.h; bit-identical to the kernels), or one
+// ---- scalar members: evaluated on the host from the mirrored coefficients (scalar_eval.h; the kernels' evaluators, csrc/wn_eval.hpp), or one
 // request each to the resident scalar kernel (wn_scalar_*, include/wnoise.h) with WN_SCALAR_ON_DEVICE=1.  A tile of the other
 // dimension goes to the C ABI either way, which reports it.
 float WaveletNoise::evaluate2D(const float p[2]) const

@@ -4,8 +4,10 @@
 // next instruction (the reference's ray tracer: material.h:72 -> texture.h:37-43 / 67-107, 29.6 M calls a render) cannot
 // be served by a device faster than the PCIe round trip (1.9 us measured, profiles/r03_scalar_latency.json); the
 // reference's own call takes ~0.1 us.  These functions are that call: the reference's arithmetic in the reference's order
-// (file:line beside each), written for this library, compiled with -ffp-contract=off into libwnoise_host.so, bit-identical
-// to the reference and to the HIP kernels (tests/test_host_scalar.py, tools/scalar_api_check).
+// (file:line beside each), compiled with -ffp-contract=off into libwnoise_host.so.  scalar_eval.cpp states none of it
+// itself: each function calls the evaluator of csrc/wn_eval.hpp that the HIP kernels call, so host and device share one
+// source and return the same bits, those of the reference (tests/test_host_scalar.py, tools/scalar_api_check).  This
+// header includes nothing from csrc/ and can be copied next to the reference's sources on its own.
 //
 // They are not a fallback: nothing that takes more than one sample (points lists, textures' values(), dense grids, tile
 // generation) has a host form, and the host classes still throw without a HIP device.  WN_SCALAR_ON_DEVICE=1 in the
