@@ -263,6 +263,46 @@ WN_API int wn_multiband3d_projected_grad_points(const wn_tile *tile3d, const flo
                                                 int one_normal, size_t n, float s, int first_band, int nbands,
                                                 const float *w_host, float var_per_band, float *out4_dev, void *stream);
 
+/* ---- analytic gradients of perlin::noise, turb and fractal_noise (absent from the reference) -------------------------
+ * noise (perlin.h:42-62) is the trilinear blend, weights u, v, w = fade(xf), fade(yf), fade(zf), of the eight corner dot
+ * products a_c = G_c . (p - c), c = cx + 2 cy + 4 cz in the value's order (AA, BA, AB, BB, AA+1, ...); grad() picks
+ * G_c in {-1, 0, 1}^3 from hash & 15.  With fade'(t) = 30 t^2 (t-1)^2 (evaluated as s = t*(t-1), 30*(s*s)) and the value's
+ * own intermediates x00, x10, x01, x11, y0 = lerp(v, x00, x10), y1 = lerp(v, x01, x11):
+ *     d/dx = T_x + fade'(xf) * lerp(w, lerp(v, a1-a0, a3-a2), lerp(v, a5-a4, a7-a6))
+ *     d/dy = T_y + fade'(yf) * lerp(w, x10-x00, x11-x01)
+ *     d/dz = T_z + fade'(zf) * (y1 - y0)
+ * T_k is the trilinear blend of the eight G_c[k].  Operation order (fp64, unfused, lerp(t,a,b) = a + t*(b-a)): the corner
+ * components are blended over z first, then y -- P0_k = lerp(v, lerp(w, G0, G4), lerp(w, G2, G6)) for the corners at
+ * cx = 0 and P1_k likewise from G1, G5, G3, G7 -- and over x last, T_k = lerp(u, P0_k, P1_k); then the product with fade'
+ * and one addition.  (P0_k, P1_k do not change along a run of x samples inside a cell: the dense-grid kernel forms them
+ * once per cell and row.)  The gradient is continuous across cell faces; at a lattice point the value is 0 and the
+ * gradient is that corner's G_c.
+ * turb: value |sum_i 2^-i noise(2^i p)| on the float point (an exact doubling per octave); the chain-rule factor
+ * 2^-i * 2^i is exactly 1, so the gradient is sigma * sum_i grad noise(2^i p), the octaves added in order, sigma = -1 where
+ * the value's own accumulated sum is negative and +1 otherwise.  turb is not differentiable where that sum is 0; the entry
+ * points return sigma = +1 there.  depth == 0 gives 0 in all four channels.
+ * fractal_noise (perlin.h:75-90): amplitude 2^-i times frequency 2^i is exactly 1: the gradient is
+ * (sum_i grad noise(p * 2^i)) / max_value with the value's max_value.
+ *
+ * Points: `n` records {value, d/dx, d/dy, d/dz} of four doubles (32 bytes, written as two 16-byte stores); out4_dev must
+ * be 16-byte aligned (else WN_ERR_INVALID).  The value channel has the bits of wn_perlin_points / _points_vec3 /
+ * _turb_points / _fractal_points, and every channel those of the host evaluators (wnhost_perlin_grad, ...).
+ * Grids: four consecutive float volumes -- value, d/dx, d/dy, d/dz -- each in wn_perlin_grid's layout.  The gradient is
+ * taken with respect to the sample's noise-space coordinate, not per lattice index; every channel is
+ * (float)channel * out_scale; under WN_Z_CONST d/dz is taken at z_const.  Channel 0 has the bits of wn_perlin_grid /
+ * _turb_grid / _fractal_grid and every channel those of (float) of the point entry point at the lattice's float
+ * coordinates, times out_scale: a sample's bits do not depend on how the volume is cut into z-slabs.
+ * Argument checks as the value entry points: NULL pointers and depth < 0 are refused, a perm is used on its own device,
+ * n == 0 or an empty lattice is WN_OK. */
+WN_API int wn_perlin_grad_points(const wn_perm *perm, const double *xyz_dev, size_t n, double *out4_dev, void *stream);
+WN_API int wn_perlin_grad_points_vec3(const wn_perm *perm, const float *xyz_dev, size_t n, double *out4_dev, void *stream);
+WN_API int wn_perlin_turb_grad_points(const wn_perm *perm, const float *xyz_dev, size_t n, int depth, double *out4_dev,
+                                      void *stream);
+WN_API int wn_perlin_fractal_grad_points(const wn_perm *perm, const float *xyz_dev, size_t n, double *out4_dev, void *stream);
+WN_API int wn_perlin_grad_grid(const wn_perm *perm, const wn_grid *g, float *out_dev, void *stream);
+WN_API int wn_perlin_turb_grad_grid(const wn_perm *perm, const wn_grid *g, int depth, float *out_dev, void *stream);
+WN_API int wn_perlin_fractal_grad_grid(const wn_perm *perm, const wn_grid *g, float *out_dev, void *stream);
+
 /* ---- texture adaptor (texture.h), batched over ray hit points -------------------------------- */
 /* `active_dev` (may be NULL = all active): one byte per point, 0 = this hit is not on a
  * noise-textured surface.  Inactive points are skipped (their output is left untouched); the

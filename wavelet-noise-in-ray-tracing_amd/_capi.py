@@ -91,6 +91,13 @@ SIGNATURES = {
     "wn_eval3d_projected_grad_points": (_i, [_vp, _vp, _vp, _sz, _vp, _vp]),
     "wn_eval3d_projected_grad_grid": (_i, [_vp, _gp, C.POINTER(C.c_float), _vp, _vp]),
     "wn_multiband3d_projected_grad_points": (_i, [_vp, _vp, _vp, _i, _sz, _f, _i, _i, C.POINTER(C.c_float), _f, _vp, _vp]),
+    "wn_perlin_grad_points": (_i, [_vp, _vp, _sz, _vp, _vp]),
+    "wn_perlin_grad_points_vec3": (_i, [_vp, _vp, _sz, _vp, _vp]),
+    "wn_perlin_turb_grad_points": (_i, [_vp, _vp, _sz, _i, _vp, _vp]),
+    "wn_perlin_fractal_grad_points": (_i, [_vp, _vp, _sz, _vp, _vp]),
+    "wn_perlin_grad_grid": (_i, [_vp, _gp, _vp, _vp]),
+    "wn_perlin_turb_grad_grid": (_i, [_vp, _gp, _i, _vp, _vp]),
+    "wn_perlin_fractal_grad_grid": (_i, [_vp, _gp, _vp, _vp]),
     "wn_wavelet_texture_points": (_i, [_vp, _i, _d, _i, _vp, _vp, _sz, _vp, _vp]),
     "wn_noise_texture_points": (_i, [_vp, _d, _i, _vp, _vp, _sz, _vp, _vp]),
     "wn_scalar_eval3d": (_i, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),

@@ -393,6 +393,140 @@ WN_EVAL_FN double perlin_fractal(const Table perm, float x, float y, float z)
     return result / max_value;
 }
 
+// ---- analytic gradient of Perlin noise, turb and fractal_noise (absent from the reference) -----------------------------
+// noise(p) = trilinear blend, weights fade(xf), fade(yf), fade(zf), of the eight corner dot products a_c = G_c . (p - c),
+// c = cx + 2 cy + 4 cz in the value's order (AA, BA, AB, BB, AA+1, ...).  With u, v, w the fades and x00 .. x11, y0, y1 the
+// value's own intermediates:
+//     d/dx = T_x + fade'(xf) * lerp(w, lerp(v, a1 - a0, a3 - a2), lerp(v, a5 - a4, a7 - a6))
+//     d/dy = T_y + fade'(yf) * lerp(w, x10 - x00, x11 - x01)
+//     d/dz = T_z + fade'(zf) * (y1 - y0)
+// T_k is the trilinear blend of the eight G_c[k].  The order of the gradient channels is this library's to define (the
+// reference has none): the corner components are blended over z, then y -- P0_k, P1_k of perlin_corner_blend, constant
+// along a run of x samples inside one cell, so the dense-grid run kernel forms them once per cell and row -- and over x
+// last, T_k = plerp(u, P0_k, P1_k).  Every product and sum unfused, as everywhere in this file.
+WN_EVAL_FN double pfade_d(double t) // fade'(t) = 30 t^2 (t - 1)^2
+{
+    const double s = t * (t - 1.0);
+    return 30.0 * (s * s);
+}
+
+// grad()'s corner vector G (perlin.h:26-31): pgrad(hash, x, y, z) = G . (x, y, z), components in {-1, 0, 1}.
+// u = h < 8 ? x : y carries the sign of bit 0, v = h < 4 ? y : (h == 12 || h == 14 ? x : z) that of bit 1.
+constexpr int pgrad_component(int h, int k)
+{
+    const int uk = h < 8 ? 0 : 1, vk = h < 4 ? 1 : ((h == 12 || h == 14) ? 0 : 2);
+    return (uk == k ? ((h & 1) ? -1 : 1) : 0) + (vk == k ? ((h & 2) ? -1 : 1) : 0);
+}
+// component + 1 of the 16 hashes, two bits each: one shift and mask instead of a tree of selects
+constexpr uint32_t pgrad_lut(int k)
+{
+    uint32_t lut = 0;
+    for (int h = 0; h < 16; ++h) lut |= (uint32_t)(pgrad_component(h, k) + 1) << (2 * h);
+    return lut;
+}
+WN_EVAL_FN double pgrad_decode(uint32_t lut, int hash) { return (double)((int)((lut >> (2 * (hash & 15))) & 3u) - 1); }
+
+// The corner vectors of one cell blended over z, then y: P0 for the corners at cx = 0, P1 for cx = 1.
+WN_EVAL_FN void perlin_corner_blend(const int h[8], double v, double w, double P0[3], double P1[3])
+{
+    constexpr uint32_t lut[3] = {pgrad_lut(0), pgrad_lut(1), pgrad_lut(2)};
+    WN_UNROLL
+    for (int k = 0; k < 3; ++k) {
+        double G[8];
+        WN_UNROLL
+        for (int c = 0; c < 8; ++c) G[c] = pgrad_decode(lut[k], h[c]);
+        P0[k] = plerp(v, plerp(w, G[0], G[4]), plerp(w, G[2], G[6]));
+        P1[k] = plerp(v, plerp(w, G[1], G[5]), plerp(w, G[3], G[7]));
+    }
+}
+
+// One sample from its eight corner dot products: returns the value in perlin_exact's operations (the same bits), writes
+// the gradient to g.  du, dv, dw = fade'(xf), fade'(yf), fade'(zf).
+WN_EVAL_FN double perlin_sample_grad(const double a[8], double u, double v, double w, double du, double dv, double dw,
+                                     const double P0[3], const double P1[3], double g[3])
+{
+    const double x00 = plerp(u, a[0], a[1]), x10 = plerp(u, a[2], a[3]);
+    const double x01 = plerp(u, a[4], a[5]), x11 = plerp(u, a[6], a[7]);
+    const double y0 = plerp(v, x00, x10), y1 = plerp(v, x01, x11);
+    const double dx = plerp(w, plerp(v, a[1] - a[0], a[3] - a[2]), plerp(v, a[5] - a[4], a[7] - a[6]));
+    const double dy = plerp(w, x10 - x00, x11 - x01);
+    g[0] = plerp(u, P0[0], P1[0]) + du * dx;
+    g[1] = plerp(u, P0[1], P1[1]) + dv * dy;
+    g[2] = plerp(u, P0[2], P1[2]) + dw * (y1 - y0);
+    return plerp(w, y0, y1);
+}
+
+// perlin::noise and its gradient: returns the value (perlin_exact's bits), writes d/dx, d/dy, d/dz to g.
+template <typename Table>
+WN_EVAL_FN double perlin_grad_exact(const Table perm, double x, double y, double z, double g[3])
+{
+    const double fx = floor(x), fy = floor(y), fz = floor(z);
+    const int X = (int)fx & 255, Y = (int)fy & 255, Z = (int)fz & 255;
+    x -= fx;
+    y -= fy;
+    z -= fz;
+    const double u = pfade(x), v = pfade(y), w = pfade(z);
+    const int A = perm[X] + Y, AA = perm[A] + Z, AB = perm[A + 1] + Z;
+    const int B = perm[X + 1] + Y, BA = perm[B] + Z, BB = perm[B + 1] + Z;
+    const int h[8] = {(int)perm[AA],     (int)perm[BA],     (int)perm[AB],     (int)perm[BB],
+                      (int)perm[AA + 1], (int)perm[BA + 1], (int)perm[AB + 1], (int)perm[BB + 1]};
+    const double a[8] = {pgrad(h[0], x, y, z),         pgrad(h[1], x - 1, y, z),
+                         pgrad(h[2], x, y - 1, z),     pgrad(h[3], x - 1, y - 1, z),
+                         pgrad(h[4], x, y, z - 1),     pgrad(h[5], x - 1, y, z - 1),
+                         pgrad(h[6], x, y - 1, z - 1), pgrad(h[7], x - 1, y - 1, z - 1)};
+    double P0[3], P1[3];
+    perlin_corner_blend(h, v, w, P0, P1);
+    return perlin_sample_grad(a, u, v, w, pfade_d(x), pfade_d(y), pfade_d(z), P0, P1, g);
+}
+
+// turb and its gradient with respect to the float point.  Octave i evaluates noise at 2^i p (an exact doubling) with weight
+// 2^-i: the chain-rule factor 2^-i * 2^i is exactly 1, so the gradient is the plain sum of the octaves' noise gradients, in
+// octave order, times sigma = -1 where the value's own accumulated sum is negative and +1 otherwise.  Not differentiable
+// where that sum is 0 (the kink of |.|): sigma = +1 there.  depth == 0: 0 in all four channels.
+template <typename Table>
+WN_EVAL_FN double perlin_turb_grad(const Table perm, float x, float y, float z, int depth, double g[3])
+{
+    double accum = 0.0, weight = 1.0, gx = 0.0, gy = 0.0, gz = 0.0;
+    for (int i = 0; i < depth; ++i) {
+        double gn[3];
+        accum += weight * perlin_grad_exact(perm, (double)x, (double)y, (double)z, gn);
+        gx += gn[0];
+        gy += gn[1];
+        gz += gn[2];
+        weight *= 0.5;
+        x *= 2.0f;
+        y *= 2.0f;
+        z *= 2.0f;
+    }
+    const bool negative = accum < 0.0;
+    g[0] = negative ? -gx : gx;
+    g[1] = negative ? -gy : gy;
+    g[2] = negative ? -gz : gz;
+    return fabs(accum);
+}
+
+// fractal_noise and its gradient: amplitude 2^-i times frequency 2^i is exactly 1, so the gradient is the plain sum of the
+// six octaves' noise gradients divided by the value's max_value.
+template <typename Table>
+WN_EVAL_FN double perlin_fractal_grad(const Table perm, float x, float y, float z, double g[3])
+{
+    double result = 0.0, amplitude = 1.0, frequency = 1.0, max_value = 0.0, gx = 0.0, gy = 0.0, gz = 0.0;
+    for (int i = 0; i < 6; ++i) {
+        double gn[3];
+        result += perlin_grad_exact(perm, x * frequency, y * frequency, z * frequency, gn) * amplitude;
+        gx += gn[0];
+        gy += gn[1];
+        gz += gn[2];
+        max_value += amplitude;
+        amplitude *= 0.5;
+        frequency *= 2.0;
+    }
+    g[0] = gx / max_value;
+    g[1] = gy / max_value;
+    g[2] = gz / max_value;
+    return result / max_value;
+}
+
 // ---- the texture adaptors' per-point arithmetic (texture.h:37-43, 67-107) ----------------------------------------------
 // wavelet_texture's coordinate scaling, texture.h:71-80: (float)(p * scale) * (octave_scale * 2.0f)
 template <typename A>

@@ -3,6 +3,7 @@
 #ifndef PERLINNOISE_HPP
 #define PERLINNOISE_HPP
 
+#include <cstddef>
 #include <random>
 #include <vector>
 
@@ -32,6 +33,19 @@ class PerlinNoise {
         return v;
     }
     double noise(double x, double y) const { return noise(x, y, 0.0); } // PerlinNoise.hpp:58-60
+
+    // additive: noise and its analytic gradient (absent from the reference; include/wnoise.h).  The scalar member is
+    // evaluated on the host and returns the value, d/dx, d/dy, d/dz to grad; the batched overload writes n records
+    // {value, d/dx, d/dy, d/dz} of four doubles through the GPU.  Bit-identical to each other.
+    double noise_gradient(double x, double y, double z, double grad[3]) const { return wnhost_perlin_grad(p.data(), x, y, z, grad); }
+    void noise_gradient(const double *xyz, size_t n, double *out4) const
+    {
+        if (!n) return;
+        wnhost::DeviceBuffer in(3 * n * sizeof(double)), res(4 * n * sizeof(double));
+        in.upload(xyz);
+        wnhost::check(wn_perlin_grad_points(perm_, in.as<double>(), n, res.as<double>(), nullptr), "wn_perlin_grad_points");
+        res.download(out4);
+    }
 
     const std::vector<int> &table() const { return p; }
     const wn_perm *perm() const { return perm_; }

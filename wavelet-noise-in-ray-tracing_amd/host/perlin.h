@@ -73,8 +73,49 @@ class perlin {
         wnhost::check(wn_perlin_points(perm_, in.as<double>(), n, res.as<double>(), nullptr), "wn_perlin_points");
         res.download(out);
     }
+
+    // ---- additive: analytic gradients (absent from the reference; include/wnoise.h) --------------
+    // Scalar members: return the value (the bits of noise / turb / fractal_noise) and write d/dx, d/dy, d/dz to grad;
+    // evaluated on the host from the mirrored table (scalar_eval.h), bit-identical to the kernels.
+    double noise_gradient(double x, double y, double z, double grad[3]) const { return wnhost_perlin_grad(p.data(), x, y, z, grad); }
+    double noise_gradient(const point3 &q, double grad[3]) const { return noise_gradient(q.x(), q.y(), q.z(), grad); }
+    double turb_gradient(const point3 &q, double grad[3], int depth = 7) const
+    {
+        const float xyz[3] = {q.x(), q.y(), q.z()};
+        return wnhost_perlin_turb_grad(p.data(), xyz, depth, grad);
+    }
+    double fractal_noise_gradient(const point3 &q, double grad[3]) const
+    {
+        const float xyz[3] = {q.x(), q.y(), q.z()};
+        return wnhost_perlin_fractal_grad(p.data(), xyz, grad);
+    }
+    // Batched overloads (host pointers, through the GPU): n records {value, d/dx, d/dy, d/dz} of four doubles to out4.
+    void noise_gradient(const double *xyz, size_t n, double *out4) const
+    {
+        if (!n) return;
+        wnhost::DeviceBuffer in(3 * n * sizeof(double)), res(4 * n * sizeof(double));
+        in.upload(xyz);
+        wnhost::check(wn_perlin_grad_points(perm_, in.as<double>(), n, res.as<double>(), nullptr), "wn_perlin_grad_points");
+        res.download(out4);
+    }
+    void noise_gradient(const float *xyz, size_t n, double *out4) const { grad_vec3(xyz, n, 0, 0, out4); }
+    void turb_gradient(const float *xyz, size_t n, double *out4, int depth = 7) const { grad_vec3(xyz, n, 1, depth, out4); }
+    void fractal_noise_gradient(const float *xyz, size_t n, double *out4) const { grad_vec3(xyz, n, 2, 0, out4); }
+
     const std::vector<int> &table() const { return p; }
     const wn_perm *perm() const { return perm_; }
+
+  private:
+    void grad_vec3(const float *xyz, size_t n, int kind, int depth, double *out4) const // kind 0: noise, 1: turb, 2: fractal_noise
+    {
+        if (!n) return;
+        wnhost::DeviceBuffer in(3 * n * sizeof(float)), res(4 * n * sizeof(double));
+        in.upload(xyz);
+        if (kind == 0) wnhost::check(wn_perlin_grad_points_vec3(perm_, in.as<float>(), n, res.as<double>(), nullptr), "wn_perlin_grad_points_vec3");
+        else if (kind == 1) wnhost::check(wn_perlin_turb_grad_points(perm_, in.as<float>(), n, depth, res.as<double>(), nullptr), "wn_perlin_turb_grad_points");
+        else wnhost::check(wn_perlin_fractal_grad_points(perm_, in.as<float>(), n, res.as<double>(), nullptr), "wn_perlin_fractal_grad_points");
+        res.download(out4);
+    }
 };
 
 #endif

@@ -70,6 +70,21 @@ double wnhost_perlin_turb(const int *perm, const float q[3], int depth)
     return wn::perlin_turb(perm, q[0], q[1], q[2], depth);
 }
 
+double wnhost_perlin_grad(const int *perm, double x, double y, double z, double grad[3])
+{
+    return wn::perlin_grad_exact(perm, x, y, z, grad);
+}
+
+double wnhost_perlin_fractal_grad(const int *perm, const float q[3], double grad[3])
+{
+    return wn::perlin_fractal_grad(perm, q[0], q[1], q[2], grad);
+}
+
+double wnhost_perlin_turb_grad(const int *perm, const float q[3], int depth, double grad[3])
+{
+    return wn::perlin_turb_grad(perm, q[0], q[1], q[2], depth, grad);
+}
+
 float wnhost_wavelet_texture_value(const float *coef, int n, int use_3d, double scale, int octave, const float xyz[3])
 {
     const float octave_scale = (float)std::pow(2.0, (double)octave); // std::pow(2.0f, int) is evaluated in double, :77

@@ -48,6 +48,14 @@ WNHOST_API float wnhost_eval3d_projected_grad(const float *coef, int n, const fl
 WNHOST_API double wnhost_perlin(const int *perm, double x, double y, double z);      // perlin.h:42-62
 WNHOST_API double wnhost_perlin_fractal(const int *perm, const float q[3]);           // perlin.h:75-90
 WNHOST_API double wnhost_perlin_turb(const int *perm, const float q[3], int depth);   // RTOW turb (absent from the reference)
+// noise / fractal_noise / turb and their gradients (absent from the reference): each returns the value (the bits of the
+// function above) and writes d/dx, d/dy, d/dz to grad -- corner vectors blended over z, then y, then x, plus fade' times the
+// value's own differences (include/wnoise.h): the bits of wn_perlin_grad_points / _fractal_grad_points / _turb_grad_points.
+// turb: the sign of the accumulated sum multiplies the gradient (+1 where the sum is 0: not differentiable there);
+// depth == 0 -> 0 in all four.
+WNHOST_API double wnhost_perlin_grad(const int *perm, double x, double y, double z, double grad[3]);
+WNHOST_API double wnhost_perlin_fractal_grad(const int *perm, const float q[3], double grad[3]);
+WNHOST_API double wnhost_perlin_turb_grad(const int *perm, const float q[3], int depth, double grad[3]);
 // grey level of texture::value (texture.h); use_3d = 0: the 2-D tile and branch; coef == NULL: the no-tile grey
 WNHOST_API float wnhost_wavelet_texture_value(const float *coef, int n, int use_3d, double scale, int octave,
                                               const float xyz[3]);                    // texture.h:67-107

@@ -341,6 +341,30 @@ class perlin:
         out = self._run(_lib.wn_perlin_turb_points, _dev(p, torch.float32).reshape(-1, 3), int(depth))
         return float(out.item()) if single else out
 
+    # -- analytic gradients (absent from the reference): (N, 4) float64 CUDA tensors of {value, d/dx, d/dy, d/dz}
+    def _grad(self, fn, pts, *mid):
+        out = torch.empty((pts.shape[0], 4), dtype=torch.float64, device="cuda")
+        check(fn(self._h, _ptr(pts), pts.shape[0], *mid, _ptr(out), _stream()))
+        return out
+
+    def noise_gradient(self, p):
+        """noise and its gradient at one point or an (N, 3) batch: float64 input follows noise(double, double, double)
+        (wn_perlin_grad_points), anything else noise(const point3&) on floats (wn_perlin_grad_points_vec3).  The value
+        column has the bits of noise()."""
+        is64 = (p.dtype == torch.float64) if isinstance(p, torch.Tensor) else (np.asarray(p).dtype == np.float64)
+        if is64:
+            return self._grad(_lib.wn_perlin_grad_points, _dev(p, torch.float64).reshape(-1, 3))
+        return self._grad(_lib.wn_perlin_grad_points_vec3, _dev(p, torch.float32).reshape(-1, 3))
+
+    def turb_gradient(self, p, depth=7):
+        """turb(p, depth) and its gradient (wn_perlin_turb_grad_points): the sign of the octave sum times the sum of the
+        octaves' noise gradients; not differentiable where the sum is 0."""
+        return self._grad(_lib.wn_perlin_turb_grad_points, _dev(p, torch.float32).reshape(-1, 3), int(depth))
+
+    def fractal_noise_gradient(self, p):
+        """fractal_noise(p) and its gradient (wn_perlin_fractal_grad_points)."""
+        return self._grad(_lib.wn_perlin_fractal_grad_points, _dev(p, torch.float32).reshape(-1, 3))
+
 
 PerlinNoise = perlin  # experient/PerlinNoise.hpp is the same algorithm with an explicit seed
 
@@ -629,3 +653,23 @@ def turb_volume(perlin_obj, den, nx, ny, z0, z1, depth=7, out=None):
     gc = g.c()
     check(_lib.wn_perlin_turb_grid(perlin_obj._h, C.byref(gc), int(depth), _ptr(out), _stream()))
     return out[: g.nz * ny * nx].view(g.nz, ny, nx)
+
+
+def perlin_gradient_volume(perlin_obj, den, nx, ny, z0, z1, octave, out=None):
+    """perlin_volume's lattice with the gradient (wn_perlin_grad_grid): [4, nz, ny, nx] -- value, d/dx, d/dy, d/dz with
+    respect to the coordinate passed to noise()."""
+    g = GridSpec(den, nx, ny, z0, z1, octave_scale=_octave_scale(octave))
+    out = _grad_out(g, out)
+    gc = g.c()
+    check(_lib.wn_perlin_grad_grid(perlin_obj._h, C.byref(gc), _ptr(out), _stream()))
+    return out[: 4 * g.nz * ny * nx].view(4, g.nz, ny, nx)
+
+
+def turb_gradient_volume(perlin_obj, den, nx, ny, z0, z1, depth=7, out=None):
+    """turb_volume's lattice with the gradient with respect to p = (i/den)*4 (wn_perlin_turb_grad_grid):
+    [4, nz, ny, nx]."""
+    g = GridSpec(den, nx, ny, z0, z1)
+    out = _grad_out(g, out)
+    gc = g.c()
+    check(_lib.wn_perlin_turb_grad_grid(perlin_obj._h, C.byref(gc), int(depth), _ptr(out), _stream()))
+    return out[: 4 * g.nz * ny * nx].view(4, g.nz, ny, nx)
