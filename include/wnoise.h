@@ -303,6 +303,49 @@ WN_API int wn_perlin_grad_grid(const wn_perm *perm, const wn_grid *g, float *out
 WN_API int wn_perlin_turb_grad_grid(const wn_perm *perm, const wn_grid *g, int depth, float *out_dev, void *stream);
 WN_API int wn_perlin_fractal_grad_grid(const wn_perm *perm, const wn_grid *g, float *out_dev, void *stream);
 
+/* ---- divergence-free curl noise from 3-D wavelet noise potentials (absent from the reference) -------------------------
+ * The vector potential is Psi = (psi0, psi1, psi2); psi_k is evaluate3D of the same tile shifted by a whole-cell offset
+ * o_k = (ox, oy, oz)_k:
+ *     psi_k(p) = sum_{fz,fy,fx} w * C[Mod(mid_x+fx+ox_k), Mod(mid_y+fy+oy_k), Mod(mid_z+fz+oz_k)]
+ * The offset acts on the tile index, not on the coordinate: psi_k(p) is exactly evaluate3D(p) of the tile
+ * T_k[z][y][x] = C[Mod(z+oz_k)][Mod(y+oy_k)][Mod(x+ox_k)] (numpy: np.roll(c3, shift=(-oz, -oy, -ox), axis=(0, 1, 2))).
+ * `offsets9_host`: nine int32 on the host, the (x, y, z) triples of psi0, psi1, psi2; any integers (negative ones and
+ * ones >= n included), reduced with the reference's Mod; equal offsets are allowed.  The velocity is the curl
+ *     v = (d psi2/dy - d psi1/dz,  d psi0/dz - d psi2/dx,  d psi1/dx - d psi0/dy)
+ * The tensor-product quadratic B-spline is C1 and its mixed second partials commute: div v = 0 analytically, and v is
+ * continuous across cell faces.
+ * Arithmetic: the per-axis weights and derivatives are formed once (the three potentials share mids, weights and
+ * derivatives).  Each of the six partial derivatives is the sum wn_eval3d_grad_points forms for that channel -- the same
+ * tap weights, z outer and x inner, unfused -- over the coefficients at the offset indices; each component of v is then
+ * one float subtraction: it has the bits of the subtraction of two channels of wn_eval3d_grad_points run on the rolled
+ * tiles.  Multiband (normal == NULL branch; bands, out_div and division as wn_multiband3d_grad_points): per potential
+ * each of its two derivative sums accumulates (w[b] * (2 * 2^(first_band+b))) * its band's sum over the active bands and
+ * is divided by out_div when the weights are not all zero; then the subtraction -- the bits of composing
+ * wn_multiband3d_grad_points on the rolled tiles.  The offsets are the same in every band.  An empty tile gives 0 in all
+ * three channels; when no band is active the result is 0.
+ *
+ * Points: `n` packed records {vx, vy, vz} of three floats (no alignment beyond a float's); every component has the bits
+ * of the host's scalar evaluator (evaluate3DCurl, wnhost_eval3d_curl).
+ * Grids: three consecutive volumes -- vx, vy, vz -- each in wn_eval3d_grid's layout (a z-sharded caller gathers each
+ * channel with wn_gather_volume).  Derivatives are taken with respect to the sample's noise-space coordinate (the value
+ * passed to evaluate3D; multiband: the lattice coordinate p); out_scale multiplies all three channels last; under
+ * WN_Z_CONST the z-derivatives are taken at z_const.  WN_GRID_EXACT: bit-identical to the point entry points at the
+ * lattice's float coordinates.  Default: a separable brick kernel in the gradient brick kernel's regime, every channel
+ * within 2e-5 * |out_scale| (multiband: * sum_b |w_b| 2^(first_band+b+1) / out_div) of the exact tier (a component is
+ * the difference of two gradient channels); a sample's bits do not depend on how the volume is cut into z-slabs.
+ * Argument checks as the gradient entry points; a NULL offsets9_host is WN_ERR_INVALID; n == 0 or an empty lattice is
+ * WN_OK. */
+WN_API int wn_eval3d_curl_points(const wn_tile *tile3d, const float *xyz_dev, size_t n, const int32_t *offsets9_host,
+                                 float *out3_dev, void *stream);
+WN_API int wn_multiband3d_curl_points(const wn_tile *tile3d, const float *xyz_dev, size_t n, const int32_t *offsets9_host,
+                                      float s, int first_band, int nbands, const float *w_host, float var_per_band,
+                                      float *out3_dev, void *stream);
+WN_API int wn_eval3d_curl_grid(const wn_tile *tile3d, const wn_grid *g, const int32_t *offsets9_host, float *out_dev,
+                               void *stream);
+WN_API int wn_multiband3d_curl_grid(const wn_tile *tile3d, const wn_grid *g, const int32_t *offsets9_host, float s,
+                                    int first_band, int nbands, const float *w_host, float var_per_band, float *out_dev,
+                                    void *stream);
+
 /* ---- texture adaptor (texture.h), batched over ray hit points -------------------------------- */
 /* `active_dev` (may be NULL = all active): one byte per point, 0 = this hit is not on a
  * noise-textured surface.  Inactive points are skipped (their output is left untouched); the

@@ -23,7 +23,7 @@ from .noise import (  # noqa: E402
     generate3DProjectedOctaveBandNoise, generatePerlinNoise2D, generatePerlinNoise3DSliced,
     wavelet_volume, wavelet_volume_launcher, multiband_volume, perlin_volume, turb_volume, device_info, HipTimer,
     wavelet_gradient_volume, multiband_gradient_volume, wavelet2d_gradient_image, projected_gradient_volume,
-    perlin_gradient_volume, turb_gradient_volume,
+    perlin_gradient_volume, turb_gradient_volume, curl_volume, multiband_curl_volume,
 )
 from .shard import slab_bounds, gather_volume, NativeComm  # noqa: E402
 from . import formats  # noqa: E402
@@ -35,5 +35,6 @@ __all__ = [
     "generate3DProjectedOctaveBandNoise", "generatePerlinNoise2D", "generatePerlinNoise3DSliced",
     "wavelet_volume", "wavelet_volume_launcher", "multiband_volume", "perlin_volume", "turb_volume", "device_info",
     "HipTimer", "wavelet_gradient_volume", "multiband_gradient_volume", "wavelet2d_gradient_image",
-    "projected_gradient_volume", "perlin_gradient_volume", "turb_gradient_volume", "slab_bounds", "gather_volume", "NativeComm", "formats",
+    "projected_gradient_volume", "perlin_gradient_volume", "turb_gradient_volume", "curl_volume",
+    "multiband_curl_volume", "slab_bounds", "gather_volume", "NativeComm", "formats",
 ]

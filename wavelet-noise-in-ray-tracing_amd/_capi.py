@@ -31,6 +31,7 @@ class wn_grid(C.Structure):
 _vp, _sz, _i, _u32, _f, _d = C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.c_float, C.c_double
 _pp = C.POINTER(C.c_void_p)
 _gp = C.POINTER(wn_grid)
+_i32p = C.POINTER(C.c_int32)
 SIGNATURES = {
     "wn_last_error": (C.c_char_p, []),
     "wn_version": (C.c_char_p, []),
@@ -98,6 +99,10 @@ SIGNATURES = {
     "wn_perlin_grad_grid": (_i, [_vp, _gp, _vp, _vp]),
     "wn_perlin_turb_grad_grid": (_i, [_vp, _gp, _i, _vp, _vp]),
     "wn_perlin_fractal_grad_grid": (_i, [_vp, _gp, _vp, _vp]),
+    "wn_eval3d_curl_points": (_i, [_vp, _vp, _sz, _i32p, _vp, _vp]),
+    "wn_multiband3d_curl_points": (_i, [_vp, _vp, _sz, _i32p, _f, _i, _i, C.POINTER(C.c_float), _f, _vp, _vp]),
+    "wn_eval3d_curl_grid": (_i, [_vp, _gp, _i32p, _vp, _vp]),
+    "wn_multiband3d_curl_grid": (_i, [_vp, _gp, _i32p, _f, _i, _i, C.POINTER(C.c_float), _f, _vp, _vp]),
     "wn_wavelet_texture_points": (_i, [_vp, _i, _d, _i, _vp, _vp, _sz, _vp, _vp]),
     "wn_noise_texture_points": (_i, [_vp, _d, _i, _vp, _vp, _sz, _vp, _vp]),
     "wn_scalar_eval3d": (_i, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),

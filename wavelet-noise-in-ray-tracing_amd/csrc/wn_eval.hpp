@@ -333,6 +333,124 @@ WN_EVAL_FN float multiband_exact(const A &a, const float p[3], const float *nrm,
     return v;
 }
 
+// ---- curl of a vector potential of three whole-cell shifts of one tile (absent from the reference) ---------------------
+// Psi = (psi0, psi1, psi2), psi_k = evaluate3D of the tile T_k[z][y][x] = C[Mod(z+oz_k)][Mod(y+oy_k)][Mod(x+ox_k)];
+// v = curl Psi = (d psi2/dy - d psi1/dz, d psi0/dz - d psi2/dx, d psi1/dx - d psi0/dy).  The shifts are whole cells, so the
+// three potentials share mids, weights and derivatives (bspline_grad once per axis) and differ in the coefficients read.
+// `off`: the nine offsets (x, y, z of psi0, psi1, psi2), each already reduced to [0, n) with dmod.
+
+// The two derivative sums that the curl needs of potential K (psi0: d/dy, d/dz; psi1: d/dx, d/dz; psi2: d/dx, d/dy): the
+// sums of eval3d_exact_impl<.., GRAD> for those channels -- the same tap weights, f2 -> f1 -> f0, unfused -- over the
+// coefficients at the offset indices: the bits of that evaluator on T_K.
+template <bool PADDED, bool POW2, int K>
+WN_EVAL_FN void curl_potential_sums(const float *coef, int n, int nmask, const int *off, int mx, int my, int mz,
+                                    const float *wx, const float *wy, const float *wz, const float *dx, const float *dy,
+                                    const float *dz, float &s0, float &s1)
+{
+    const int stride = PADDED ? n + 2 : n;
+    int cx[3], cy[3], cz[3];
+    WN_UNROLL
+    for (int f = 0; f < 3; ++f) {
+        cx[f] = POW2 ? ((mx + f - 1 + off[3 * K]) & nmask) : dmod(mx + f - 1 + off[3 * K], n, -1);
+        cy[f] = (POW2 ? ((my + f - 1 + off[3 * K + 1]) & nmask) : dmod(my + f - 1 + off[3 * K + 1], n, -1)) * stride;
+        cz[f] = (POW2 ? ((mz + f - 1 + off[3 * K + 2]) & nmask) : dmod(mz + f - 1 + off[3 * K + 2], n, -1)) * stride * n;
+    }
+    float a0 = 0.0f, a1 = 0.0f;
+    WN_UNROLL
+    for (int fz = 0; fz < 3; ++fz)
+        WN_UNROLL
+        for (int fy = 0; fy < 3; ++fy) {
+            float c[3];
+            if (PADDED) {
+                __builtin_memcpy(c, coef + cx[0] + cy[fy] + cz[fz], sizeof(c)); // the x taps stay adjacent under an x offset
+            } else {
+                WN_UNROLL
+                for (int fx = 0; fx < 3; ++fx) c[fx] = coef[cx[fx] + cy[fy] + cz[fz]];
+            }
+            WN_UNROLL
+            for (int fx = 0; fx < 3; ++fx) {
+                if constexpr (K == 0) {
+                    a0 += wx[fx] * dy[fy] * wz[fz] * c[fx];
+                    a1 += wx[fx] * wy[fy] * dz[fz] * c[fx];
+                } else if constexpr (K == 1) {
+                    a0 += dx[fx] * wy[fy] * wz[fz] * c[fx];
+                    a1 += wx[fx] * wy[fy] * dz[fz] * c[fx];
+                } else {
+                    a0 += dx[fx] * wy[fy] * wz[fz] * c[fx];
+                    a1 += wx[fx] * dy[fy] * wz[fz] * c[fx];
+                }
+            }
+        }
+    s0 = a0;
+    s1 = a1;
+}
+
+// The six sums at one point: s = {d psi0/dy, d psi0/dz, d psi1/dx, d psi1/dz, d psi2/dx, d psi2/dy}; an empty tile: 0.
+template <bool PADDED = false>
+WN_EVAL_FN void eval3d_curl_sums(const float *coef, int n, int nmask, const int *off, float px, float py, float pz, float s[6])
+{
+    if (n == 0) {
+        WN_UNROLL
+        for (int i = 0; i < 6; ++i) s[i] = 0.0f;
+        return;
+    }
+    int mx, my, mz;
+    float wx[3], wy[3], wz[3], dx[3], dy[3], dz[3];
+    bspline_grad(px, mx, wx, dx);
+    bspline_grad(py, my, wy, dy);
+    bspline_grad(pz, mz, wz, dz);
+    if (nmask >= 0) {
+        curl_potential_sums<PADDED, true, 0>(coef, n, nmask, off, mx, my, mz, wx, wy, wz, dx, dy, dz, s[0], s[1]);
+        curl_potential_sums<PADDED, true, 1>(coef, n, nmask, off, mx, my, mz, wx, wy, wz, dx, dy, dz, s[2], s[3]);
+        curl_potential_sums<PADDED, true, 2>(coef, n, nmask, off, mx, my, mz, wx, wy, wz, dx, dy, dz, s[4], s[5]);
+    } else {
+        curl_potential_sums<PADDED, false, 0>(coef, n, nmask, off, mx, my, mz, wx, wy, wz, dx, dy, dz, s[0], s[1]);
+        curl_potential_sums<PADDED, false, 1>(coef, n, nmask, off, mx, my, mz, wx, wy, wz, dx, dy, dz, s[2], s[3]);
+        curl_potential_sums<PADDED, false, 2>(coef, n, nmask, off, mx, my, mz, wx, wy, wz, dx, dy, dz, s[4], s[5]);
+    }
+}
+
+// Each component of the curl is one float subtraction of two of the six sums.
+WN_EVAL_FN void curl_of_sums(const float s[6], float v[3])
+{
+    v[0] = s[5] - s[3];
+    v[1] = s[1] - s[4];
+    v[2] = s[2] - s[0];
+}
+
+// curl at one point: every component has the bits of the subtraction of two channels of eval3d_grad_exact on the shifted
+// tiles.
+template <bool PADDED = false>
+WN_EVAL_FN void eval3d_curl_exact(const float *coef, int n, int nmask, const int *off, float px, float py, float pz, float v[3])
+{
+    float s[6];
+    eval3d_curl_sums<PADDED>(coef, n, nmask, off, px, py, pz, s);
+    curl_of_sums(s, v);
+}
+
+// curl of the potentials psi_k = WMultibandNoise (normal == NULL branch) of T_k, with respect to p: each of the six sums
+// accumulates (w[b] * (2 * 2^(first_band+b))) * its band's sum over the active bands and is divided by out_div when
+// apply_div, as multiband_exact<.., GRAD> does for its gradient channels; then the subtractions.  The offsets are the same
+// in every band.  `a` carries coef, n, nmask, off and the bands of wn::multiband_bands.  No active band: 0.
+template <bool PADDED, typename A>
+WN_EVAL_FN void multiband_curl_exact(const A &a, const float p[3], float v[3])
+{
+    float acc[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    for (int b = 0; b < a.nbands; ++b) {
+        const float s = a.band_scale[b];
+        float sb[6];
+        eval3d_curl_sums<PADDED>(a.coef, a.n, a.nmask, a.off, 2.0f * p[0] * s, 2.0f * p[1] * s, 2.0f * p[2] * s, sb);
+        const float f = a.band_w[b] * (2.0f * s);
+        WN_UNROLL
+        for (int i = 0; i < 6; ++i) acc[i] += f * sb[i];
+    }
+    if (a.apply_div) {
+        WN_UNROLL
+        for (int i = 0; i < 6; ++i) acc[i] /= a.out_div;
+    }
+    curl_of_sums(acc, v);
+}
+
 // ---- Perlin improved noise, fp64 (perlin.h:18-31, 42-62) ------------------------------------------
 WN_EVAL_FN double pfade(double t) { return t * t * t * (t * (t * 6 - 15) + 10); }
 WN_EVAL_FN double plerp(double t, double a, double b) { return a + t * (b - a); }

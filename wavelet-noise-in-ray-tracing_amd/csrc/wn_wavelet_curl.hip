@@ -1,0 +1,457 @@
+// wn_wavelet_curl.hip -- divergence-free curl noise from 3-D wavelet noise potentials, on point lists and dense grids.
+//
+// The vector potential Psi = (psi0, psi1, psi2) is evaluate3D (or WMultibandNoise, normal == NULL) of three whole-cell
+// shifts of ONE tile: psi_k reads C[Mod(z+oz_k)][Mod(y+oy_k)][Mod(x+ox_k)].  The velocity is
+//     v = curl Psi = (d psi2/dy - d psi1/dz, d psi0/dz - d psi2/dx, d psi1/dx - d psi0/dy).
+// The tensor-product quadratic B-spline is C1 and its mixed second partials commute: div v = 0, v continuous across cell
+// faces.  Whole-cell shifts leave a sample's mids, weights and derivatives alone: bspline_grad runs once per axis for the
+// three potentials; six derivative sums, three output channels.
+//
+//   curl3d_points_kernel<PADDED, MB>   one point per lane, wn::eval3d_curl_exact / multiband_curl_exact (every component has
+//                                      the bits of the subtraction of two channels of wn_eval3d_grad_points /
+//                                      wn_multiband3d_grad_points on the shifted tiles), records {vx, vy, vz}.
+//   curl3d_grid_direct_kernel<PADDED>  WN_GRID_EXACT and every lattice the brick kernel declines: one sample per lane, the
+//                                      point kernel's device function at lattice_coord's coordinates; three volumes.
+//   curl3d_grid_sep_kernel<NB>         the default tier: per band three coefficient boxes (one per potential) staged in LDS,
+//                                      contracted one axis at a time, float4 rows.
+//
+// Grids write three consecutive volumes of nx * ny * nz samples (vx, vy, vz), each in wn_eval3d_grid's layout.  Derivatives
+// are taken with respect to the coordinate the sample passes to evaluate3D (multiband: the lattice coordinate p), and
+// out_scale multiplies all three channels last.
+#include "wn_internal.hpp"
+
+#include <algorithm>
+#include <cmath>
+
+namespace {
+
+using wn::GridArgs;
+using wn::kMaxBands;
+
+typedef float v4f __attribute__((ext_vector_type(4)));
+
+// What wn::eval3d_curl_exact / multiband_curl_exact read.
+struct CurlEval {
+    const float *coef;
+    int n, nmask;
+    int off[9]; // (x, y, z) of psi0, psi1, psi2, each in [0, n)
+    int mb;     // 0: evaluate3D potentials; 1: WMultibandNoise potentials (nbands may be 0: no band is active)
+    int nbands;
+    float band_scale[kMaxBands], band_w[kMaxBands];
+    float out_div;
+    int apply_div;
+};
+
+// ---- point lists -----------------------------------------------------------------------------------------------------
+struct CurlPointsArgs {
+    CurlEval e;
+    const float *pts; // xyz interleaved
+    float *out;       // {vx, vy, vz} per point
+    size_t count;
+};
+
+template <bool PADDED, bool MB>
+__global__ __launch_bounds__(256) void curl3d_points_kernel(const CurlPointsArgs a)
+{
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.count; i += (size_t)gridDim.x * blockDim.x) {
+        const float p[3] = {a.pts[3 * i], a.pts[3 * i + 1], a.pts[3 * i + 2]};
+        float v[3];
+        if (MB) wn::multiband_curl_exact<PADDED>(a.e, p, v);
+        else wn::eval3d_curl_exact<PADDED>(a.e.coef, a.e.n, a.e.nmask, a.e.off, p[0], p[1], p[2], v);
+        a.out[3 * i] = v[0];
+        a.out[3 * i + 1] = v[1];
+        a.out[3 * i + 2] = v[2];
+    }
+}
+
+// ---- dense grids, exact tier ---------------------------------------------------------------------------------------------
+struct CurlDirectArgs {
+    CurlEval e;
+    float *out;
+    size_t vol; // samples per channel volume
+    GridArgs g;
+};
+
+template <bool PADDED>
+__global__ __launch_bounds__(256) void curl3d_grid_direct_kernel(const CurlDirectArgs a)
+{
+    const GridArgs &g = a.g;
+    const float den = (float)g.den;
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < a.vol; e += (size_t)gridDim.x * blockDim.x) {
+        const int x = (int)(e % g.nx);
+        const size_t r = e / g.nx;
+        const int y = (int)(r % g.ny), z = (int)(r / g.ny);
+        const float p[3] = {wn::lattice_coord(x, den, g.base_range, g.octave_scale, g.post_scale),
+                            wn::lattice_coord(y, den, g.base_range, g.octave_scale, g.post_scale),
+                            g.z_const_mode ? g.z_const
+                                           : wn::lattice_coord(g.z0 + z, den, g.base_range, g.octave_scale, g.post_scale)};
+        float v[3];
+        if (a.e.mb) wn::multiband_curl_exact<PADDED>(a.e, p, v);
+        else wn::eval3d_curl_exact<PADDED>(a.e.coef, a.e.n, a.e.nmask, a.e.off, p[0], p[1], p[2], v);
+        a.out[e] = v[0] * g.out_scale;
+        a.out[e + a.vol] = v[1] * g.out_scale;
+        a.out[e + 2 * a.vol] = v[2] * g.out_scale;
+    }
+}
+
+// ---- dense grids, default tier: the separable brick kernel ---------------------------------------------------------------
+// The gradient brick kernel's brick (256 x 8 x 8 samples per 4-wave workgroup; a lane owns 4 consecutive x samples, a wave
+// rows (y, z)) and regime.  Per band the workgroup stages THREE boxes, box_k[k][j][i] = coef[Mod(kz0+k+oz_k)]
+// [Mod(jy0+j+oy_k)][Mod(ix0+i+ox_k)], of one geometry (the potentials share the mids), and the lane forms the 4-wide x
+// window (Wx, Dx) once.  Per row, band and potential the lane contracts the 4 box columns under its samples' taps
+//     z:  Z = sum_k wz_k C[k][j][i],  Z' = sum_k dz_k C[k][j][i]
+//     y:  A = sum_j wy_j Z,  B = sum_j dy_j Z,  D = sum_j wy_j Z'
+// and needs only two of the three column contractions per potential:
+//     psi0: B, D      psi1: A, D      psi2: A, B  (no Z' at all)
+//     vx = sum_i Wx_i (B2 - D1),  vy = sum_i (Wx_i D0 - Dx_i A2),  vz = sum_i (Dx_i A1 - Wx_i B0)
+// the components accumulated with signs.  Every sample is summed in the same order from its own weights and coefficients,
+// wherever it sits in a brick: its bits do not depend on how the volume was cut into z-slabs.  Fused (FMA) arithmetic.
+constexpr int kGX = 256, kGY = 8, kGZ = 8; // samples per brick
+constexpr int kGWaves = 4;
+// LDS: one band's three boxes are at most 3 x 3.2 K floats inside two_mids, eight bands' less than twice that (each lower
+// band's step halves): < 77 KB.  Up to 48 KB the launch needs nothing; beyond, the kernel is opted in to the request
+// (wn::ensure_dynamic_lds; the CU has 160 KB, so two workgroups still share one).  The cap never binds inside two_mids.
+constexpr int kCMaxBoxFloats = 36 * 1024; // 144 KB
+constexpr size_t kLdsNoOptIn = 48 * 1024;
+
+struct CurlBand {
+    float qmul;  // the band's coordinate is q = p * qmul (1; multiband 2 * 2^(first_band+b): exact)
+    float fg;    // factor of its derivatives: out_scale, or w_b / out_div * out_scale * qmul
+    int box_off; // float offset of its first box in dynamic LDS; potential k's box at box_off + k * box_cap
+    int box_cap; // floats reserved for each of its boxes
+};
+
+struct CurlSepArgs {
+    const float *coef; // linear tile
+    float *out;
+    size_t vol;
+    int n, nmask;
+    int off[9];
+    GridArgs g;
+    int vec4_ok;
+    CurlBand band[kMaxBands];
+};
+
+template <int NB>
+__global__ __launch_bounds__(64 * kGWaves) void curl3d_grid_sep_kernel(const CurlSepArgs a)
+{
+    extern __shared__ float box[];
+    __shared__ int s_geo[NB][6]; // per band: ix0, jy0, kz0, ex, ey, ez
+    const GridArgs &g = a.g;
+    const float den = (float)g.den;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int x_first = blockIdx.x * kGX, y_first = blockIdx.y * kGY, z_first = blockIdx.z * kGZ;
+    auto coord = [&](int i) { return wn::lattice_coord(i, den, g.base_range, g.octave_scale, g.post_scale); };
+    auto zcoord = [&](int zi) { return g.z_const_mode ? g.z_const : coord(g.z0 + zi); };
+
+    // ---- the boxes' geometry (shared by the three potentials): the mids of an axis's first and last sample bound all of
+    // them; one column / row / plane of support on either side, and one more column (the window's fourth, at zero weight)
+    if (tid < 3 * NB) {
+        const int b = tid / 3, ax = tid - 3 * b;
+        const int lo_i = ax == 0 ? x_first : (ax == 1 ? y_first : z_first);
+        const int n_i = ax == 0 ? g.nx : (ax == 1 ? g.ny : g.nz);
+        const int hi_i = min(lo_i + (ax == 0 ? kGX : (ax == 1 ? kGY : kGZ)), n_i) - 1;
+        const float qm = a.band[b].qmul;
+        const float c_lo = (ax == 2 ? zcoord(lo_i) : coord(lo_i)) * qm, c_hi = (ax == 2 ? zcoord(hi_i) : coord(hi_i)) * qm;
+        int m_lo, m_hi;
+        float w0, w1, w2;
+        wn::bspline(c_lo, m_lo, w0, w1, w2);
+        wn::bspline(c_hi, m_hi, w0, w1, w2);
+        s_geo[b][ax] = min(m_lo, m_hi) - 1;
+        s_geo[b][3 + ax] = abs(m_hi - m_lo) + (ax == 0 ? 4 : 3);
+    }
+    __syncthreads();
+
+    // ---- fill: a wave takes whole (k, j) rows of a potential's box
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        const int ix0 = s_geo[b][0], jy0 = s_geo[b][1], kz0 = s_geo[b][2];
+        const int ex = s_geo[b][3], ey = s_geo[b][4], ez = s_geo[b][5];
+        if ((long long)ex * ey * ez > a.band[b].box_cap) return; // never: the host bounds the box (memory safety); uniform
+#pragma unroll 1
+        for (int k3 = 0; k3 < 3; ++k3) {
+            float *bb = box + a.band[b].box_off + k3 * a.band[b].box_cap;
+            const int ox = a.off[3 * k3], oy = a.off[3 * k3 + 1], oz = a.off[3 * k3 + 2];
+            for (int r = wave; r < ey * ez; r += kGWaves) {
+                const int k = r / ey, j = r - k * ey;
+                const float *row =
+                    a.coef + ((size_t)wn::dmod(kz0 + k + oz, a.n, a.nmask) * a.n + wn::dmod(jy0 + j + oy, a.n, a.nmask)) * a.n;
+                for (int i = lane; i < ex; i += 64) bb[r * ex + i] = row[wn::dmod(ix0 + i + ox, a.n, a.nmask)];
+            }
+        }
+    }
+
+    // ---- x: this lane's 4 samples (coordinates once: the bands scale them) in a 4-column window per band
+    const int x0 = x_first + lane * 4;
+    float px[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) px[q] = coord(min(x0 + q, g.nx - 1));
+    struct XWin { int col; float w[4][4], d[4][4]; }; // window's first box column; per sample q the window's weights
+    auto x_window = [&](int b, XWin &xw) {
+        int m[4];
+        float w[4][3], d[4][3];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) wn::bspline_grad(px[q] * a.band[b].qmul, m[q], w[q], d[q]);
+        xw.col = m[0] - 1 - s_geo[b][0];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const bool sh = m[q] != m[0]; // then m[q] == m[0] + 1 (the host's two_mids)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                xw.w[q][c] = sh ? (c == 0 ? 0.0f : w[q][c - 1]) : (c == 3 ? 0.0f : w[q][c]);
+                xw.d[q][c] = sh ? (c == 0 ? 0.0f : d[q][c - 1]) : (c == 3 ? 0.0f : d[q][c]);
+            }
+        }
+    };
+    XWin xw1;
+    if (NB == 1) x_window(0, xw1);
+    __syncthreads();
+
+    const int rows_y = min(kGY, g.ny - y_first), rows_z = min(kGZ, g.nz - z_first);
+    for (int r = wave; r < rows_y * rows_z; r += kGWaves) {
+        const int yi = r % rows_y, zi = r / rows_y;
+        const float py = coord(y_first + yi), pz = zcoord(z_first + zi);
+        float acc[3][4] = {}; // [component][sample]
+        // bands one after the other (not unrolled: each band's x window is live only inside its iteration)
+#pragma unroll 1
+        for (int b = 0; b < NB; ++b) {
+            XWin xwb;
+            if (NB != 1) x_window(b, xwb);
+            const XWin &xw = NB == 1 ? xw1 : xwb;
+            const float qm = a.band[b].qmul;
+            int my, mz;
+            float wy[3], dy[3], wz[3], dz[3];
+            wn::bspline_grad(py * qm, my, wy, dy);
+            wn::bspline_grad(pz * qm, mz, wz, dz);
+            const int ex = s_geo[b][3], ey = s_geo[b][4];
+            const int cap = a.band[b].box_cap;
+            const float *base = box + a.band[b].box_off + ((mz - 1 - s_geo[b][2]) * ey + (my - 1 - s_geo[b][1])) * ex + xw.col;
+            // per window column: P = B2 - D1 (for vx), D0 and A2 (vy), A1 and B0 (vz)
+            float P[4], D0[4], A2[4], A1[4], B0[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                float zw[3][3], zd[2][3]; // [potential][fy]: Z for all three, Z' for psi0 and psi1
+#pragma unroll
+                for (int k3 = 0; k3 < 3; ++k3)
+#pragma unroll
+                    for (int fy = 0; fy < 3; ++fy) {
+                        const float *bk = base + k3 * cap;
+                        const float c0 = bk[(0 * ey + fy) * ex + c], c1 = bk[(1 * ey + fy) * ex + c], c2 = bk[(2 * ey + fy) * ex + c];
+                        zw[k3][fy] = __builtin_fmaf(wz[2], c2, __builtin_fmaf(wz[1], c1, wz[0] * c0));
+                        if (k3 < 2) zd[k3][fy] = __builtin_fmaf(dz[2], c2, __builtin_fmaf(dz[1], c1, dz[0] * c0));
+                    }
+                B0[c] = __builtin_fmaf(dy[2], zw[0][2], __builtin_fmaf(dy[1], zw[0][1], dy[0] * zw[0][0]));
+                D0[c] = __builtin_fmaf(wy[2], zd[0][2], __builtin_fmaf(wy[1], zd[0][1], wy[0] * zd[0][0]));
+                A1[c] = __builtin_fmaf(wy[2], zw[1][2], __builtin_fmaf(wy[1], zw[1][1], wy[0] * zw[1][0]));
+                const float D1 = __builtin_fmaf(wy[2], zd[1][2], __builtin_fmaf(wy[1], zd[1][1], wy[0] * zd[1][0]));
+                A2[c] = __builtin_fmaf(wy[2], zw[2][2], __builtin_fmaf(wy[1], zw[2][1], wy[0] * zw[2][0]));
+                const float B2 = __builtin_fmaf(dy[2], zw[2][2], __builtin_fmaf(dy[1], zw[2][1], dy[0] * zw[2][0]));
+                P[c] = B2 - D1;
+                // one column's 27 LDS reads in flight, not all 108: 127 VGPRs (4 waves per SIMD) instead of 170 (2); measured
+                // 597 against 742 us at 512^3 (profiles/curl_kernels.txt)
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            const float fg = a.band[b].fg;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                float vx = 0.0f, vy = 0.0f, vz = 0.0f;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    vx = __builtin_fmaf(xw.w[q][c], P[c], vx);
+                    vy = __builtin_fmaf(xw.w[q][c], D0[c], vy);
+                    vy = __builtin_fmaf(-xw.d[q][c], A2[c], vy);
+                    vz = __builtin_fmaf(xw.d[q][c], A1[c], vz);
+                    vz = __builtin_fmaf(-xw.w[q][c], B0[c], vz);
+                }
+                acc[0][q] = __builtin_fmaf(fg, vx, acc[0][q]);
+                acc[1][q] = __builtin_fmaf(fg, vy, acc[1][q]);
+                acc[2][q] = __builtin_fmaf(fg, vz, acc[2][q]);
+            }
+        }
+        float *dst = a.out + ((size_t)(z_first + zi) * g.ny + (y_first + yi)) * g.nx + x0;
+        if (a.vec4_ok && x0 + 3 < g.nx) {
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch)
+                *reinterpret_cast<v4f *>(dst + ch * a.vol) = v4f{acc[ch][0], acc[ch][1], acc[ch][2], acc[ch][3]};
+        } else {
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch)
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    if (x0 + q < g.nx) dst[ch * a.vol + q] = acc[ch][q];
+        }
+    }
+}
+
+constexpr size_t kBlockCap = 256u * 8u * 8u; // workgroups of a grid-stride launch (wn::stride_blocks)
+constexpr size_t kPointBlockCap = 256u * 8u;  // of the point kernel's: its lanes hold 27 row loads each
+
+template <int NB>
+int launch_curl_sep(const CurlSepArgs &a, dim3 grid, size_t lds, hipStream_t stream)
+{
+    if (lds > kLdsNoOptIn &&
+        !wn::ensure_dynamic_lds(reinterpret_cast<const void *>(&curl3d_grid_sep_kernel<NB>), wn::current_device(), lds))
+        return wn::kDeclined; // the runtime refused the LDS: the exact kernel serves the lattice
+    hipLaunchKernelGGL(curl3d_grid_sep_kernel<NB>, grid, dim3(64 * kGWaves), lds, stream, a);
+    WN_LAUNCH_CHECK("curl3d_grid_sep_kernel");
+    return WN_OK;
+}
+
+// Launches the brick kernel when the lattice is in its regime -- the gradient brick kernel's: a tile that is not empty
+// (any size: the boxes are filled modulo n), steps >= 0 at which 4 consecutive samples span at most two mids in every band
+// (wn::LatticeStep::two_mids: step < 1/3 cell) -- and the runtime grants the boxes' LDS (see kCMaxBoxFloats).  nbands bands
+// (1..kMaxBands) with coordinate multipliers qmul[b] and the factors fg[b] of their derivatives.
+int curl_sep_try(const wn_tile *tile, const GridArgs &g, const int off[9], int nbands, const float *qmul, const float *fg,
+                 float *out_dev, hipStream_t stream)
+{
+    if (tile->n == 0 || nbands < 1 || nbands > kMaxBands || g.nx <= 0 || g.ny <= 0 || g.nz <= 0) return wn::kDeclined;
+    CurlSepArgs a{};
+    long long box_total = 0;
+    for (int b = 0; b < nbands; ++b) {
+        wn::LatticeStep ls;
+        if (!wn::lattice_step(g, g.octave_scale * qmul[b], true, false, 0.0, &ls) || !ls.two_mids()) return wn::kDeclined;
+        const long long ex = ls.extent(kGX) + 1, ey = ls.extent(kGY), ez = g.z_const_mode ? 3 : ls.extent(kGZ);
+        a.band[b].qmul = qmul[b];
+        a.band[b].fg = fg[b];
+        a.band[b].box_off = (int)box_total;
+        a.band[b].box_cap = (int)(ex * ey * ez);
+        box_total += 3 * ex * ey * ez;
+        if (box_total > kCMaxBoxFloats) return wn::kDeclined;
+    }
+    const int nbx = (g.nx + kGX - 1) / kGX, nby = (g.ny + kGY - 1) / kGY, nbz = (g.nz + kGZ - 1) / kGZ;
+    if (nby > 65535 || nbz > 65535) return wn::kDeclined;
+    a.coef = tile->dev;
+    a.out = out_dev;
+    a.vol = (size_t)g.nx * g.ny * g.nz;
+    a.n = tile->n;
+    a.nmask = wn::pow2_mask(tile->n);
+    std::copy(off, off + 9, a.off);
+    a.g = g;
+    a.vec4_ok = wn::vec4_ok(out_dev, g.nx);
+    const size_t lds = (size_t)box_total * sizeof(float);
+    const dim3 grid(nbx, nby, nbz);
+    switch (nbands) {
+    case 1: return launch_curl_sep<1>(a, grid, lds, stream);
+    case 2: return launch_curl_sep<2>(a, grid, lds, stream);
+    case 3: return launch_curl_sep<3>(a, grid, lds, stream);
+    case 4: return launch_curl_sep<4>(a, grid, lds, stream);
+    case 5: return launch_curl_sep<5>(a, grid, lds, stream);
+    case 6: return launch_curl_sep<6>(a, grid, lds, stream);
+    case 7: return launch_curl_sep<7>(a, grid, lds, stream);
+    default: return launch_curl_sep<8>(a, grid, lds, stream);
+    }
+}
+
+// The tile's fields of CurlEval (its padded copy when it has one) and the offsets reduced with the reference's Mod.
+int curl_eval_args(const wn_tile *tile, const int32_t *offsets9_host, const char *entry, CurlEval *e)
+{
+    const int rc = wn::check_tile(tile, 3, entry);
+    if (rc) return rc;
+    if (!offsets9_host) return wn::fail(WN_ERR_INVALID, "%s: offsets9_host is NULL", entry);
+    *e = CurlEval{};
+    e->coef = tile->dev_padded ? tile->dev_padded : tile->dev;
+    e->n = tile->n;
+    e->nmask = wn::pow2_mask(tile->n);
+    for (int i = 0; i < 9; ++i) e->off[i] = tile->n > 0 ? wn::dmod(offsets9_host[i], tile->n, e->nmask) : 0;
+    return WN_OK;
+}
+
+int launch_curl_points(const wn_tile *tile, const CurlEval &e, const float *xyz_dev, size_t n, float *out3_dev,
+                       hipStream_t stream)
+{
+    if (!xyz_dev || !out3_dev) return wn::fail(WN_ERR_INVALID, "points/out pointer is NULL");
+    CurlPointsArgs a{e, xyz_dev, out3_dev, n};
+    const dim3 grid(wn::stride_blocks(n, kPointBlockCap)), block(256);
+    const bool padded = tile->dev_padded != nullptr;
+    if (e.mb) {
+        if (padded) hipLaunchKernelGGL((curl3d_points_kernel<true, true>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((curl3d_points_kernel<false, true>), grid, block, 0, stream, a);
+    } else {
+        if (padded) hipLaunchKernelGGL((curl3d_points_kernel<true, false>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((curl3d_points_kernel<false, false>), grid, block, 0, stream, a);
+    }
+    WN_LAUNCH_CHECK("curl3d_points_kernel");
+    return WN_OK;
+}
+
+// The grid entry points after their argument checks: the brick kernel (bands given by qmul / fg, nbands >= 1) unless the
+// caller asks for WN_GRID_EXACT or it declines, then the exact kernel.
+int curl_grid(const wn_tile *tile, const wn_grid *grid, const CurlEval &e, float *out_dev, hipStream_t stream)
+{
+    GridArgs g;
+    int rc = wn::check_grid(grid, true, &g);
+    if (rc) return rc;
+    const size_t total = (size_t)g.nx * g.ny * g.nz;
+    if (total == 0) return WN_OK;
+    if (!out_dev) return wn::fail(WN_ERR_INVALID, "out_dev is NULL");
+    if (!(grid->flags & WN_GRID_EXACT) && (!e.mb || e.nbands >= 1)) {
+        // band b: q = p * (2 * 2^(first_band+b)); derivative factor w_b / out_div * out_scale * 2 * 2^(first_band+b)
+        float qmul[kMaxBands] = {1.0f}, fg[kMaxBands] = {g.out_scale};
+        for (int b = 0; e.mb && b < e.nbands; ++b) {
+            qmul[b] = 2.0f * e.band_scale[b];
+            fg[b] = (float)((double)e.band_w[b] / (double)e.out_div * (double)g.out_scale * (double)qmul[b]);
+        }
+        if ((rc = curl_sep_try(tile, g, e.off, e.mb ? e.nbands : 1, qmul, fg, out_dev, stream)) != wn::kDeclined) return rc;
+    }
+    CurlDirectArgs d{e, out_dev, total, g};
+    const dim3 blocks(wn::stride_blocks(total, kBlockCap)), block(256);
+    if (tile->dev_padded) hipLaunchKernelGGL(curl3d_grid_direct_kernel<true>, blocks, block, 0, stream, d);
+    else hipLaunchKernelGGL(curl3d_grid_direct_kernel<false>, blocks, block, 0, stream, d);
+    WN_LAUNCH_CHECK("curl3d_grid_direct_kernel");
+    return WN_OK;
+}
+
+} // namespace
+
+using namespace wn;
+
+extern "C" {
+
+int wn_eval3d_curl_points(const wn_tile *tile, const float *xyz_dev, size_t n, const int32_t *offsets9_host, float *out3_dev,
+                          void *stream)
+{
+    WN_ENTRY();
+    CurlEval e;
+    const int rc = curl_eval_args(tile, offsets9_host, "wn_eval3d_curl_points", &e);
+    if (rc || n == 0) return rc;
+    return launch_curl_points(tile, e, xyz_dev, n, out3_dev, as_stream(stream));
+}
+
+int wn_multiband3d_curl_points(const wn_tile *tile, const float *xyz_dev, size_t n, const int32_t *offsets9_host, float s,
+                               int first_band, int nbands, const float *w_host, float var_per_band, float *out3_dev,
+                               void *stream)
+{
+    WN_ENTRY();
+    CurlEval e;
+    int rc = curl_eval_args(tile, offsets9_host, "wn_multiband3d_curl_points", &e);
+    if (rc) return rc;
+    rc = multiband_bands(s, first_band, nbands, w_host, var_per_band, &e);
+    if (rc || n == 0) return rc;
+    e.mb = 1;
+    return launch_curl_points(tile, e, xyz_dev, n, out3_dev, as_stream(stream));
+}
+
+int wn_eval3d_curl_grid(const wn_tile *tile, const wn_grid *grid, const int32_t *offsets9_host, float *out_dev, void *stream)
+{
+    WN_ENTRY();
+    CurlEval e;
+    const int rc = curl_eval_args(tile, offsets9_host, "wn_eval3d_curl_grid", &e);
+    if (rc) return rc;
+    return curl_grid(tile, grid, e, out_dev, as_stream(stream));
+}
+
+int wn_multiband3d_curl_grid(const wn_tile *tile, const wn_grid *grid, const int32_t *offsets9_host, float s, int first_band,
+                             int nbands, const float *w_host, float var_per_band, float *out_dev, void *stream)
+{
+    WN_ENTRY();
+    CurlEval e;
+    int rc = curl_eval_args(tile, offsets9_host, "wn_multiband3d_curl_grid", &e);
+    if (rc) return rc;
+    rc = multiband_bands(s, first_band, nbands, w_host, var_per_band, &e);
+    if (rc) return rc;
+    e.mb = 1;
+    return curl_grid(tile, grid, e, out_dev, as_stream(stream));
+}
+
+} // extern "C"

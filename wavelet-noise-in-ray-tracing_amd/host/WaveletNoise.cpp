@@ -219,6 +219,61 @@ void WaveletNoise::WMultibandNoiseGradient(const float *xyz, const float *normal
     res.download(out4);
 }
 
+// ---- curl noise: the scalar member on the host (bit-identical to the point kernel), the multiband one a batch of one on
+// the device; a 2-D tile goes to the C ABI, which reports it
+void WaveletNoise::defaultCurlOffsets(int offsets9[9]) const
+{
+    for (int k = 0; k < 3; ++k) offsets9[3 * k] = offsets9[3 * k + 1] = offsets9[3 * k + 2] = k * tileSizeN / 3;
+}
+
+void WaveletNoise::evaluate3DCurl(const float p[3], const int *offsets9, float v[3]) const
+{
+    if (tileDims == 2) return evaluate3DCurl(p, 1, offsets9, v);
+    int def[9];
+    if (!offsets9) defaultCurlOffsets(def);
+    wnhost_eval3d_curl(noiseCoefficients.empty() ? nullptr : noiseCoefficients.data(), tileSizeN, p,
+                       offsets9 ? offsets9 : def, v);
+}
+
+void WaveletNoise::evaluate3DCurl(const float *xyz, size_t n, const int *offsets9, float *out3) const
+{
+    if (!n) return;
+    int def[9];
+    if (!offsets9) defaultCurlOffsets(def);
+    wnhost::DeviceBuffer in(3 * n * sizeof(float)), res(3 * n * sizeof(float));
+    in.upload(xyz);
+    check(wn_eval3d_curl_points(tile(3), in.as<float>(), n, offsets9 ? offsets9 : def, res.as<float>(), nullptr),
+          "wn_eval3d_curl_points");
+    res.download(out3);
+}
+
+void WaveletNoise::WMultibandNoiseCurl(const float p[3], const int *offsets9, float sarg, int firstBand, int nbands,
+                                       const float *w, float v[3], float variance) const
+{
+    int def[9];
+    if (!offsets9) defaultCurlOffsets(def);
+    auto &s = wnhost::Scratch::get();
+    std::copy(p, p + 3, s.in_host());
+    check(wn_multiband3d_curl_points(tile(3), static_cast<const float *>(s.in_dev()), 1, offsets9 ? offsets9 : def, sarg,
+                                     firstBand, nbands, w, variance, static_cast<float *>(s.out_dev()), nullptr),
+          "wn_multiband3d_curl_points");
+    check(wn_stream_sync(nullptr), "wn_stream_sync");
+    std::copy(s.out_host(), s.out_host() + 3, v);
+}
+
+void WaveletNoise::WMultibandNoiseCurl(const float *xyz, size_t n, const int *offsets9, float sarg, int firstBand,
+                                       int nbands, const float *w, float variance, float *out3) const
+{
+    if (!n) return;
+    int def[9];
+    if (!offsets9) defaultCurlOffsets(def);
+    wnhost::DeviceBuffer in(3 * n * sizeof(float)), res(3 * n * sizeof(float));
+    in.upload(xyz);
+    check(wn_multiband3d_curl_points(tile(3), in.as<float>(), n, offsets9 ? offsets9 : def, sarg, firstBand, nbands, w,
+                                     variance, res.as<float>(), nullptr), "wn_multiband3d_curl_points");
+    res.download(out3);
+}
+
 // ---- batched members ----------------------------------------------------------------------------------
 void WaveletNoise::evaluate2D(const float *xy, size_t n, float *out) const
 {

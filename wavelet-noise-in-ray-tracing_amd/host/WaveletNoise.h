@@ -90,6 +90,19 @@ class WaveletNoise {
                                   float grad[3], float variance = 0.296f) const;
     void WMultibandNoiseGradient(const float *xyz, const float *normals, bool oneNormal, size_t n, float s, int firstBand,
                                  int nbands, const float *w, float variance, float *out4) const;
+    // Divergence-free curl noise (absent from the reference; include/wnoise.h): the curl of the vector potential whose
+    // components are evaluate3D (WMultibandNoiseCurl: WMultibandNoise, normal == NULL) of this tile shifted by the whole-cell
+    // offsets offsets9 = (x, y, z) of psi0, psi1, psi2; nullptr: defaultCurlOffsets().  evaluate3DCurl(p, ., v) is
+    // evaluated on the host (scalar_eval.h), bit-identical to wn_eval3d_curl_points; the scalar WMultibandNoiseCurl is a
+    // batch of one on the device.  The batched forms write n records {vx, vy, vz} to out3.
+    void evaluate3DCurl(const float p[3], const int *offsets9, float v[3]) const;
+    void evaluate3DCurl(const float *xyz, size_t n, const int *offsets9, float *out3) const;
+    void WMultibandNoiseCurl(const float p[3], const int *offsets9, float s, int firstBand, int nbands, const float *w,
+                             float v[3], float variance = 0.18402f) const;
+    void WMultibandNoiseCurl(const float *xyz, size_t n, const int *offsets9, float s, int firstBand, int nbands,
+                             const float *w, float variance, float *out3) const;
+    // (0,0,0), (n/3,)*3, (2n/3,)*3 with integer division: a default only, not a measured decorrelation.
+    void defaultCurlOffsets(int offsets9[9]) const;
     // The device-resident tile (an empty tile before generate*); for the C-ABI grid entry points.
     const wn_tile *tile(int dims) const;
 

@@ -48,6 +48,16 @@ float wnhost_eval3d_grad(const float *coef, int n, const float p[3], float grad[
     return wn::eval3d_grad_exact(coef, n, wn::pow2_mask(n), p[0], p[1], p[2], grad);
 }
 
+void wnhost_eval3d_curl(const float *coef, int n, const float p[3], const int offsets9[9], float v[3])
+{
+    v[0] = v[1] = v[2] = 0.0f;
+    if (!coef || n <= 0) return;
+    const int nmask = wn::pow2_mask(n);
+    int off[9];
+    for (int i = 0; i < 9; ++i) off[i] = wn::dmod(offsets9[i], n, nmask);
+    wn::eval3d_curl_exact(coef, n, nmask, off, p[0], p[1], p[2], v);
+}
+
 float wnhost_eval3d_projected(const float *coef, int n, const float p[3], const float nrm[3])
 {
     if (!coef || n <= 0) return 0.0f;

@@ -38,6 +38,12 @@ WNHOST_API float wnhost_eval3d(const float *coef, int n, const float p[3]);     
 // d/dx, d/dy, d/dz to grad -- tap weights (d_x*w_y)*w_z, (w_x*d_y)*w_z, (w_x*w_y)*d_z in evaluate3D's order, unfused:
 // the bits of wn_eval3d_grad_points.  n == 0 or coef == NULL -> 0 in all four.
 WNHOST_API float wnhost_eval3d_grad(const float *coef, int n, const float p[3], float grad[3]);
+// The curl of the vector potential (psi0, psi1, psi2), psi_k = evaluate3D of the tile shifted by the whole-cell offset
+// offsets9[3k .. 3k+2] = (ox, oy, oz)_k (any integers; include/wnoise.h), absent from the reference: writes
+// v = (d psi2/dy - d psi1/dz, d psi0/dz - d psi2/dx, d psi1/dx - d psi0/dy) -- six of wnhost_eval3d_grad's derivative sums
+// over the offset coefficients and one subtraction per component: the bits of wn_eval3d_curl_points.
+// n == 0 or coef == NULL -> 0 in all three.
+WNHOST_API void wnhost_eval3d_curl(const float *coef, int n, const float p[3], const int offsets9[9], float v[3]);
 WNHOST_API float wnhost_eval3d_projected(const float *coef, int n, const float p[3], const float normal[3]); // WaveletNoise.cpp:218-265
 // evaluate3DProjected and its gradient with respect to p, the normal held fixed (absent from the reference): returns the
 // value (the bits of wnhost_eval3d_projected, its 1e-6 cut included), writes the gradient of the uncut sum over the same

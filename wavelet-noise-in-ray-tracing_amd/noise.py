@@ -247,6 +247,40 @@ class WaveletNoise:
                                               int(nbands), wa, float(variance), _ptr(out), _stream()))
         return out
 
+    # -- divergence-free curl noise (absent from the reference): (N, 3) CUDA tensors of {vx, vy, vz}
+    def _curl_offsets(self, offsets):
+        """Nine int32: the (x, y, z) whole-cell tile offsets of the potentials psi0, psi1, psi2.  None: (0, 0, 0),
+        (n//3,)*3, (2*n//3,)*3 of the tile size n -- a default only, not a measured decorrelation."""
+        if offsets is None:
+            n = self.tileSizeN
+            offsets = ((0, 0, 0), (n // 3,) * 3, (2 * n // 3,) * 3)
+        flat = [int(v) for v in np.asarray(offsets, dtype=np.int64).reshape(-1)]
+        if len(flat) != 9:
+            raise ValueError("offsets: three (x, y, z) triples")
+        return (C.c_int32 * 9)(*flat)
+
+    def evaluate3DCurl(self, p, offsets=None):
+        """The curl of the vector potential whose components are evaluate3D of this tile shifted by the whole-cell
+        `offsets` (wn_eval3d_curl_points), at one point or an (N, 3) batch: v = (d psi2/dy - d psi1/dz, d psi0/dz -
+        d psi2/dx, d psi1/dx - d psi0/dy), divergence-free.  Every component has the bits of the subtraction of two
+        evaluate3DGradient channels on from_coefficients(np.roll(c3, (-oz, -oy, -ox), (0, 1, 2))) tiles."""
+        pts = _dev(p, torch.float32).reshape(-1, 3)
+        out = torch.empty((pts.shape[0], 3), dtype=torch.float32, device="cuda")
+        check(_lib.wn_eval3d_curl_points(self._handle(3), _ptr(pts), pts.shape[0], self._curl_offsets(offsets), _ptr(out),
+                                         _stream()))
+        return out
+
+    def WMultibandNoiseCurl(self, p, s, firstBand, nbands, w, variance=None, offsets=None):
+        """evaluate3DCurl with WMultibandNoise (normal=None) potentials, derivatives with respect to p
+        (wn_multiband3d_curl_points); the offsets are the same in every band."""
+        pts = _dev(p, torch.float32).reshape(-1, 3)
+        out = torch.empty((pts.shape[0], 3), dtype=torch.float32, device="cuda")
+        wa = (C.c_float * max(1, nbands))(*[float(x) for x in list(w)[:nbands]])
+        check(_lib.wn_multiband3d_curl_points(self._handle(3), _ptr(pts), pts.shape[0], self._curl_offsets(offsets),
+                                              float(s), int(firstBand), int(nbands), wa,
+                                              float(0.18402 if variance is None else variance), _ptr(out), _stream()))
+        return out
+
     def evaluate2DGradient(self, p):
         """evaluate2D and its gradient at one point or an (N, 2) batch (wn_eval2d_grad_points): an (N, 3) CUDA tensor of
         {value, d/dx, d/dy}; the value column has the bits of evaluate2D."""
@@ -612,6 +646,40 @@ def multiband_gradient_volume(noise, den, nx, ny, z0, z1, s=-16.0, firstBand=0, 
     check(_lib.wn_multiband3d_grad_grid(noise._handle(3), C.byref(gc), float(s), int(firstBand),
                                         int(nbands), wa, float(variance), _ptr(out), _stream()))
     return out[: 4 * g.nz * ny * nx].view(4, g.nz, ny, nx)
+
+
+def _curl_out(g, out):
+    n = 3 * g.nz * g.ny * g.nx
+    if out is None:
+        return torch.empty(n, dtype=torch.float32, device="cuda")
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= n
+    return out
+
+
+def curl_volume(noise, den, nx, ny, z0, z1, octave, offsets=None, exact=False, out=None):
+    """wavelet_gradient_volume's lattice with the curl of the three shifted potentials (wn_eval3d_curl_grid; `offsets` as
+    WaveletNoise.evaluate3DCurl): [3, nz, ny, nx] -- vx, vy, vz, derivatives with respect to the coordinate passed to
+    evaluate3D, all three times 1/sqrt(0.18402)."""
+    g = GridSpec(den, nx, ny, z0, z1, octave_scale=_octave_scale(octave), post_scale=2.0,
+                 out_scale=_inv_stddev(0.18402), flags=WN_GRID_EXACT if exact else WN_GRID_DEFAULT)
+    out = _curl_out(g, out)
+    gc = g.c()
+    check(_lib.wn_eval3d_curl_grid(noise._handle(3), C.byref(gc), noise._curl_offsets(offsets), _ptr(out), _stream()))
+    return out[: 3 * g.nz * ny * nx].view(3, g.nz, ny, nx)
+
+
+def multiband_curl_volume(noise, den, nx, ny, z0, z1, s=-16.0, firstBand=0, nbands=5, w=None, variance=0.18402,
+                          offsets=None, exact=False, out=None):
+    """multiband_gradient_volume's lattice with the curl of three shifted WMultibandNoise potentials, derivatives with
+    respect to p = (i/den)*4 (wn_multiband3d_curl_grid): [3, nz, ny, nx]."""
+    w = [1.0] * nbands if w is None else list(w)
+    g = GridSpec(den, nx, ny, z0, z1, flags=WN_GRID_EXACT if exact else WN_GRID_DEFAULT)
+    out = _curl_out(g, out)
+    gc = g.c()
+    wa = (C.c_float * max(1, nbands))(*[float(x) for x in w[:nbands]])
+    check(_lib.wn_multiband3d_curl_grid(noise._handle(3), C.byref(gc), noise._curl_offsets(offsets), float(s),
+                                        int(firstBand), int(nbands), wa, float(variance), _ptr(out), _stream()))
+    return out[: 3 * g.nz * ny * nx].view(3, g.nz, ny, nx)
 
 
 def wavelet2d_gradient_image(noise, den, nx, ny, octave, out=None):
