@@ -1,43 +1,32 @@
 """Every kernel of csrc/wn_wavelet_grad.hip (the gradient point kernel, the exact grid kernel and the separable brick kernel
-for 1..8 bands) compiles without scratch: a spill would put vector-memory traffic on the brick kernel's store stream.
-This compiles the file with the Makefile's own command line for the device only and reads the kernel descriptors."""
-import os
-import re
-import shlex
-import subprocess
+for 1..8 bands) compiles without scratch: a spill would put vector-memory traffic on the brick kernel's store stream.  The
+brick kernel keeps its occupancy by registers (6 waves per SIMD for one band, 4 for more) and its static LDS (the boxes'
+geometry: 24 bytes per band).  This compiles the file with the Makefile's own command line for the device only and reads
+the kernel descriptors."""
+import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "wavelet-noise-in-ray-tracing_amd")
-SRC = "csrc/wn_wavelet_grad.hip"
+from _device_asm import assert_no_scratch, descriptor, device_assembly, kernels, waves_per_simd
 
-KERNELS = ([f"_ZN12_GLOBAL__N_122grad3d_grid_sep_kernelILi{nb}EEEvNS_11GradSepArgsE" for nb in range(1, 9)]
+SEP = "_ZN12_GLOBAL__N_122grad3d_grid_sep_kernelILi{}EEEvNS_11GradSepArgsE"
+KERNELS = ([SEP.format(nb) for nb in range(1, 9)]
            + [f"_ZN12_GLOBAL__N_125grad3d_grid_direct_kernelILb{p}EEEvNS_14GradDirectArgsE" for p in (0, 1)]
            + [f"_ZN12_GLOBAL__N_120grad3d_points_kernelILb{p}ELb{m}EEEvNS_14GradPointsArgsE" for p in (0, 1) for m in (0, 1)])
 
 
-def _makefile_compile_command():
-    out = subprocess.run(["make", "--no-print-directory", "-n", "-B", "-C", PKG, "build/wn_wavelet_grad.o"],
-                         capture_output=True, text=True, check=True).stdout
-    lines = [ln for ln in out.splitlines() if SRC in ln and " -c " in ln]
-    assert len(lines) == 1, out
-    return shlex.split(lines[0])
+@pytest.fixture(scope="module")
+def text(tmp_path_factory):
+    return device_assembly("wn_wavelet_grad", tmp_path_factory.mktemp("asm"))
 
 
-def test_gradient_kernels_use_no_scratch(tmp_path):
-    cmd = _makefile_compile_command()
-    i = cmd.index("-o")
-    del cmd[i:i + 2]
-    cmd.remove("-c")
-    asm = tmp_path / "wn_wavelet_grad.s"
-    cmd += ["--cuda-device-only", "-S", "-o", str(asm)]
-    res = subprocess.run(cmd, cwd=PKG, capture_output=True, text=True, timeout=600)
-    assert res.returncode == 0, res.stderr
-    text = asm.read_text()
-    found = set(re.findall(r"^\s*\.amdhsa_kernel (\S+)", text, re.M))
-    assert found == set(KERNELS), sorted(found ^ set(KERNELS))
+def test_gradient_kernels_use_no_scratch(text):
+    assert kernels(text) == set(KERNELS), sorted(kernels(text) ^ set(KERNELS))
     for sym in KERNELS:
-        body = re.search(rf"^{sym}:[^\n]*\n(.*?)^\.Lfunc_end\d+:", text, re.S | re.M)
-        assert body, f"{sym} not found in the device assembly"
-        assert "scratch_" not in body.group(1), f"{sym} spills to scratch"
-        kd = re.search(rf"^\s*\.amdhsa_kernel {sym}\n(.*?)^\s*\.end_amdhsa_kernel", text, re.S | re.M)
-        assert kd and re.search(r"\.amdhsa_private_segment_fixed_size 0\n", kd.group(1)), f"{sym} has a private segment"
+        assert_no_scratch(text, sym)
+
+
+def test_brick_kernel_keeps_its_occupancy(text):
+    for nb in range(1, 9):
+        d = descriptor(text, SEP.format(nb))
+        print(f"grad3d_grid_sep_kernel<{nb}>: vgprs", d["next_free_vgpr"], "static LDS", d["group_segment_fixed_size"])
+        assert waves_per_simd(d["next_free_vgpr"]) >= (6 if nb == 1 else 4), (nb, d["next_free_vgpr"])
+        assert d["group_segment_fixed_size"] == 24 * nb, (nb, d["group_segment_fixed_size"])

@@ -3,13 +3,7 @@ instantiations) compile without scratch: the run form keeps 24 running sums per 
 vector-memory traffic into every sample.  The value kernels of csrc/wn_perlin.hip are not this feature's to change: their
 VGPR counts, static LDS and scratch are pinned to the figures they had before the gradient was added.  Both files are
 compiled with the Makefile's own command line for the device only, and the kernel descriptors are read."""
-import os
-import re
-import shlex
-import subprocess
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "wavelet-noise-in-ray-tracing_amd")
+from _device_asm import assert_no_scratch, descriptor, device_assembly, kernels
 
 GRAD_KERNELS = ["_ZN12_GLOBAL__N_131perlin_grad_grid_generic_kernelENS_18PerlinGradGridArgsE",
                 "_ZN12_GLOBAL__N_125perlin_grad_points_kernelENS_20PerlinGradPointsArgsE",
@@ -30,55 +24,24 @@ VALUE_KERNELS = {"_ZN12_GLOBAL__N_126perlin_grid_generic_kernelENS_14PerlinGridA
                  "_ZN12_GLOBAL__N_120noise_texture_kernelILb0EEEvNS_12NoiseTexArgsE": (60, 512)}
 
 
-def _device_assembly(stem, tmp_path):
-    """The device assembly of csrc/<stem>.hip, compiled as the Makefile compiles it."""
-    src = f"csrc/{stem}.hip"
-    out = subprocess.run(["make", "--no-print-directory", "-n", "-B", "-C", PKG, f"build/{stem}.o"],
-                         capture_output=True, text=True, check=True).stdout
-    lines = [ln for ln in out.splitlines() if src in ln and " -c " in ln]
-    assert len(lines) == 1, out
-    cmd = shlex.split(lines[0])
-    i = cmd.index("-o")
-    del cmd[i:i + 2]
-    cmd.remove("-c")
-    asm = tmp_path / f"{stem}.s"
-    cmd += ["--cuda-device-only", "-S", "-o", str(asm)]
-    res = subprocess.run(cmd, cwd=PKG, capture_output=True, text=True, timeout=900)
-    assert res.returncode == 0, res.stderr
-    return asm.read_text()
-
-
-def _descriptor(text, sym):
-    kd = re.search(rf"^\s*\.amdhsa_kernel {sym}\n(.*?)^\s*\.end_amdhsa_kernel", text, re.S | re.M)
-    assert kd, f"{sym} has no kernel descriptor"
-    return {k: int(v) for k, v in re.findall(r"\.amdhsa_(\w+) (\d+)\n", kd.group(1))}
-
-
-def _assert_no_scratch(text, sym):
-    body = re.search(rf"^{sym}:[^\n]*\n(.*?)^\.Lfunc_end\d+:", text, re.S | re.M)
-    assert body, f"{sym} not found in the device assembly"
-    assert "scratch_" not in body.group(1), f"{sym} spills to scratch"
-    assert _descriptor(text, sym)["private_segment_fixed_size"] == 0, f"{sym} has a private segment"
-
-
 def test_perlin_gradient_kernels_use_no_scratch(tmp_path):
-    text = _device_assembly("wn_perlin_grad", tmp_path)
-    found = set(re.findall(r"^\s*\.amdhsa_kernel (\S+)", text, re.M))
+    text = device_assembly("wn_perlin_grad", tmp_path)
+    found = kernels(text)
     assert found == set(GRAD_KERNELS), sorted(found ^ set(GRAD_KERNELS))
     for sym in GRAD_KERNELS:
-        _assert_no_scratch(text, sym)
-        d = _descriptor(text, sym)
+        assert_no_scratch(text, sym)
+        d = descriptor(text, sym)
         print(sym, "vgprs", d["next_free_vgpr"], "static LDS", d["group_segment_fixed_size"])
         # the run form is launched with 8 waves per workgroup: two waves per SIMD share its 512 registers
         assert d["next_free_vgpr"] <= 256
 
 
 def test_perlin_value_kernels_keep_their_resources(tmp_path):
-    text = _device_assembly("wn_perlin", tmp_path)
-    found = set(re.findall(r"^\s*\.amdhsa_kernel (\S+)", text, re.M))
+    text = device_assembly("wn_perlin", tmp_path)
+    found = kernels(text)
     assert found == set(VALUE_KERNELS), sorted(found ^ set(VALUE_KERNELS))
     for sym, (vgprs, lds) in VALUE_KERNELS.items():
-        _assert_no_scratch(text, sym)
-        d = _descriptor(text, sym)
+        assert_no_scratch(text, sym)
+        d = descriptor(text, sym)
         assert (d["next_free_vgpr"], d["group_segment_fixed_size"]) == (vgprs, lds), (sym, d["next_free_vgpr"],
                                                                                         d["group_segment_fixed_size"])

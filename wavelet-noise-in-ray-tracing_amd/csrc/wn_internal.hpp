@@ -14,6 +14,8 @@
 #include "wn_eval.hpp" // dmod, pow2_mask, bspline and the exact evaluators, shared with host/scalar_eval.cpp
 #include "wnoise.h"
 
+typedef float v4f __attribute__((ext_vector_type(4)));
+
 struct wn_tile {
     int n = 0;          // even tile size (0 = empty tile)
     int dims = 0;       // 2 or 3
@@ -106,7 +108,8 @@ int check_perm(const wn_perm *perm, const char *entry);
 inline bool vec4_ok(const float *out, int nx) { return nx % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0; }
 
 // 256-lane workgroups for a grid-stride loop over `total` items: at least one, at most `cap`.
-inline int stride_blocks(size_t total, size_t cap)
+constexpr size_t kStrideBlockCap = 256u * 8u * 8u;
+inline int stride_blocks(size_t total, size_t cap = kStrideBlockCap)
 {
     const size_t b = (total + 255) / 256;
     return (int)(b < 1 ? 1 : (b > cap ? cap : b));
@@ -140,11 +143,17 @@ inline bool lattice_step(const GridArgs &g, float oscale, bool with_z_const, boo
 }
 
 // WMultibandNoise (Cook & DeRose, Appendix 2): bands run while s + first_band + b < 0, band b at 2^(first_band+b) with
-// weight w_host[b]; the variance sums ALL nbands.  Checks nbands / w_host, then fills a's nbands (the active bands),
+// weight w_host[b]; the variance sums ALL nbands.  The argument structs of the multiband kernels carry Bands as a base
+// (wn::multiband_exact reads it).  multiband_bands checks nbands / w_host, then fills nbands (the active bands),
 // band_scale, band_w, apply_div and out_div.
 constexpr int kMaxBands = 8;
-template <typename Args>
-int multiband_bands(float s, int first_band, int nbands, const float *w_host, float var_per_band, Args *a)
+struct Bands {
+    int nbands;
+    float band_scale[kMaxBands], band_w[kMaxBands]; // 2^(first_band+b) and w_host[b] of the active bands
+    float out_div;
+    int apply_div;
+};
+inline int multiband_bands(float s, int first_band, int nbands, const float *w_host, float var_per_band, Bands *a)
 {
     if (nbands < 0 || nbands > kMaxBands)
         return fail(WN_ERR_INVALID, "nbands must be in 0..%d (got %d)", kMaxBands, nbands);
@@ -202,6 +211,46 @@ __device__ __forceinline__ float lattice_coord(int i, float den, float range, fl
     c = c * oscale;
     c = c * post;
     return c;
+}
+
+// The lattice of the sample-per-lane grid kernels (den = (float)g.den): the coordinate of index i along x or y, of plane z
+// of the call (g.z0 + z, or z_const in z_const_mode), and of sample e of nx * ny * nz (2-D: nx * ny) samples, x fastest.
+__device__ __forceinline__ float grid_coord(const GridArgs &g, float den, int i)
+{
+    return lattice_coord(i, den, g.base_range, g.octave_scale, g.post_scale);
+}
+
+__device__ __forceinline__ float grid_zcoord(const GridArgs &g, float den, int z)
+{
+    return g.z_const_mode ? g.z_const : grid_coord(g, den, g.z0 + z);
+}
+
+__device__ __forceinline__ void lattice_index(const GridArgs &g, size_t e, int &x, int &y, int &z)
+{
+    x = (int)(e % g.nx);
+    const size_t r = e / g.nx;
+    y = (int)(r % g.ny);
+    z = (int)(r / g.ny);
+}
+
+__device__ __forceinline__ void lattice_point(const GridArgs &g, float den, int x, int y, int z, float p[3])
+{
+    p[0] = grid_coord(g, den, x);
+    p[1] = grid_coord(g, den, y);
+    p[2] = grid_zcoord(g, den, z);
+}
+
+__device__ __forceinline__ void lattice_point(const GridArgs &g, float den, size_t e, float p[3])
+{
+    int x, y, z;
+    lattice_index(g, e, x, y, z);
+    lattice_point(g, den, x, y, z, p);
+}
+
+__device__ __forceinline__ void lattice_point2d(const GridArgs &g, float den, size_t e, float &px, float &py)
+{
+    px = grid_coord(g, den, (int)(e % g.nx));
+    py = grid_coord(g, den, (int)(e / g.nx));
 }
 
 // lattice_coord with the division replaced by an exact multiply when den is a power of two (inv_den = inv_den_of(den)).

@@ -18,7 +18,7 @@
 // Grids write three consecutive volumes of nx * ny * nz samples (vx, vy, vz), each in wn_eval3d_grid's layout.  Derivatives
 // are taken with respect to the coordinate the sample passes to evaluate3D (multiband: the lattice coordinate p), and
 // out_scale multiplies all three channels last.
-#include "wn_internal.hpp"
+#include "wn_brick.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -28,18 +28,12 @@ namespace {
 using wn::GridArgs;
 using wn::kMaxBands;
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-
 // What wn::eval3d_curl_exact / multiband_curl_exact read.
-struct CurlEval {
+struct CurlEval : wn::Bands {
     const float *coef;
     int n, nmask;
     int off[9]; // (x, y, z) of psi0, psi1, psi2, each in [0, n)
     int mb;     // 0: evaluate3D potentials; 1: WMultibandNoise potentials (nbands may be 0: no band is active)
-    int nbands;
-    float band_scale[kMaxBands], band_w[kMaxBands];
-    float out_div;
-    int apply_div;
 };
 
 // ---- point lists -----------------------------------------------------------------------------------------------------
@@ -78,14 +72,8 @@ __global__ __launch_bounds__(256) void curl3d_grid_direct_kernel(const CurlDirec
     const GridArgs &g = a.g;
     const float den = (float)g.den;
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < a.vol; e += (size_t)gridDim.x * blockDim.x) {
-        const int x = (int)(e % g.nx);
-        const size_t r = e / g.nx;
-        const int y = (int)(r % g.ny), z = (int)(r / g.ny);
-        const float p[3] = {wn::lattice_coord(x, den, g.base_range, g.octave_scale, g.post_scale),
-                            wn::lattice_coord(y, den, g.base_range, g.octave_scale, g.post_scale),
-                            g.z_const_mode ? g.z_const
-                                           : wn::lattice_coord(g.z0 + z, den, g.base_range, g.octave_scale, g.post_scale)};
-        float v[3];
+        float p[3], v[3];
+        wn::lattice_point(g, den, e, p);
         if (a.e.mb) wn::multiband_curl_exact<PADDED>(a.e, p, v);
         else wn::eval3d_curl_exact<PADDED>(a.e.coef, a.e.n, a.e.nmask, a.e.off, p[0], p[1], p[2], v);
         a.out[e] = v[0] * g.out_scale;
@@ -95,8 +83,7 @@ __global__ __launch_bounds__(256) void curl3d_grid_direct_kernel(const CurlDirec
 }
 
 // ---- dense grids, default tier: the separable brick kernel ---------------------------------------------------------------
-// The gradient brick kernel's brick (256 x 8 x 8 samples per 4-wave workgroup; a lane owns 4 consecutive x samples, a wave
-// rows (y, z)) and regime.  Per band the workgroup stages THREE boxes, box_k[k][j][i] = coef[Mod(kz0+k+oz_k)]
+// The brick frame of wn_brick.hpp.  Per band the workgroup stages THREE boxes, box_k[k][j][i] = coef[Mod(kz0+k+oz_k)]
 // [Mod(jy0+j+oy_k)][Mod(ix0+i+ox_k)], of one geometry (the potentials share the mids), and the lane forms the 4-wide x
 // window (Wx, Dx) once.  Per row, band and potential the lane contracts the 4 box columns under its samples' taps
 //     z:  Z = sum_k wz_k C[k][j][i],  Z' = sum_k dz_k C[k][j][i]
@@ -106,19 +93,18 @@ __global__ __launch_bounds__(256) void curl3d_grid_direct_kernel(const CurlDirec
 //     vx = sum_i Wx_i (B2 - D1),  vy = sum_i (Wx_i D0 - Dx_i A2),  vz = sum_i (Dx_i A1 - Wx_i B0)
 // the components accumulated with signs.  Every sample is summed in the same order from its own weights and coefficients,
 // wherever it sits in a brick: its bits do not depend on how the volume was cut into z-slabs.  Fused (FMA) arithmetic.
-constexpr int kGX = 256, kGY = 8, kGZ = 8; // samples per brick
-constexpr int kGWaves = 4;
+using wn::kGWaves;
+using wn::kGX;
+using wn::kGY;
+using wn::kGZ;
 // LDS: one band's three boxes are at most 3 x 3.2 K floats inside two_mids, eight bands' less than twice that (each lower
 // band's step halves): < 77 KB.  Up to 48 KB the launch needs nothing; beyond, the kernel is opted in to the request
 // (wn::ensure_dynamic_lds; the CU has 160 KB, so two workgroups still share one).  The cap never binds inside two_mids.
 constexpr int kCMaxBoxFloats = 36 * 1024; // 144 KB
 constexpr size_t kLdsNoOptIn = 48 * 1024;
 
-struct CurlBand {
-    float qmul;  // the band's coordinate is q = p * qmul (1; multiband 2 * 2^(first_band+b): exact)
-    float fg;    // factor of its derivatives: out_scale, or w_b / out_div * out_scale * qmul
-    int box_off; // float offset of its first box in dynamic LDS; potential k's box at box_off + k * box_cap
-    int box_cap; // floats reserved for each of its boxes
+struct CurlBand : wn::BrickBand { // potential k's box is box k
+    float fg; // factor of its derivatives: out_scale, or w_b / out_div * out_scale * qmul
 };
 
 struct CurlSepArgs {
@@ -142,8 +128,8 @@ __global__ __launch_bounds__(64 * kGWaves) void curl3d_grid_sep_kernel(const Cur
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int x_first = blockIdx.x * kGX, y_first = blockIdx.y * kGY, z_first = blockIdx.z * kGZ;
-    auto coord = [&](int i) { return wn::lattice_coord(i, den, g.base_range, g.octave_scale, g.post_scale); };
-    auto zcoord = [&](int zi) { return g.z_const_mode ? g.z_const : coord(g.z0 + zi); };
+    auto coord = [&](int i) { return wn::grid_coord(g, den, i); };
+    auto zcoord = [&](int zi) { return wn::grid_zcoord(g, den, zi); };
 
     // ---- the boxes' geometry (shared by the three potentials): the mids of an axis's first and last sample bound all of
     // them; one column / row / plane of support on either side, and one more column (the window's fourth, at zero weight)
@@ -163,23 +149,14 @@ __global__ __launch_bounds__(64 * kGWaves) void curl3d_grid_sep_kernel(const Cur
     }
     __syncthreads();
 
-    // ---- fill: a wave takes whole (k, j) rows of a potential's box
+    // ---- fill: a potential's box is the tile's, shifted by its offsets
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
-        const int ix0 = s_geo[b][0], jy0 = s_geo[b][1], kz0 = s_geo[b][2];
-        const int ex = s_geo[b][3], ey = s_geo[b][4], ez = s_geo[b][5];
-        if ((long long)ex * ey * ez > a.band[b].box_cap) return; // never: the host bounds the box (memory safety); uniform
+        if (!wn::brick_box_fits(s_geo[b], a.band[b].box_cap)) return; // never
 #pragma unroll 1
-        for (int k3 = 0; k3 < 3; ++k3) {
-            float *bb = box + a.band[b].box_off + k3 * a.band[b].box_cap;
-            const int ox = a.off[3 * k3], oy = a.off[3 * k3 + 1], oz = a.off[3 * k3 + 2];
-            for (int r = wave; r < ey * ez; r += kGWaves) {
-                const int k = r / ey, j = r - k * ey;
-                const float *row =
-                    a.coef + ((size_t)wn::dmod(kz0 + k + oz, a.n, a.nmask) * a.n + wn::dmod(jy0 + j + oy, a.n, a.nmask)) * a.n;
-                for (int i = lane; i < ex; i += 64) bb[r * ex + i] = row[wn::dmod(ix0 + i + ox, a.n, a.nmask)];
-            }
-        }
+        for (int k3 = 0; k3 < 3; ++k3)
+            wn::brick_fill(box + a.band[b].box_off + k3 * a.band[b].box_cap, a.coef, a.n, a.nmask, s_geo[b], a.off[3 * k3],
+                           a.off[3 * k3 + 1], a.off[3 * k3 + 2], wave, lane);
     }
 
     // ---- x: this lane's 4 samples (coordinates once: the bands scale them) in a 4-column window per band
@@ -187,25 +164,8 @@ __global__ __launch_bounds__(64 * kGWaves) void curl3d_grid_sep_kernel(const Cur
     float px[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) px[q] = coord(min(x0 + q, g.nx - 1));
-    struct XWin { int col; float w[4][4], d[4][4]; }; // window's first box column; per sample q the window's weights
-    auto x_window = [&](int b, XWin &xw) {
-        int m[4];
-        float w[4][3], d[4][3];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) wn::bspline_grad(px[q] * a.band[b].qmul, m[q], w[q], d[q]);
-        xw.col = m[0] - 1 - s_geo[b][0];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const bool sh = m[q] != m[0]; // then m[q] == m[0] + 1 (the host's two_mids)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                xw.w[q][c] = sh ? (c == 0 ? 0.0f : w[q][c - 1]) : (c == 3 ? 0.0f : w[q][c]);
-                xw.d[q][c] = sh ? (c == 0 ? 0.0f : d[q][c - 1]) : (c == 3 ? 0.0f : d[q][c]);
-            }
-        }
-    };
-    XWin xw1;
-    if (NB == 1) x_window(0, xw1);
+    wn::XWin xw1;
+    if (NB == 1) wn::brick_x_window(px, a.band[0].qmul, s_geo[0][0], xw1);
     __syncthreads();
 
     const int rows_y = min(kGY, g.ny - y_first), rows_z = min(kGZ, g.nz - z_first);
@@ -216,10 +176,10 @@ __global__ __launch_bounds__(64 * kGWaves) void curl3d_grid_sep_kernel(const Cur
         // bands one after the other (not unrolled: each band's x window is live only inside its iteration)
 #pragma unroll 1
         for (int b = 0; b < NB; ++b) {
-            XWin xwb;
-            if (NB != 1) x_window(b, xwb);
-            const XWin &xw = NB == 1 ? xw1 : xwb;
             const float qm = a.band[b].qmul;
+            wn::XWin xwb;
+            if (NB != 1) wn::brick_x_window(px, qm, s_geo[b][0], xwb);
+            const wn::XWin &xw = NB == 1 ? xw1 : xwb;
             int my, mz;
             float wy[3], dy[3], wz[3], dz[3];
             wn::bspline_grad(py * qm, my, wy, dy);
@@ -270,77 +230,32 @@ __global__ __launch_bounds__(64 * kGWaves) void curl3d_grid_sep_kernel(const Cur
             }
         }
         float *dst = a.out + ((size_t)(z_first + zi) * g.ny + (y_first + yi)) * g.nx + x0;
-        if (a.vec4_ok && x0 + 3 < g.nx) {
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch)
-                *reinterpret_cast<v4f *>(dst + ch * a.vol) = v4f{acc[ch][0], acc[ch][1], acc[ch][2], acc[ch][3]};
-        } else {
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch)
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    if (x0 + q < g.nx) dst[ch * a.vol + q] = acc[ch][q];
-        }
+        wn::brick_store_row(dst, a.vol, a.vec4_ok, x0, g.nx, acc);
     }
 }
 
-constexpr size_t kBlockCap = 256u * 8u * 8u; // workgroups of a grid-stride launch (wn::stride_blocks)
 constexpr size_t kPointBlockCap = 256u * 8u;  // of the point kernel's: its lanes hold 27 row loads each
 
-template <int NB>
-int launch_curl_sep(const CurlSepArgs &a, dim3 grid, size_t lds, hipStream_t stream)
-{
-    if (lds > kLdsNoOptIn &&
-        !wn::ensure_dynamic_lds(reinterpret_cast<const void *>(&curl3d_grid_sep_kernel<NB>), wn::current_device(), lds))
-        return wn::kDeclined; // the runtime refused the LDS: the exact kernel serves the lattice
-    hipLaunchKernelGGL(curl3d_grid_sep_kernel<NB>, grid, dim3(64 * kGWaves), lds, stream, a);
-    WN_LAUNCH_CHECK("curl3d_grid_sep_kernel");
-    return WN_OK;
-}
-
-// Launches the brick kernel when the lattice is in its regime -- the gradient brick kernel's: a tile that is not empty
-// (any size: the boxes are filled modulo n), steps >= 0 at which 4 consecutive samples span at most two mids in every band
-// (wn::LatticeStep::two_mids: step < 1/3 cell) -- and the runtime grants the boxes' LDS (see kCMaxBoxFloats).  nbands bands
-// (1..kMaxBands) with coordinate multipliers qmul[b] and the factors fg[b] of their derivatives.
+// Launches the brick kernel when the lattice is in its regime (wn::brick_plan, three boxes per band) and the runtime grants
+// the boxes' LDS (see kCMaxBoxFloats); when it refuses, the exact kernel serves the lattice.  nbands bands with coordinate
+// multipliers qmul[b] and the factors fg[b] of their derivatives.
 int curl_sep_try(const wn_tile *tile, const GridArgs &g, const int off[9], int nbands, const float *qmul, const float *fg,
                  float *out_dev, hipStream_t stream)
 {
-    if (tile->n == 0 || nbands < 1 || nbands > kMaxBands || g.nx <= 0 || g.ny <= 0 || g.nz <= 0) return wn::kDeclined;
     CurlSepArgs a{};
-    long long box_total = 0;
-    for (int b = 0; b < nbands; ++b) {
-        wn::LatticeStep ls;
-        if (!wn::lattice_step(g, g.octave_scale * qmul[b], true, false, 0.0, &ls) || !ls.two_mids()) return wn::kDeclined;
-        const long long ex = ls.extent(kGX) + 1, ey = ls.extent(kGY), ez = g.z_const_mode ? 3 : ls.extent(kGZ);
-        a.band[b].qmul = qmul[b];
-        a.band[b].fg = fg[b];
-        a.band[b].box_off = (int)box_total;
-        a.band[b].box_cap = (int)(ex * ey * ez);
-        box_total += 3 * ex * ey * ez;
-        if (box_total > kCMaxBoxFloats) return wn::kDeclined;
-    }
-    const int nbx = (g.nx + kGX - 1) / kGX, nby = (g.ny + kGY - 1) / kGY, nbz = (g.nz + kGZ - 1) / kGZ;
-    if (nby > 65535 || nbz > 65535) return wn::kDeclined;
-    a.coef = tile->dev;
-    a.out = out_dev;
-    a.vol = (size_t)g.nx * g.ny * g.nz;
-    a.n = tile->n;
-    a.nmask = wn::pow2_mask(tile->n);
+    dim3 grid;
+    size_t lds;
+    if (!wn::brick_plan(tile, g, nbands, qmul, 3, kCMaxBoxFloats, out_dev, &a, &grid, &lds)) return wn::kDeclined;
+    for (int b = 0; b < nbands; ++b) a.band[b].fg = fg[b];
     std::copy(off, off + 9, a.off);
-    a.g = g;
-    a.vec4_ok = wn::vec4_ok(out_dev, g.nx);
-    const size_t lds = (size_t)box_total * sizeof(float);
-    const dim3 grid(nbx, nby, nbz);
-    switch (nbands) {
-    case 1: return launch_curl_sep<1>(a, grid, lds, stream);
-    case 2: return launch_curl_sep<2>(a, grid, lds, stream);
-    case 3: return launch_curl_sep<3>(a, grid, lds, stream);
-    case 4: return launch_curl_sep<4>(a, grid, lds, stream);
-    case 5: return launch_curl_sep<5>(a, grid, lds, stream);
-    case 6: return launch_curl_sep<6>(a, grid, lds, stream);
-    case 7: return launch_curl_sep<7>(a, grid, lds, stream);
-    default: return launch_curl_sep<8>(a, grid, lds, stream);
-    }
+    return wn::brick_dispatch(nbands, [&](auto nb) {
+        constexpr auto kernel = curl3d_grid_sep_kernel<decltype(nb)::value>;
+        if (lds > kLdsNoOptIn && !wn::ensure_dynamic_lds(reinterpret_cast<const void *>(kernel), wn::current_device(), lds))
+            return (int)wn::kDeclined;
+        hipLaunchKernelGGL(kernel, grid, dim3(64 * kGWaves), lds, stream, a);
+        WN_LAUNCH_CHECK("curl3d_grid_sep_kernel");
+        return (int)WN_OK;
+    });
 }
 
 // The tile's fields of CurlEval (its padded copy when it has one) and the offsets reduced with the reference's Mod.
@@ -395,7 +310,7 @@ int curl_grid(const wn_tile *tile, const wn_grid *grid, const CurlEval &e, float
         if ((rc = curl_sep_try(tile, g, e.off, e.mb ? e.nbands : 1, qmul, fg, out_dev, stream)) != wn::kDeclined) return rc;
     }
     CurlDirectArgs d{e, out_dev, total, g};
-    const dim3 blocks(wn::stride_blocks(total, kBlockCap)), block(256);
+    const dim3 blocks(wn::stride_blocks(total)), block(256);
     if (tile->dev_padded) hipLaunchKernelGGL(curl3d_grid_direct_kernel<true>, blocks, block, 0, stream, d);
     else hipLaunchKernelGGL(curl3d_grid_direct_kernel<false>, blocks, block, 0, stream, d);
     WN_LAUNCH_CHECK("curl3d_grid_direct_kernel");

@@ -17,7 +17,7 @@
 // Grids write four consecutive volumes of nx * ny * nz samples (value, d/dx, d/dy, d/dz), each in wn_eval3d_grid's layout.
 // The gradient is taken with respect to the coordinate the sample passes to evaluate3D (multiband: the lattice coordinate
 // p), and out_scale multiplies all four channels last.
-#include "wn_internal.hpp"
+#include "wn_brick.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -27,20 +27,13 @@ namespace {
 using wn::GridArgs;
 using wn::kMaxBands;
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-
 // ---- point lists -----------------------------------------------------------------------------------------------------
-struct GradPointsArgs {
+struct GradPointsArgs : wn::Bands {
     const float *coef;
     int n, nmask;
     const float *pts; // xyz interleaved
     v4f *out;         // {value, d/dx, d/dy, d/dz} per point
     size_t count;
-    // multiband (wn::multiband_bands)
-    int nbands;
-    float band_scale[kMaxBands], band_w[kMaxBands];
-    float out_div;
-    int apply_div;
 };
 
 template <bool PADDED, bool MB>
@@ -56,17 +49,12 @@ __global__ __launch_bounds__(256) void grad3d_points_kernel(const GradPointsArgs
 }
 
 // ---- dense grids, exact tier ---------------------------------------------------------------------------------------------
-struct GradDirectArgs {
+struct GradDirectArgs : wn::Bands { // nbands == 0: plain evaluate3D
     const float *coef;
     float *out;
     size_t vol; // samples per channel volume
     int n, nmask;
     GridArgs g;
-    // multiband (nbands == 0: plain evaluate3D)
-    int nbands;
-    float band_scale[kMaxBands], band_w[kMaxBands];
-    float out_div;
-    int apply_div;
 };
 
 template <bool PADDED>
@@ -75,14 +63,8 @@ __global__ __launch_bounds__(256) void grad3d_grid_direct_kernel(const GradDirec
     const GridArgs &g = a.g;
     const float den = (float)g.den;
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < a.vol; e += (size_t)gridDim.x * blockDim.x) {
-        const int x = (int)(e % g.nx);
-        const size_t r = e / g.nx;
-        const int y = (int)(r % g.ny), z = (int)(r / g.ny);
-        const float p[3] = {wn::lattice_coord(x, den, g.base_range, g.octave_scale, g.post_scale),
-                            wn::lattice_coord(y, den, g.base_range, g.octave_scale, g.post_scale),
-                            g.z_const_mode ? g.z_const
-                                           : wn::lattice_coord(g.z0 + z, den, g.base_range, g.octave_scale, g.post_scale)};
-        float gr[3];
+        float p[3], gr[3];
+        wn::lattice_point(g, den, e, p);
         const float v = a.nbands == 0 ? wn::eval3d_grad_exact<PADDED>(a.coef, a.n, a.nmask, p[0], p[1], p[2], gr)
                                       : wn::multiband_exact<PADDED, false, true>(a, p, nullptr, gr);
         a.out[e] = v * g.out_scale;
@@ -93,25 +75,22 @@ __global__ __launch_bounds__(256) void grad3d_grid_direct_kernel(const GradDirec
 }
 
 // ---- dense grids, default tier: the separable brick kernel ---------------------------------------------------------------
-// A workgroup (4 waves) owns a brick of 256 x 8 x 8 samples.  For every band it stages the brick's coefficient box in LDS
-// (periodic wrap resolved, x fastest) once.  A lane owns 4 consecutive x samples, a wave rows (y, z) of the brick.  Per
-// row and band the lane contracts the 4 box columns under its samples' taps (4 consecutive samples span at most two mids:
-// columns m0 - 1 .. m0 + 2):
+// The brick frame of wn_brick.hpp with one coefficient box per band.  Per row and band the lane contracts the 4 box
+// columns under its samples' taps:
 //     z:  Z = sum_k wz_k C[k][j][i],  Z' = sum_k dz_k C[k][j][i]             (2 values per (j, i))
 //     y:  A = sum_j wy_j Z,  B = sum_j dy_j Z,  D = sum_j wy_j Z'           (3 values per column i)
 //     x:  value = sum_i Wx_i A, d/dx = sum_i Dx_i A, d/dy = sum_i Wx_i B, d/dz = sum_i Wx_i D
 // with the x weights of each sample placed in a 4-wide window (Wx, Dx: zero outside its three taps), and stores a float4
 // per channel.  Every sample is summed in the same order from its own weights and coefficients, wherever it sits in a
 // brick: its bits do not depend on how the volume was cut into z-slabs.  Fused (FMA) arithmetic; within 1e-5 scaled.
-constexpr int kGX = 256, kGY = 8, kGZ = 8; // samples per brick
-constexpr int kGWaves = 4;
+using wn::kGWaves;
+using wn::kGX;
+using wn::kGY;
+using wn::kGZ;
 constexpr int kGMaxBoxFloats = 12 * 1024; // 48 KB of LDS for all bands' boxes
 
-struct GradBand {
-    float qmul;   // the band's coordinate is q = p * qmul (1; multiband 2 * 2^(first_band+b): exact)
+struct GradBand : wn::BrickBand {
     float fv, fg; // factors of its value and of its gradient: w_b / out_div * out_scale, and that * qmul
-    int box_off;  // float offset of its box in dynamic LDS
-    int box_cap;  // floats reserved for it
 };
 
 struct GradSepArgs {
@@ -134,8 +113,8 @@ __global__ __launch_bounds__(64 * kGWaves) void grad3d_grid_sep_kernel(const Gra
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int x_first = blockIdx.x * kGX, y_first = blockIdx.y * kGY, z_first = blockIdx.z * kGZ;
-    auto coord = [&](int i) { return wn::lattice_coord(i, den, g.base_range, g.octave_scale, g.post_scale); };
-    auto zcoord = [&](int zi) { return g.z_const_mode ? g.z_const : coord(g.z0 + zi); };
+    auto coord = [&](int i) { return wn::grid_coord(g, den, i); };
+    auto zcoord = [&](int zi) { return wn::grid_zcoord(g, den, zi); };
 
     // ---- the boxes: coordinates are monotone in the index, so the mids of an axis's first and last sample bound all of
     // them; one column / row / plane of support on either side, and one more column (the window's fourth, at zero weight)
@@ -155,18 +134,11 @@ __global__ __launch_bounds__(64 * kGWaves) void grad3d_grid_sep_kernel(const Gra
     }
     __syncthreads();
 
-    // ---- fill: box_b[k][j][i] = coef[Mod(kz0+k)][Mod(jy0+j)][Mod(ix0+i)]; a wave takes whole (k, j) rows
+    // ---- fill: box_b[k][j][i] = coef[Mod(kz0+k)][Mod(jy0+j)][Mod(ix0+i)]
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
-        const int ix0 = s_geo[b][0], jy0 = s_geo[b][1], kz0 = s_geo[b][2];
-        const int ex = s_geo[b][3], ey = s_geo[b][4], ez = s_geo[b][5];
-        if ((long long)ex * ey * ez > a.band[b].box_cap) return; // never: the host bounds the box (memory safety); uniform
-        float *bb = box + a.band[b].box_off;
-        for (int r = wave; r < ey * ez; r += kGWaves) {
-            const int k = r / ey, j = r - k * ey;
-            const float *row = a.coef + ((size_t)wn::dmod(kz0 + k, a.n, a.nmask) * a.n + wn::dmod(jy0 + j, a.n, a.nmask)) * a.n;
-            for (int i = lane; i < ex; i += 64) bb[r * ex + i] = row[wn::dmod(ix0 + i, a.n, a.nmask)];
-        }
+        if (!wn::brick_box_fits(s_geo[b], a.band[b].box_cap)) return; // never
+        wn::brick_fill(box + a.band[b].box_off, a.coef, a.n, a.nmask, s_geo[b], 0, 0, 0, wave, lane);
     }
 
     // ---- x: this lane's 4 samples (coordinates once: the bands scale them) in a 4-column window per band
@@ -174,25 +146,8 @@ __global__ __launch_bounds__(64 * kGWaves) void grad3d_grid_sep_kernel(const Gra
     float px[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) px[q] = coord(min(x0 + q, g.nx - 1));
-    struct XWin { int col; float w[4][4], d[4][4]; }; // window's first box column; per sample q the window's weights
-    auto x_window = [&](int b, XWin &xw) {
-        int m[4];
-        float w[4][3], d[4][3];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) wn::bspline_grad(px[q] * a.band[b].qmul, m[q], w[q], d[q]);
-        xw.col = m[0] - 1 - s_geo[b][0];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const bool sh = m[q] != m[0]; // then m[q] == m[0] + 1 (the host's two_mids)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                xw.w[q][c] = sh ? (c == 0 ? 0.0f : w[q][c - 1]) : (c == 3 ? 0.0f : w[q][c]);
-                xw.d[q][c] = sh ? (c == 0 ? 0.0f : d[q][c - 1]) : (c == 3 ? 0.0f : d[q][c]);
-            }
-        }
-    };
-    XWin xw1;
-    if (NB == 1) x_window(0, xw1);
+    wn::XWin xw1;
+    if (NB == 1) wn::brick_x_window(px, a.band[0].qmul, s_geo[0][0], xw1);
     __syncthreads();
 
     const int rows_y = min(kGY, g.ny - y_first), rows_z = min(kGZ, g.nz - z_first);
@@ -203,10 +158,10 @@ __global__ __launch_bounds__(64 * kGWaves) void grad3d_grid_sep_kernel(const Gra
         // bands one after the other (not unrolled: each band's x window is live only inside its iteration)
 #pragma unroll 1
         for (int b = 0; b < NB; ++b) {
-            XWin xwb;
-            if (NB != 1) x_window(b, xwb);
-            const XWin &xw = NB == 1 ? xw1 : xwb;
             const float qm = a.band[b].qmul;
+            wn::XWin xwb;
+            if (NB != 1) wn::brick_x_window(px, qm, s_geo[b][0], xwb);
+            const wn::XWin &xw = NB == 1 ? xw1 : xwb;
             int my, mz;
             float wy[3], dy[3], wz[3], dz[3];
             wn::bspline_grad(py * qm, my, wy, dy);
@@ -245,77 +200,70 @@ __global__ __launch_bounds__(64 * kGWaves) void grad3d_grid_sep_kernel(const Gra
             }
         }
         float *dst = a.out + ((size_t)(z_first + zi) * g.ny + (y_first + yi)) * g.nx + x0;
-        if (a.vec4_ok && x0 + 3 < g.nx) {
-#pragma unroll
-            for (int ch = 0; ch < 4; ++ch)
-                *reinterpret_cast<v4f *>(dst + ch * a.vol) = v4f{acc[ch][0], acc[ch][1], acc[ch][2], acc[ch][3]};
-        } else {
-#pragma unroll
-            for (int ch = 0; ch < 4; ++ch)
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    if (x0 + q < g.nx) dst[ch * a.vol + q] = acc[ch][q];
-        }
+        wn::brick_store_row(dst, a.vol, a.vec4_ok, x0, g.nx, acc);
     }
 }
 
-constexpr size_t kBlockCap = 256u * 8u * 8u; // workgroups of a grid-stride launch (wn::stride_blocks)
-
-// Launches the brick kernel when the lattice is in its regime: a tile that is not empty (any size: the box is filled modulo
-// n), steps >= 0 at which 4 consecutive samples span at most two mids in every band (wn::LatticeStep::two_mids: step < 1/3
-// cell), and boxes that fit 48 KB of LDS (never binding inside two_mids: <= 3.2 K floats for one band, < 2x that for eight).
-// Nothing in it depends on how many planes the call computes beyond lattice_step's bound on the coordinates.  nbands
-// bands (1..kMaxBands) with coordinate multipliers qmul[b] and the factors of value and gradient.
+// Launches the brick kernel when the lattice is in its regime (wn::brick_plan) with boxes that fit 48 KB of LDS (never
+// binding inside two_mids: <= 3.2 K floats for one band, < 2x that for eight; no opt-in needed).  nbands bands with
+// coordinate multipliers qmul[b] and the factors of value and gradient.
 int grad_sep_try(const wn_tile *tile, const GridArgs &g, int nbands, const float *qmul, const float *fv, const float *fg,
                  float *out_dev, hipStream_t stream)
 {
-    if (tile->n == 0 || nbands < 1 || nbands > kMaxBands || g.nx <= 0 || g.ny <= 0 || g.nz <= 0) return wn::kDeclined;
     GradSepArgs a{};
-    long long box_total = 0;
+    dim3 grid;
+    size_t lds;
+    if (!wn::brick_plan(tile, g, nbands, qmul, 1, kGMaxBoxFloats, out_dev, &a, &grid, &lds)) return wn::kDeclined;
     for (int b = 0; b < nbands; ++b) {
-        wn::LatticeStep ls;
-        if (!wn::lattice_step(g, g.octave_scale * qmul[b], true, false, 0.0, &ls) || !ls.two_mids()) return wn::kDeclined;
-        const long long ex = ls.extent(kGX) + 1, ey = ls.extent(kGY), ez = g.z_const_mode ? 3 : ls.extent(kGZ);
-        a.band[b].qmul = qmul[b];
         a.band[b].fv = fv[b];
         a.band[b].fg = fg[b];
-        a.band[b].box_off = (int)box_total;
-        a.band[b].box_cap = (int)(ex * ey * ez);
-        box_total += ex * ey * ez;
-        if (box_total > kGMaxBoxFloats) return wn::kDeclined;
     }
-    const int nbx = (g.nx + kGX - 1) / kGX, nby = (g.ny + kGY - 1) / kGY, nbz = (g.nz + kGZ - 1) / kGZ;
-    if (nby > 65535 || nbz > 65535) return wn::kDeclined;
-    a.coef = tile->dev;
-    a.out = out_dev;
-    a.vol = (size_t)g.nx * g.ny * g.nz;
-    a.n = tile->n;
-    a.nmask = wn::pow2_mask(tile->n);
-    a.g = g;
-    a.vec4_ok = wn::vec4_ok(out_dev, g.nx);
-    const size_t lds = (size_t)box_total * sizeof(float); // <= 48 KB: no opt-in needed
-    const dim3 grid(nbx, nby, nbz), block(64 * kGWaves);
-    switch (nbands) {
-    case 1: hipLaunchKernelGGL(grad3d_grid_sep_kernel<1>, grid, block, lds, stream, a); break;
-    case 2: hipLaunchKernelGGL(grad3d_grid_sep_kernel<2>, grid, block, lds, stream, a); break;
-    case 3: hipLaunchKernelGGL(grad3d_grid_sep_kernel<3>, grid, block, lds, stream, a); break;
-    case 4: hipLaunchKernelGGL(grad3d_grid_sep_kernel<4>, grid, block, lds, stream, a); break;
-    case 5: hipLaunchKernelGGL(grad3d_grid_sep_kernel<5>, grid, block, lds, stream, a); break;
-    case 6: hipLaunchKernelGGL(grad3d_grid_sep_kernel<6>, grid, block, lds, stream, a); break;
-    case 7: hipLaunchKernelGGL(grad3d_grid_sep_kernel<7>, grid, block, lds, stream, a); break;
-    default: hipLaunchKernelGGL(grad3d_grid_sep_kernel<8>, grid, block, lds, stream, a); break;
-    }
+    wn::brick_dispatch(nbands, [&](auto nb) {
+        hipLaunchKernelGGL(grad3d_grid_sep_kernel<decltype(nb)::value>, grid, dim3(64 * kGWaves), lds, stream, a);
+        return WN_OK;
+    });
     WN_LAUNCH_CHECK("grad3d_grid_sep_kernel");
     return WN_OK;
 }
 
-// The exact tier on the tile's padded copy when it has one; the caller checks the launch.
-void launch_grad_direct(GradDirectArgs a, const wn_tile *tile, hipStream_t stream)
+// The grid entry points after their tile (and band) checks; d carries the bands of a multiband call (mb).  The brick
+// kernel (nbands >= 1) unless the caller asks for WN_GRID_EXACT or it declines, then the exact kernel on the tile's padded
+// copy when it has one.
+int grad_grid(const wn_tile *tile, const wn_grid *grid, GradDirectArgs d, bool mb, float *out_dev, hipStream_t stream)
 {
-    a.coef = tile->dev_padded ? tile->dev_padded : tile->dev;
-    const dim3 grid(wn::stride_blocks(a.vol, kBlockCap)), block(256);
-    if (tile->dev_padded) hipLaunchKernelGGL(grad3d_grid_direct_kernel<true>, grid, block, 0, stream, a);
-    else hipLaunchKernelGGL(grad3d_grid_direct_kernel<false>, grid, block, 0, stream, a);
+    GridArgs g;
+    int rc = wn::check_grid(grid, true, &g);
+    if (rc) return rc;
+    d.vol = (size_t)g.nx * g.ny * g.nz;
+    if (d.vol == 0) return WN_OK;
+    if (!out_dev) return wn::fail(WN_ERR_INVALID, "out_dev is NULL");
+    if (!(grid->flags & WN_GRID_EXACT) && (!mb || d.nbands >= 1)) {
+        // band b: q = p * (2 * 2^(first_band+b)); value factor w_b / out_div * out_scale, gradient factor that * 2 * 2^(..)
+        float qmul[kMaxBands] = {1.0f}, fv[kMaxBands] = {g.out_scale}, fg[kMaxBands] = {g.out_scale};
+        for (int b = 0; mb && b < d.nbands; ++b) {
+            qmul[b] = 2.0f * d.band_scale[b];
+            const double f = (double)d.band_w[b] / (double)d.out_div * (double)g.out_scale;
+            fv[b] = (float)f;
+            fg[b] = (float)(f * (double)qmul[b]);
+        }
+        if ((rc = grad_sep_try(tile, g, mb ? d.nbands : 1, qmul, fv, fg, out_dev, stream)) != wn::kDeclined) return rc;
+    }
+    if (mb && d.nbands == 0) {
+        // no band contributes: 0 (/ out_div) * out_scale in all four channels, evaluated on the device
+        d.nbands = 1;
+        d.band_scale[0] = 1.0f;
+        d.band_w[0] = 0.0f;
+    }
+    d.coef = tile->dev_padded ? tile->dev_padded : tile->dev;
+    d.out = out_dev;
+    d.n = tile->n;
+    d.nmask = wn::pow2_mask(tile->n);
+    d.g = g;
+    const dim3 blocks(wn::stride_blocks(d.vol)), block(256);
+    if (tile->dev_padded) hipLaunchKernelGGL(grad3d_grid_direct_kernel<true>, blocks, block, 0, stream, d);
+    else hipLaunchKernelGGL(grad3d_grid_direct_kernel<false>, blocks, block, 0, stream, d);
+    WN_LAUNCH_CHECK(mb ? "grad3d_grid_direct_kernel(multiband)" : "grad3d_grid_direct_kernel");
+    return WN_OK;
 }
 
 // The arguments every gradient entry point checks: the tile (wn::check_tile), and out4_dev 16-byte aligned for points.
@@ -338,7 +286,7 @@ int launch_grad_points(const wn_tile *tile, const GradPointsArgs &a, bool mb, hi
 {
     if (!a.pts || !a.out) return wn::fail(WN_ERR_INVALID, "points/out pointer is NULL");
     if (reinterpret_cast<uintptr_t>(a.out) & 15) return wn::fail(WN_ERR_INVALID, "out4_dev must be 16-byte aligned");
-    const dim3 grid(wn::stride_blocks(a.count, kBlockCap)), block(256);
+    const dim3 grid(wn::stride_blocks(a.count)), block(256);
     const bool padded = tile->dev_padded != nullptr;
     if (mb) {
         if (padded) hipLaunchKernelGGL((grad3d_points_kernel<true, true>), grid, block, 0, stream, a);
@@ -381,28 +329,9 @@ int wn_multiband3d_grad_points(const wn_tile *tile, const float *xyz_dev, size_t
 int wn_eval3d_grad_grid(const wn_tile *tile, const wn_grid *grid, float *out_dev, void *stream)
 {
     WN_ENTRY();
-    int rc = check_tile(tile, 3, "wn_eval3d_grad_grid");
+    const int rc = check_tile(tile, 3, "wn_eval3d_grad_grid");
     if (rc) return rc;
-    GridArgs g;
-    rc = check_grid(grid, true, &g);
-    if (rc) return rc;
-    const size_t total = (size_t)g.nx * g.ny * g.nz;
-    if (total == 0) return WN_OK;
-    if (!out_dev) return fail(WN_ERR_INVALID, "out_dev is NULL");
-    const hipStream_t st = as_stream(stream);
-    if (!(grid->flags & WN_GRID_EXACT)) {
-        const float one = 1.0f, os = g.out_scale;
-        if ((rc = grad_sep_try(tile, g, 1, &one, &os, &os, out_dev, st)) != kDeclined) return rc;
-    }
-    GradDirectArgs d{};
-    d.out = out_dev;
-    d.vol = total;
-    d.n = tile->n;
-    d.nmask = pow2_mask(tile->n);
-    d.g = g;
-    launch_grad_direct(d, tile, st);
-    WN_LAUNCH_CHECK("grad3d_grid_direct_kernel");
-    return WN_OK;
+    return grad_grid(tile, grid, GradDirectArgs{}, false, out_dev, as_stream(stream));
 }
 
 int wn_multiband3d_grad_grid(const wn_tile *tile, const wn_grid *grid, float s, int first_band, int nbands,
@@ -414,38 +343,7 @@ int wn_multiband3d_grad_grid(const wn_tile *tile, const wn_grid *grid, float s, 
     GradDirectArgs d{};
     rc = multiband_bands(s, first_band, nbands, w_host, var_per_band, &d);
     if (rc) return rc;
-    GridArgs g;
-    rc = check_grid(grid, true, &g);
-    if (rc) return rc;
-    const size_t total = (size_t)g.nx * g.ny * g.nz;
-    if (total == 0) return WN_OK;
-    if (!out_dev) return fail(WN_ERR_INVALID, "out_dev is NULL");
-    const hipStream_t st = as_stream(stream);
-    if (!(grid->flags & WN_GRID_EXACT) && d.nbands >= 1) {
-        // band b: q = p * (2 * 2^(first_band+b)); value factor w_b / out_div * out_scale, gradient factor that * 2 * 2^(..)
-        float qmul[kMaxBands], fv[kMaxBands], fg[kMaxBands];
-        for (int b = 0; b < d.nbands; ++b) {
-            qmul[b] = 2.0f * d.band_scale[b];
-            const double f = (double)d.band_w[b] / (double)d.out_div * (double)g.out_scale;
-            fv[b] = (float)f;
-            fg[b] = (float)(f * (double)qmul[b]);
-        }
-        if ((rc = grad_sep_try(tile, g, d.nbands, qmul, fv, fg, out_dev, st)) != kDeclined) return rc;
-    }
-    if (d.nbands == 0) {
-        // no band contributes: 0 (/ out_div) * out_scale in all four channels, evaluated on the device
-        d.nbands = 1;
-        d.band_scale[0] = 1.0f;
-        d.band_w[0] = 0.0f;
-    }
-    d.out = out_dev;
-    d.vol = total;
-    d.n = tile->n;
-    d.nmask = pow2_mask(tile->n);
-    d.g = g;
-    launch_grad_direct(d, tile, st);
-    WN_LAUNCH_CHECK("grad3d_grid_direct_kernel(multiband)");
-    return WN_OK;
+    return grad_grid(tile, grid, d, true, out_dev, as_stream(stream));
 }
 
 } // extern "C"

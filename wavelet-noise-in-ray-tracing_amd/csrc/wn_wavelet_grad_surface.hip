@@ -28,14 +28,9 @@
 namespace {
 
 using wn::GridArgs;
-using wn::kMaxBands;
-
-typedef float v4f __attribute__((ext_vector_type(4)));
-
-constexpr size_t kBlockCap = 256u * 8u * 8u; // workgroups of a grid-stride launch (wn::stride_blocks)
 
 // ---- point lists -----------------------------------------------------------------------------------------------------
-struct SurfPointsArgs {
+struct SurfPointsArgs : wn::Bands {
     const float *coef; // linear layout (n^2 or n^3, x fastest)
     int n, nmask;
     const float *pts;     // xy or xyz interleaved
@@ -43,11 +38,6 @@ struct SurfPointsArgs {
     float *out;           // 2-D: 3 floats per point; projected: 4 (16-byte aligned)
     size_t count;
     int one_normal;
-    // multiband (wn::multiband_bands)
-    int nbands;
-    float band_scale[kMaxBands], band_w[kMaxBands];
-    float out_div;
-    int apply_div;
 };
 
 __global__ __launch_bounds__(256) void grad2d_points_kernel(const SurfPointsArgs a)
@@ -102,10 +92,8 @@ __global__ __launch_bounds__(256) void grad2d_grid_kernel(const SurfGridArgs a)
     const GridArgs &g = a.g;
     const float den = (float)g.den;
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < a.vol; e += (size_t)gridDim.x * blockDim.x) {
-        const int x = (int)(e % g.nx), y = (int)(e / g.nx);
-        const float px = wn::lattice_coord(x, den, g.base_range, g.octave_scale, g.post_scale);
-        const float py = wn::lattice_coord(y, den, g.base_range, g.octave_scale, g.post_scale);
-        float gr[2];
+        float px, py, gr[2];
+        wn::lattice_point2d(g, den, e, px, py);
         const float v = wn::eval2d_exact<true>(a.coef, a.n, a.nmask, px, py, gr);
         a.out[e] = v * g.out_scale;
         a.out[e + a.vol] = gr[0] * g.out_scale;
@@ -118,14 +106,8 @@ __global__ __launch_bounds__(256) void grad_projected_grid_kernel(const SurfGrid
     const GridArgs &g = a.g;
     const float den = (float)g.den;
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < a.vol; e += (size_t)gridDim.x * blockDim.x) {
-        const int x = (int)(e % g.nx);
-        const size_t r = e / g.nx;
-        const int y = (int)(r % g.ny), z = (int)(r / g.ny);
-        const float p[3] = {wn::lattice_coord(x, den, g.base_range, g.octave_scale, g.post_scale),
-                            wn::lattice_coord(y, den, g.base_range, g.octave_scale, g.post_scale),
-                            g.z_const_mode ? g.z_const
-                                           : wn::lattice_coord(g.z0 + z, den, g.base_range, g.octave_scale, g.post_scale)};
-        float gr[3];
+        float p[3], gr[3];
+        wn::lattice_point(g, den, e, p);
         const float v = wn::projected_grad_exact(a.coef, a.n, a.nmask, p, a.normal, gr);
         a.out[e] = v * g.out_scale;
         a.out[e + a.vol] = gr[0] * g.out_scale;
@@ -170,7 +152,7 @@ int wn_eval2d_grad_points(const wn_tile *tile, const float *xy_dev, size_t n, fl
     if (rc || n == 0) return rc;
     const SurfPointsArgs a = surf_points_args(tile, xy_dev, nullptr, n, out3_dev);
     if ((rc = check_points(a, false)) != WN_OK) return rc;
-    hipLaunchKernelGGL(grad2d_points_kernel, dim3(wn::stride_blocks(n, kBlockCap)), dim3(256), 0, as_stream(stream), a);
+    hipLaunchKernelGGL(grad2d_points_kernel, dim3(wn::stride_blocks(n)), dim3(256), 0, as_stream(stream), a);
     WN_LAUNCH_CHECK("grad2d_points_kernel");
     return WN_OK;
 }
@@ -183,7 +165,7 @@ int wn_eval3d_projected_grad_points(const wn_tile *tile, const float *xyz_dev, c
     if (rc || n == 0) return rc;
     const SurfPointsArgs a = surf_points_args(tile, xyz_dev, normals_dev, n, out4_dev);
     if ((rc = check_points(a, true)) != WN_OK) return rc;
-    hipLaunchKernelGGL(grad_projected_points_kernel, dim3(wn::stride_blocks(n, kBlockCap)), dim3(256), 0, as_stream(stream), a);
+    hipLaunchKernelGGL(grad_projected_points_kernel, dim3(wn::stride_blocks(n)), dim3(256), 0, as_stream(stream), a);
     WN_LAUNCH_CHECK("grad_projected_points_kernel");
     return WN_OK;
 }
@@ -200,7 +182,7 @@ int wn_multiband3d_projected_grad_points(const wn_tile *tile, const float *xyz_d
     if (rc || n == 0) return rc;
     if ((rc = check_points(a, true)) != WN_OK) return rc;
     a.one_normal = one_normal ? 1 : 0;
-    hipLaunchKernelGGL(grad_multiband_projected_points_kernel, dim3(wn::stride_blocks(n, kBlockCap)), dim3(256), 0,
+    hipLaunchKernelGGL(grad_multiband_projected_points_kernel, dim3(wn::stride_blocks(n)), dim3(256), 0,
                        as_stream(stream), a);
     WN_LAUNCH_CHECK("grad_multiband_projected_points_kernel");
     return WN_OK;
@@ -224,7 +206,7 @@ int wn_eval2d_grad_grid(const wn_tile *tile, const wn_grid *grid, float *out_dev
     a.n = tile->n;
     a.nmask = pow2_mask(tile->n);
     a.g = g;
-    hipLaunchKernelGGL(grad2d_grid_kernel, dim3(wn::stride_blocks(total, kBlockCap)), dim3(256), 0, as_stream(stream), a);
+    hipLaunchKernelGGL(grad2d_grid_kernel, dim3(wn::stride_blocks(total)), dim3(256), 0, as_stream(stream), a);
     WN_LAUNCH_CHECK("grad2d_grid_kernel");
     return WN_OK;
 }
@@ -250,7 +232,7 @@ int wn_eval3d_projected_grad_grid(const wn_tile *tile, const wn_grid *grid, cons
     a.nmask = pow2_mask(tile->n);
     a.g = g;
     for (int i = 0; i < 3; ++i) a.normal[i] = normal[i];
-    hipLaunchKernelGGL(grad_projected_grid_kernel, dim3(wn::stride_blocks(total, kBlockCap)), dim3(256), 0,
+    hipLaunchKernelGGL(grad_projected_grid_kernel, dim3(wn::stride_blocks(total)), dim3(256), 0,
                        as_stream(stream), a);
     WN_LAUNCH_CHECK("grad_projected_grid_kernel");
     return WN_OK;

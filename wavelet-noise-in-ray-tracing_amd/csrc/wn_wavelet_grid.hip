@@ -34,8 +34,6 @@ namespace {
 
 using wn::GridArgs;
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-
 using wn::kMaxBands;
 constexpr int kBrickY = 8;    // sample rows per brick along y
 constexpr int kMaxBZ = 16;    // ... and along z (power of two: 16 for fine single-band lattices, 8, fewer for thin slabs)
@@ -478,17 +476,11 @@ __global__ __launch_bounds__(256 * XW) void grid3d_sep_kernel(const SepArgs a)
 // ------------------------------------------------------------------------------------------------
 // Direct kernels: the reference's loops, one sample per lane, unfused -> bit-identical.
 // ------------------------------------------------------------------------------------------------
-struct DirectArgs {
+struct DirectArgs : wn::Bands { // nbands == 0: plain evaluate3D
     const float *coef;
     float *out;
     int n, nmask;
     GridArgs g;
-    // multiband (nbands == 0: plain evaluate3D)
-    int nbands;
-    float band_scale[kMaxBands]; // 2^(first_band+b)
-    float band_w[kMaxBands];
-    float out_div;
-    int apply_div;
 };
 
 // (The band sum is wn::multiband_exact's, written out here with the coordinates in both arms: through the helper, or with the
@@ -501,28 +493,19 @@ __global__ __launch_bounds__(256) void grid3d_direct_kernel(const DirectArgs a)
     const float den = (float)g.den;
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total;
          e += (size_t)gridDim.x * blockDim.x) {
-        const int x = (int)(e % g.nx);
-        const size_t r = e / g.nx;
-        const int y = (int)(r % g.ny), z = (int)(r / g.ny);
-        float v;
+        int x, y, z;
+        wn::lattice_index(g, e, x, y, z);
+        float v, p[3];
         if (a.nbands == 0) {
-            const float px = wn::lattice_coord(x, den, g.base_range, g.octave_scale, g.post_scale);
-            const float py = wn::lattice_coord(y, den, g.base_range, g.octave_scale, g.post_scale);
-            const float pz = g.z_const_mode ? g.z_const
-                                            : wn::lattice_coord(g.z0 + z, den, g.base_range,
-                                                                g.octave_scale, g.post_scale);
-            v = wn::eval3d_exact<PADDED>(a.coef, a.n, a.nmask, px, py, pz);
+            wn::lattice_point(g, den, x, y, z, p);
+            v = wn::eval3d_exact<PADDED>(a.coef, a.n, a.nmask, p[0], p[1], p[2]);
         } else {
-            const float px = wn::lattice_coord(x, den, g.base_range, g.octave_scale, g.post_scale);
-            const float py = wn::lattice_coord(y, den, g.base_range, g.octave_scale, g.post_scale);
-            const float pz = g.z_const_mode ? g.z_const
-                                            : wn::lattice_coord(g.z0 + z, den, g.base_range,
-                                                                g.octave_scale, g.post_scale);
+            wn::lattice_point(g, den, x, y, z, p);
             v = 0.0f;
             for (int b = 0; b < a.nbands; ++b) {
                 const float s = a.band_scale[b];
-                v += a.band_w[b] * wn::eval3d_exact<PADDED>(a.coef, a.n, a.nmask, 2.0f * px * s,
-                                                2.0f * py * s, 2.0f * pz * s);
+                v += a.band_w[b] * wn::eval3d_exact<PADDED>(a.coef, a.n, a.nmask, 2.0f * p[0] * s,
+                                                2.0f * p[1] * s, 2.0f * p[2] * s);
             }
             if (a.apply_div) v /= a.out_div;
         }
@@ -538,9 +521,8 @@ __global__ __launch_bounds__(256) void grid2d_direct_kernel(const DirectArgs a)
     const int n = a.n;
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total;
          e += (size_t)gridDim.x * blockDim.x) {
-        const int x = (int)(e % g.nx), y = (int)(e / g.nx);
-        const float px = wn::lattice_coord(x, den, g.base_range, g.octave_scale, g.post_scale);
-        const float py = wn::lattice_coord(y, den, g.base_range, g.octave_scale, g.post_scale);
+        float px, py;
+        wn::lattice_point2d(g, den, e, px, py);
         const float result = wn::eval2d_exact(a.coef, n, a.nmask, px, py);
         a.out[e] = result * g.out_scale;
     }
@@ -565,15 +547,8 @@ __global__ __launch_bounds__(256) void grid3d_projected_kernel(const ProjGridArg
     const float den = (float)g.den;
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total;
          e += (size_t)gridDim.x * blockDim.x) {
-        const int x = (int)(e % g.nx);
-        const size_t r = e / g.nx;
-        const int y = (int)(r % g.ny), z = (int)(r / g.ny);
         float p[3];
-        p[0] = wn::lattice_coord(x, den, g.base_range, g.octave_scale, g.post_scale);
-        p[1] = wn::lattice_coord(y, den, g.base_range, g.octave_scale, g.post_scale);
-        p[2] = g.z_const_mode ? g.z_const
-                              : wn::lattice_coord(g.z0 + z, den, g.base_range, g.octave_scale,
-                                                  g.post_scale);
+        wn::lattice_point(g, den, e, p);
         a.out[e] = wn::projected_exact(a.coef, a.n, a.nmask, p, a.normal) * g.out_scale;
     }
 }

@@ -14,20 +14,14 @@
 
 namespace {
 
-using wn::kMaxBands;
 
-struct PointsArgs {
+struct PointsArgs : wn::Bands {
     const float *coef;
     int n, nmask;
     const float *pts;     // xyz (or xy) interleaved
     const float *normals; // projected only
     float *out;
     size_t count;
-    // multiband
-    int nbands;
-    float band_scale[kMaxBands], band_w[kMaxBands];
-    float out_div;
-    int apply_div;
     int one_normal; // multiband projected: `normals` holds ONE normal for all points
 };
 
@@ -633,8 +627,6 @@ int launch_sorted(const Ops &ops, hipStream_t stream)
     return WN_OK;
 }
 
-constexpr size_t kBlockCap = 256u * 8u * 8u; // workgroups of a grid-stride launch (wn::stride_blocks)
-
 // The tile's fields of PointsArgs (its padded copy for 3-D tiles that have one) and the point count.
 PointsArgs points_args(const wn_tile *tile, int dims, size_t n)
 {
@@ -674,9 +666,9 @@ int wn_eval3d_points(const wn_tile *tile, const float *xyz_dev, size_t n, float 
         return WN_OK;
     }
     if (tile->dev_padded)
-        hipLaunchKernelGGL(eval3d_points_kernel<true>, dim3(wn::stride_blocks(n, kBlockCap)), dim3(256), 0, as_stream(stream), a);
+        hipLaunchKernelGGL(eval3d_points_kernel<true>, dim3(wn::stride_blocks(n)), dim3(256), 0, as_stream(stream), a);
     else
-        hipLaunchKernelGGL(eval3d_points_kernel<false>, dim3(wn::stride_blocks(n, kBlockCap)), dim3(256), 0, as_stream(stream), a);
+        hipLaunchKernelGGL(eval3d_points_kernel<false>, dim3(wn::stride_blocks(n)), dim3(256), 0, as_stream(stream), a);
     WN_LAUNCH_CHECK("eval3d_points_kernel");
     return WN_OK;
 }
@@ -691,7 +683,7 @@ int wn_eval2d_points(const wn_tile *tile, const float *xy_dev, size_t n, float *
     PointsArgs a = points_args(tile, 2, n);
     a.pts = xy_dev;
     a.out = out_dev;
-    hipLaunchKernelGGL(eval2d_points_kernel, dim3(wn::stride_blocks(n, kBlockCap)), dim3(256), 0, as_stream(stream), a);
+    hipLaunchKernelGGL(eval2d_points_kernel, dim3(wn::stride_blocks(n)), dim3(256), 0, as_stream(stream), a);
     WN_LAUNCH_CHECK("eval2d_points_kernel");
     return WN_OK;
 }
@@ -709,7 +701,7 @@ int wn_eval3d_projected_points(const wn_tile *tile, const float *xyz_dev, const 
     a.pts = xyz_dev;
     a.normals = normals_dev;
     a.out = out_dev;
-    hipLaunchKernelGGL(eval3d_projected_points_kernel, dim3(wn::stride_blocks(n, kBlockCap)), dim3(256), 0,
+    hipLaunchKernelGGL(eval3d_projected_points_kernel, dim3(wn::stride_blocks(n)), dim3(256), 0,
                        as_stream(stream), a);
     WN_LAUNCH_CHECK("eval3d_projected_points_kernel");
     return WN_OK;
@@ -736,10 +728,10 @@ int wn_multiband3d_points(const wn_tile *tile, const float *xyz_dev, size_t n, f
         return WN_OK;
     }
     if (tile->dev_padded)
-        hipLaunchKernelGGL(multiband3d_points_kernel<true>, dim3(wn::stride_blocks(n, kBlockCap)), dim3(256), 0,
+        hipLaunchKernelGGL(multiband3d_points_kernel<true>, dim3(wn::stride_blocks(n)), dim3(256), 0,
                            as_stream(stream), a);
     else
-        hipLaunchKernelGGL(multiband3d_points_kernel<false>, dim3(wn::stride_blocks(n, kBlockCap)), dim3(256), 0,
+        hipLaunchKernelGGL(multiband3d_points_kernel<false>, dim3(wn::stride_blocks(n)), dim3(256), 0,
                            as_stream(stream), a);
     WN_LAUNCH_CHECK("multiband3d_points_kernel");
     return WN_OK;
@@ -762,7 +754,7 @@ int wn_multiband3d_projected_points(const wn_tile *tile, const float *xyz_dev, c
     a.normals = normals_dev;
     a.one_normal = one_normal ? 1 : 0;
     a.out = out_dev;
-    hipLaunchKernelGGL(multiband3d_projected_points_kernel, dim3(wn::stride_blocks(n, kBlockCap)), dim3(256), 0, as_stream(stream), a);
+    hipLaunchKernelGGL(multiband3d_projected_points_kernel, dim3(wn::stride_blocks(n)), dim3(256), 0, as_stream(stream), a);
     WN_LAUNCH_CHECK("multiband3d_projected_points_kernel");
     return WN_OK;
 }
