@@ -125,7 +125,18 @@ WN_API void wn_perm_destroy(wn_perm *p);
  * evaluated in float in exactly this order (experient/main.cpp:20-26, 47-54, 102-104).  With
  * z_mode == WN_Z_CONST the third coordinate is z_const for every sample ("sliced" generators,
  * experient/main.cpp:50-54, 122) and the slab is one plane thick.  Output index is
- * x + nx*(y + ny*(z - z0)), i.e. a contiguous z-slab of the volume (shard-friendly). */
+ * x + nx*(y + ny*(z - z0)), i.e. a contiguous z-slab of the volume (shard-friendly).
+ *
+ * Output placement (every grid entry point of this header, the gradient and curl grids included): out_dev needs only a
+ * float's alignment, and exactly the nx*ny*nz samples (times the channel count) are written -- nothing in front of, behind
+ * or, for several channels, between them beyond the channel volumes themselves.  An output that is not 16-byte aligned (or
+ * rows with nx % 4 != 0) is written with scalar stores; a kernel's bits do not depend on where its output lies.  For
+ * wn_eval3d_grid and wn_multiband3d_grid in the default tier the KERNEL does: an output that is not 16-byte aligned is
+ * served by the brick kernel where an aligned one gets the plane pipeline or the strip kernel, so default-tier results for
+ * differently aligned outputs agree to 1e-5 rather than bit for bit (WN_GRID_EXACT: bit for bit).  z-slabs of one volume
+ * with nx % 4 == 0 share their base's alignment (z0*ny*nx is a multiple of 4), and with nx % 4 != 0 no pointer is
+ * treated as aligned, so a sample's bits still do not depend on how the volume is cut into z-slabs, also when each slab
+ * is written in place at out + z0*ny*nx. */
 enum { WN_Z_LATTICE = 0, WN_Z_CONST = 1 };
 enum {
     WN_GRID_DEFAULT = 0,
@@ -168,7 +179,12 @@ WN_API int wn_perlin_turb_grid(const wn_perm *perm, const wn_grid *g, int depth,
 WN_API int wn_perlin_fractal_grid(const wn_perm *perm, const wn_grid *g, float *out_dev,
                                   void *stream);
 
-/* ---- point lists (the scalar API batched: one call = n calls of the reference member) ------- */
+/* ---- point lists (the scalar API batched: one call = n calls of the reference member) -------
+ * Placement (every point-list and texture entry point of this header): out_dev and the input lists (xyz_dev, xy_dev,
+ * normals_dev) need only their element's alignment -- a float's, a double's for the Perlin lists -- and packed records of 2
+ * or 3 elements need no more; the results do not depend on it.  The exceptions are the float4 and 4-double record outputs
+ * (out4_dev) of the gradient entry points below: 16-byte aligned, else WN_ERR_INVALID.  Exactly the n output records are
+ * written; with an `active_dev` mask exactly the active ones. */
 WN_API int wn_eval3d_points(const wn_tile *tile3d, const float *xyz_dev, size_t n, float *out_dev,
                             void *stream); /* evaluate3D, WaveletNoise.h:33 */
 WN_API int wn_eval2d_points(const wn_tile *tile2d, const float *xy_dev, size_t n, float *out_dev,

@@ -525,15 +525,15 @@ def generate2DOctaveBandNoise(imageSize, octave, outputFile, noise, flags=WN_GRI
     return out
 
 
-def generate3DSlicedOctaveBandNoise(imageSize, octave, outputFile, noise, flags=WN_GRID_EXACT):
+def generate3DSlicedOctaveBandNoise(imageSize, octave, outputFile, noise, flags=WN_GRID_EXACT, out=None):
     """Byte-identical to the reference's file by default (WN_GRID_EXACT); flags=WN_GRID_DEFAULT opts in
-    to the separable brick kernel (within 1e-5)."""
+    to the separable brick kernel (within 1e-5).  `out`: a flat float32 CUDA tensor to write into, as the volume helpers."""
     g = GridSpec(imageSize, imageSize, imageSize, octave_scale=_octave_scale(octave), post_scale=2.0,
                  z_mode=WN_Z_CONST, z_const=2.0, out_scale=_inv_stddev(0.18402), flags=flags)
-    out = g.empty()
+    out = g.empty(out)
     gc = g.c()
     check(_lib.wn_eval3d_grid(noise._handle(3), C.byref(gc), _ptr(out), _stream()))
-    out = out.view(imageSize, imageSize)
+    out = out[: imageSize * imageSize].view(imageSize, imageSize)
     _write(out, outputFile)
     return out
 
