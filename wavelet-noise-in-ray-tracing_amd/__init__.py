@@ -14,6 +14,7 @@ The directory name is not a Python identifier: import it with
 """
 from . import _capi
 from ._capi import WnError, wn_grid, WN_GRID_DEFAULT, WN_GRID_EXACT, WN_Z_CONST, WN_Z_LATTICE
+from ._capi import WN_PERLIN_CURL_NOISE, WN_PERLIN_CURL_TURB, WN_PERLIN_CURL_FRACTAL
 
 _capi.load()  # fail loudly when the HIP library is missing
 
@@ -23,18 +24,19 @@ from .noise import (  # noqa: E402
     generate3DProjectedOctaveBandNoise, generatePerlinNoise2D, generatePerlinNoise3DSliced,
     wavelet_volume, wavelet_volume_launcher, multiband_volume, perlin_volume, turb_volume, device_info, HipTimer,
     wavelet_gradient_volume, multiband_gradient_volume, wavelet2d_gradient_image, projected_gradient_volume,
-    perlin_gradient_volume, turb_gradient_volume, curl_volume, multiband_curl_volume,
+    perlin_gradient_volume, turb_gradient_volume, curl_volume, multiband_curl_volume, perlin_curl_volume,
 )
 from .shard import slab_bounds, gather_volume, NativeComm  # noqa: E402
 from . import formats  # noqa: E402
 
 __all__ = [
     "WnError", "wn_grid", "WN_GRID_DEFAULT", "WN_GRID_EXACT", "WN_Z_CONST", "WN_Z_LATTICE",
+    "WN_PERLIN_CURL_NOISE", "WN_PERLIN_CURL_TURB", "WN_PERLIN_CURL_FRACTAL",
     "WaveletNoise", "perlin", "PerlinNoise", "noise_texture", "wavelet_texture", "GridSpec",
     "generate2DOctaveBandNoise", "generate3DSlicedOctaveBandNoise",
     "generate3DProjectedOctaveBandNoise", "generatePerlinNoise2D", "generatePerlinNoise3DSliced",
     "wavelet_volume", "wavelet_volume_launcher", "multiband_volume", "perlin_volume", "turb_volume", "device_info",
     "HipTimer", "wavelet_gradient_volume", "multiband_gradient_volume", "wavelet2d_gradient_image",
     "projected_gradient_volume", "perlin_gradient_volume", "turb_gradient_volume", "curl_volume",
-    "multiband_curl_volume", "slab_bounds", "gather_volume", "NativeComm", "formats",
+    "multiband_curl_volume", "perlin_curl_volume", "slab_bounds", "gather_volume", "NativeComm", "formats",
 ]

@@ -1,4 +1,4 @@
-"""ctypes binding of libwnoise_hip.so (include/wnoise.h).
+"""ctypes binding of libwnoise_hip.so (include/wnoise.h, include/wnoise_perlin_curl.h).
 
 The library is the product: if it is missing or fails to load this module raises, it never
 substitutes a CPU implementation.
@@ -116,6 +116,14 @@ SIGNATURES = {
     "wn_scalar_shutdown": (_i, []),
 }
 
+# name -> (restype, argtypes); every symbol include/wnoise_perlin_curl.h declares (SIGNATURES mirrors include/wnoise.h alone).
+WN_PERLIN_CURL_NOISE, WN_PERLIN_CURL_TURB, WN_PERLIN_CURL_FRACTAL = range(3)
+PERLIN_CURL_SIGNATURES = {
+    "wn_perlin_curl_points": (_i, [_vp, _vp, _sz, _i32p, _vp, _vp]),
+    "wn_perlin_curl_points_vec3": (_i, [_vp, _vp, _sz, _i, _i, _i32p, _vp, _vp]),
+    "wn_perlin_curl_grid": (_i, [_vp, _gp, _i, _i, _i32p, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -129,7 +137,7 @@ def load():
             f"{LIB_PATH} is missing: build it with `make -C {HERE}` (or "
             "__graft_entry__.build()).  This package has no CPU implementation.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in (*SIGNATURES.items(), *PERLIN_CURL_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

@@ -645,6 +645,97 @@ WN_EVAL_FN double perlin_fractal_grad(const Table perm, float x, float y, float 
     return result / max_value;
 }
 
+// ---- curl of three Perlin potentials (include/wnoise_perlin_curl.h; absent from the reference) --------------------------
+// psi_k is noise / the signed turb sum / fractal_noise with the cell index shifted by off[3k .. 3k+2] (any integers, taken
+// & 255).  Of each potential's gradient two partials enter the curl; s holds the six in the order
+//     {d psi0/dy, d psi0/dz, d psi1/dx, d psi1/dz, d psi2/dx, d psi2/dy}.
+// One octave at the double point (x, y, z): floor, fractional parts, fade and fade' once, the hashes three times, each
+// partial from perlin_sample_grad's own expression (its value and the third partial are unused and not computed).
+// ADD: s += the octave's partials (turb, fractal_noise); else s = them (noise).
+template <bool ADD, typename Table>
+WN_EVAL_FN void perlin_curl_octave(const Table perm, double x, double y, double z, const int *off, double s[6])
+{
+    const double fx = floor(x), fy = floor(y), fz = floor(z);
+    const int X = (int)fx & 255, Y = (int)fy & 255, Z = (int)fz & 255;
+    x -= fx;
+    y -= fy;
+    z -= fz;
+    const double u = pfade(x), v = pfade(y), w = pfade(z);
+    const double du = pfade_d(x), dv = pfade_d(y), dw = pfade_d(z);
+    WN_UNROLL
+    for (int k = 0; k < 3; ++k) {
+        const int Xk = (X + (off[3 * k] & 255)) & 255, Yk = (Y + (off[3 * k + 1] & 255)) & 255,
+                  Zk = (Z + (off[3 * k + 2] & 255)) & 255;
+        const int A = perm[Xk] + Yk, AA = perm[A] + Zk, AB = perm[A + 1] + Zk;
+        const int B = perm[Xk + 1] + Yk, BA = perm[B] + Zk, BB = perm[B + 1] + Zk;
+        const int h[8] = {(int)perm[AA],     (int)perm[BA],     (int)perm[AB],     (int)perm[BB],
+                          (int)perm[AA + 1], (int)perm[BA + 1], (int)perm[AB + 1], (int)perm[BB + 1]};
+        const double a[8] = {pgrad(h[0], x, y, z),         pgrad(h[1], x - 1, y, z),
+                             pgrad(h[2], x, y - 1, z),     pgrad(h[3], x - 1, y - 1, z),
+                             pgrad(h[4], x, y, z - 1),     pgrad(h[5], x - 1, y, z - 1),
+                             pgrad(h[6], x, y - 1, z - 1), pgrad(h[7], x - 1, y - 1, z - 1)};
+        double P0[3], P1[3], g[3];
+        perlin_corner_blend(h, v, w, P0, P1);
+        perlin_sample_grad(a, u, v, w, du, dv, dw, P0, P1, g);
+        const double first = g[k == 0 ? 1 : 0], second = g[k == 2 ? 1 : 2];
+        s[2 * k] = ADD ? s[2 * k] + first : first;
+        s[2 * k + 1] = ADD ? s[2 * k + 1] + second : second;
+    }
+}
+
+// v = (d psi2/dy - d psi1/dz, d psi0/dz - d psi2/dx, d psi1/dx - d psi0/dy): one subtraction per component.
+WN_EVAL_FN void perlin_curl_of(const double s[6], double v[3])
+{
+    v[0] = s[5] - s[3];
+    v[1] = s[1] - s[4];
+    v[2] = s[2] - s[0];
+}
+
+// The curl of three perlin::noise potentials: each component has the bits of the subtraction of two perlin_grad_exact
+// channels on the shifted cells.
+template <typename Table>
+WN_EVAL_FN void perlin_curl_exact(const Table perm, double x, double y, double z, const int *off, double v[3])
+{
+    double s[6];
+    perlin_curl_octave<false>(perm, x, y, z, off, s);
+    perlin_curl_of(s, v);
+}
+
+// ... of three turb potentials WITHOUT the final fabs (|.| is not differentiable, and the curl of |S| is not
+// divergence-free where S = 0): psi_k = sum_i 2^-i noise_k(2^i p).  Each partial is the plain sum of the octaves' noise
+// partials in octave order, as in perlin_turb_grad, without its sign.  The offsets act on every octave's own cell index.
+// depth == 0: 0 in all three components.
+template <typename Table>
+WN_EVAL_FN void perlin_turb_curl(const Table perm, float x, float y, float z, int depth, const int *off, double v[3])
+{
+    double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int i = 0; i < depth; ++i) {
+        perlin_curl_octave<true>(perm, (double)x, (double)y, (double)z, off, s);
+        x *= 2.0f;
+        y *= 2.0f;
+        z *= 2.0f;
+    }
+    perlin_curl_of(s, v);
+}
+
+// ... of three fractal_noise potentials: each partial is (sum of the six octaves' noise partials) / max_value, as
+// perlin_fractal_grad forms it.
+template <typename Table>
+WN_EVAL_FN void perlin_fractal_curl(const Table perm, float x, float y, float z, const int *off, double v[3])
+{
+    double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    double amplitude = 1.0, frequency = 1.0, max_value = 0.0;
+    for (int i = 0; i < 6; ++i) {
+        perlin_curl_octave<true>(perm, x * frequency, y * frequency, z * frequency, off, s);
+        max_value += amplitude;
+        amplitude *= 0.5;
+        frequency *= 2.0;
+    }
+    WN_UNROLL
+    for (int j = 0; j < 6; ++j) s[j] = s[j] / max_value;
+    perlin_curl_of(s, v);
+}
+
 // ---- the texture adaptors' per-point arithmetic (texture.h:37-43, 67-107) ----------------------------------------------
 // wavelet_texture's coordinate scaling, texture.h:71-80: (float)(p * scale) * (octave_scale * 2.0f)
 template <typename A>

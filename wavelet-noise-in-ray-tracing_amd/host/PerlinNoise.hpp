@@ -9,6 +9,7 @@
 
 #include "scalar_eval.h"
 #include "wn_host.hpp"
+#include "wnoise_perlin_curl.h"
 
 class PerlinNoise {
   private:
@@ -47,8 +48,33 @@ class PerlinNoise {
         res.download(out4);
     }
 
+    // additive: the curl of three noise potentials on cells shifted by offsets9 (include/wnoise_perlin_curl.h; NULL:
+    // (0,0,0), (85,85,85), (170,170,170), a default only).  Scalar on the host, batched (n records {vx, vy, vz} of three
+    // doubles) through the GPU; bit-identical to each other.
+    void noise_curl(double x, double y, double z, double v[3], const int *offsets9 = nullptr) const
+    {
+        wnhost_perlin_curl(p.data(), x, y, z, curl_offsets(offsets9), v);
+    }
+    void noise_curl(const double *xyz, size_t n, double *out3, const int *offsets9 = nullptr) const
+    {
+        if (!n) return;
+        wnhost::DeviceBuffer in(3 * n * sizeof(double)), res(3 * n * sizeof(double));
+        in.upload(xyz);
+        static_assert(sizeof(int) == sizeof(int32_t), "offsets are int32");
+        wnhost::check(wn_perlin_curl_points(perm_, in.as<double>(), n, reinterpret_cast<const int32_t *>(curl_offsets(offsets9)),
+                                            res.as<double>(), nullptr), "wn_perlin_curl_points");
+        res.download(out3);
+    }
+
     const std::vector<int> &table() const { return p; }
     const wn_perm *perm() const { return perm_; }
+
+  private:
+    static const int *curl_offsets(const int *offsets9)
+    {
+        static const int o[9] = {0, 0, 0, 85, 85, 85, 170, 170, 170};
+        return offsets9 ? offsets9 : o;
+    }
 };
 
 #endif

@@ -5,7 +5,7 @@
 // wn_perm_create_seeded) and lives on the device as 512 bytes.  The batched forms run as HIP kernels in fp64 with the
 // reference's operation order; the scalar members are evaluated on the host from the mirrored table (scalar_eval.h;
 // WN_SCALAR_ON_DEVICE=1: by the resident scalar kernel).  Bit-identical either way.
-// Additive: turb() (RTOW; absent from the reference) and batched overloads.
+// Additive: turb() (RTOW; absent from the reference), batched overloads, analytic gradients and curl noise.
 #ifndef PERLIN_H
 #define PERLIN_H
 
@@ -16,6 +16,7 @@
 #include "scalar_eval.h"
 #include "vec3.h"
 #include "wn_host.hpp"
+#include "wnoise_perlin_curl.h"
 
 using point3 = vec3;
 
@@ -102,6 +103,43 @@ class perlin {
     void turb_gradient(const float *xyz, size_t n, double *out4, int depth = 7) const { grad_vec3(xyz, n, 1, depth, out4); }
     void fractal_noise_gradient(const float *xyz, size_t n, double *out4) const { grad_vec3(xyz, n, 2, 0, out4); }
 
+    // ---- additive: divergence-free curl noise (absent from the reference; include/wnoise_perlin_curl.h) ----------
+    // v = curl of the three potentials noise / the signed turb sum / fractal_noise on cells shifted by offsets9 (the
+    // (x, y, z) triples of psi0, psi1, psi2; NULL: default_curl_offsets(), a default only, not a measured
+    // decorrelation).  Scalar members: evaluated on the host, bit-identical to the kernels.
+    static const int *default_curl_offsets()
+    {
+        static const int o[9] = {0, 0, 0, 85, 85, 85, 170, 170, 170};
+        return o;
+    }
+    void noise_curl(double x, double y, double z, double v[3], const int *offsets9 = nullptr) const
+    {
+        wnhost_perlin_curl(p.data(), x, y, z, offsets9 ? offsets9 : default_curl_offsets(), v);
+    }
+    void noise_curl(const point3 &q, double v[3], const int *offsets9 = nullptr) const { noise_curl(q.x(), q.y(), q.z(), v, offsets9); }
+    void turb_curl(const point3 &q, double v[3], int depth = 7, const int *offsets9 = nullptr) const
+    {
+        const float xyz[3] = {q.x(), q.y(), q.z()};
+        wnhost_perlin_turb_curl(p.data(), xyz, depth, offsets9 ? offsets9 : default_curl_offsets(), v);
+    }
+    void fractal_noise_curl(const point3 &q, double v[3], const int *offsets9 = nullptr) const
+    {
+        const float xyz[3] = {q.x(), q.y(), q.z()};
+        wnhost_perlin_fractal_curl(p.data(), xyz, offsets9 ? offsets9 : default_curl_offsets(), v);
+    }
+    // Batched overloads (host pointers, through the GPU): n records {vx, vy, vz} of three doubles to out3.
+    void noise_curl(const double *xyz, size_t n, double *out3, const int *offsets9 = nullptr) const
+    {
+        if (!n) return;
+        wnhost::DeviceBuffer in(3 * n * sizeof(double)), res(3 * n * sizeof(double));
+        in.upload(xyz);
+        wnhost::check(wn_perlin_curl_points(perm_, in.as<double>(), n, curl_offsets(offsets9), res.as<double>(), nullptr), "wn_perlin_curl_points");
+        res.download(out3);
+    }
+    void noise_curl(const float *xyz, size_t n, double *out3, const int *offsets9 = nullptr) const { curl_vec3(xyz, n, WN_PERLIN_CURL_NOISE, 0, offsets9, out3); }
+    void turb_curl(const float *xyz, size_t n, double *out3, int depth = 7, const int *offsets9 = nullptr) const { curl_vec3(xyz, n, WN_PERLIN_CURL_TURB, depth, offsets9, out3); }
+    void fractal_noise_curl(const float *xyz, size_t n, double *out3, const int *offsets9 = nullptr) const { curl_vec3(xyz, n, WN_PERLIN_CURL_FRACTAL, 0, offsets9, out3); }
+
     const std::vector<int> &table() const { return p; }
     const wn_perm *perm() const { return perm_; }
 
@@ -115,6 +153,20 @@ class perlin {
         else if (kind == 1) wnhost::check(wn_perlin_turb_grad_points(perm_, in.as<float>(), n, depth, res.as<double>(), nullptr), "wn_perlin_turb_grad_points");
         else wnhost::check(wn_perlin_fractal_grad_points(perm_, in.as<float>(), n, res.as<double>(), nullptr), "wn_perlin_fractal_grad_points");
         res.download(out4);
+    }
+    static const int32_t *curl_offsets(const int *offsets9)
+    {
+        static_assert(sizeof(int) == sizeof(int32_t), "offsets are int32");
+        return reinterpret_cast<const int32_t *>(offsets9 ? offsets9 : default_curl_offsets());
+    }
+    void curl_vec3(const float *xyz, size_t n, int kind, int depth, const int *offsets9, double *out3) const
+    {
+        if (!n) return;
+        wnhost::DeviceBuffer in(3 * n * sizeof(float)), res(3 * n * sizeof(double));
+        in.upload(xyz);
+        wnhost::check(wn_perlin_curl_points_vec3(perm_, in.as<float>(), n, kind, depth, curl_offsets(offsets9), res.as<double>(), nullptr),
+                      "wn_perlin_curl_points_vec3");
+        res.download(out3);
     }
 };
 

@@ -95,6 +95,21 @@ double wnhost_perlin_turb_grad(const int *perm, const float q[3], int depth, dou
     return wn::perlin_turb_grad(perm, q[0], q[1], q[2], depth, grad);
 }
 
+void wnhost_perlin_curl(const int *perm, double x, double y, double z, const int offsets9[9], double v[3])
+{
+    wn::perlin_curl_exact(perm, x, y, z, offsets9, v);
+}
+
+void wnhost_perlin_turb_curl(const int *perm, const float q[3], int depth, const int offsets9[9], double v[3])
+{
+    wn::perlin_turb_curl(perm, q[0], q[1], q[2], depth, offsets9, v);
+}
+
+void wnhost_perlin_fractal_curl(const int *perm, const float q[3], const int offsets9[9], double v[3])
+{
+    wn::perlin_fractal_curl(perm, q[0], q[1], q[2], offsets9, v);
+}
+
 float wnhost_wavelet_texture_value(const float *coef, int n, int use_3d, double scale, int octave, const float xyz[3])
 {
     const float octave_scale = (float)std::pow(2.0, (double)octave); // std::pow(2.0f, int) is evaluated in double, :77

@@ -62,6 +62,14 @@ WNHOST_API double wnhost_perlin_turb(const int *perm, const float q[3], int dept
 WNHOST_API double wnhost_perlin_grad(const int *perm, double x, double y, double z, double grad[3]);
 WNHOST_API double wnhost_perlin_fractal_grad(const int *perm, const float q[3], double grad[3]);
 WNHOST_API double wnhost_perlin_turb_grad(const int *perm, const float q[3], int depth, double grad[3]);
+// The curl of three Perlin potentials (absent from the reference; include/wnoise_perlin_curl.h): psi_k is noise / the signed
+// turb sum (no fabs) / fractal_noise with the cell index shifted by offsets9[3k .. 3k+2] = (ox, oy, oz)_k (any integers, taken
+// & 255); writes v = (d psi2/dy - d psi1/dz, d psi0/dz - d psi2/dx, d psi1/dx - d psi0/dy) -- six of the partial sums the
+// gradient functions above form, at the shifted hashes, and one subtraction per component: the bits of
+// wn_perlin_curl_points / _points_vec3.  turb: depth == 0 -> 0 in all three.
+WNHOST_API void wnhost_perlin_curl(const int *perm, double x, double y, double z, const int offsets9[9], double v[3]);
+WNHOST_API void wnhost_perlin_turb_curl(const int *perm, const float q[3], int depth, const int offsets9[9], double v[3]);
+WNHOST_API void wnhost_perlin_fractal_curl(const int *perm, const float q[3], const int offsets9[9], double v[3]);
 // grey level of texture::value (texture.h); use_3d = 0: the 2-D tile and branch; coef == NULL: the no-tile grey
 WNHOST_API float wnhost_wavelet_texture_value(const float *coef, int n, int use_3d, double scale, int octave,
                                               const float xyz[3]);                    // texture.h:67-107

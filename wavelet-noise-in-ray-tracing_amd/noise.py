@@ -400,6 +400,49 @@ class perlin:
         return self._grad(_lib.wn_perlin_fractal_grad_points, _dev(p, torch.float32).reshape(-1, 3))
 
 
+    # -- divergence-free curl noise (absent from the reference; include/wnoise_perlin_curl.h): (N, 3) float64 CUDA
+    # tensors of {vx, vy, vz}
+    @staticmethod
+    def _curl_offsets(offsets):
+        """Nine int32: the (x, y, z) whole-cell offsets of the potentials psi0, psi1, psi2 (any integers, reduced
+        & 255).  None: (0, 0, 0), (85, 85, 85), (170, 170, 170) -- a default only, not a measured decorrelation."""
+        if offsets is None:
+            offsets = ((0, 0, 0), (85, 85, 85), (170, 170, 170))
+        flat = [int(v) for v in np.asarray(offsets, dtype=np.int64).reshape(-1)]
+        if len(flat) != 9:
+            raise ValueError("offsets: three (x, y, z) triples")
+        return (C.c_int32 * 9)(*flat)
+
+    def _curl(self, pts, kind, depth, offsets):
+        out = torch.empty((pts.shape[0], 3), dtype=torch.float64, device="cuda")
+        check(_lib.wn_perlin_curl_points_vec3(self._h, _ptr(pts), pts.shape[0], kind, int(depth), self._curl_offsets(offsets),
+                                              _ptr(out), _stream()))
+        return out
+
+    def noise_curl(self, p, offsets=None):
+        """The curl of the vector potential whose components are noise() on cells shifted by the whole-cell `offsets`,
+        at one point or an (N, 3) batch: v = (d psi2/dy - d psi1/dz, d psi0/dz - d psi2/dx, d psi1/dx - d psi0/dy),
+        divergence-free.  float64 input follows noise(double, double, double) (wn_perlin_curl_points), anything else
+        noise(const point3&) on floats (wn_perlin_curl_points_vec3).  Every component has the bits of the subtraction
+        of two noise_gradient channels at p + o_k wherever that addition is exact."""
+        is64 = (p.dtype == torch.float64) if isinstance(p, torch.Tensor) else (np.asarray(p).dtype == np.float64)
+        if not is64:
+            return self._curl(_dev(p, torch.float32).reshape(-1, 3), _capi.WN_PERLIN_CURL_NOISE, 0, offsets)
+        pts = _dev(p, torch.float64).reshape(-1, 3)
+        out = torch.empty((pts.shape[0], 3), dtype=torch.float64, device="cuda")
+        check(_lib.wn_perlin_curl_points(self._h, _ptr(pts), pts.shape[0], self._curl_offsets(offsets), _ptr(out), _stream()))
+        return out
+
+    def turb_curl(self, p, depth=7, offsets=None):
+        """noise_curl with the potentials sum_{i<depth} 2^-i noise_k(2^i p): turb's sum before its fabs (the curl of
+        |sum| is not divergence-free where the sum is 0).  The offsets are the same in every octave."""
+        return self._curl(_dev(p, torch.float32).reshape(-1, 3), _capi.WN_PERLIN_CURL_TURB, depth, offsets)
+
+    def fractal_noise_curl(self, p, offsets=None):
+        """noise_curl with fractal_noise potentials (six octaves)."""
+        return self._curl(_dev(p, torch.float32).reshape(-1, 3), _capi.WN_PERLIN_CURL_FRACTAL, 0, offsets)
+
+
 PerlinNoise = perlin  # experient/PerlinNoise.hpp is the same algorithm with an explicit seed
 
 
@@ -741,3 +784,19 @@ def turb_gradient_volume(perlin_obj, den, nx, ny, z0, z1, depth=7, out=None):
     gc = g.c()
     check(_lib.wn_perlin_turb_grad_grid(perlin_obj._h, C.byref(gc), int(depth), _ptr(out), _stream()))
     return out[: 4 * g.nz * ny * nx].view(4, g.nz, ny, nx)
+
+
+_PERLIN_CURL_KINDS = {"noise": _capi.WN_PERLIN_CURL_NOISE, "turb": _capi.WN_PERLIN_CURL_TURB,
+                      "fractal": _capi.WN_PERLIN_CURL_FRACTAL}
+
+
+def perlin_curl_volume(perlin_obj, den, nx, ny, z0, z1, octave, kind="noise", depth=7, offsets=None, out=None):
+    """perlin_volume's lattice p = (i/den)*4 * 2^octave (octave 0: turb_volume's) with the curl of three shifted Perlin
+    potentials (wn_perlin_curl_grid; `kind`: "noise", "turb" with `depth`, "fractal"; `offsets` as perlin.noise_curl):
+    [3, nz, ny, nx] -- vx, vy, vz, derivatives with respect to p."""
+    g = GridSpec(den, nx, ny, z0, z1, octave_scale=_octave_scale(octave))
+    out = _curl_out(g, out)
+    gc = g.c()
+    check(_lib.wn_perlin_curl_grid(perlin_obj._h, C.byref(gc), _PERLIN_CURL_KINDS[kind], int(depth),
+                                   perlin._curl_offsets(offsets), _ptr(out), _stream()))
+    return out[: 3 * g.nz * ny * nx].view(3, g.nz, ny, nx)
