@@ -5,9 +5,7 @@
 // The evaluators are wn_eval.hpp's perlin_curl_exact / perlin_turb_curl / perlin_fractal_curl: per point and octave the
 // lattice decode, fractional parts, fade and fade' once, the hashes per potential, six partials in perlin_sample_grad's
 // expressions, one subtraction per component.  fp64, contraction off: host and device return the same bits.
-#include "wn_internal.hpp"
-#include "wn_device_eval.hpp"
-#include "wn_perlin_run.hpp"
+#include "wn_perlin_frame.hpp"
 #include "wnoise_perlin_curl.h"
 
 #include <cmath>
@@ -15,21 +13,17 @@
 
 namespace {
 
-using wn::GridArgs;
-
-enum { kNoise = WN_PERLIN_CURL_NOISE, kTurb = WN_PERLIN_CURL_TURB, kFractal = WN_PERLIN_CURL_FRACTAL };
+using wn::GridArgs, wn::kNoise, wn::kTurb, wn::kFractal;
+using wn::kRunMaxDepth, wn::kRunTY, wn::kRunTZ, wn::RunAxisEntryD, wn::RunKEntry;
+static_assert(WN_PERLIN_CURL_NOISE == kNoise && WN_PERLIN_CURL_TURB == kTurb && WN_PERLIN_CURL_FRACTAL == kFractal,
+              "the public kinds are the kernels' kinds");
 
 struct CurlOffsets {
     int o[9]; // (x, y, z) of psi0, psi1, psi2, each in 0..255
 };
 
-struct PerlinCurlGridArgs {
-    const uint8_t *perm;
-    float *out; // three consecutive volumes: vx, vy, vz
-    GridArgs g;
+struct PerlinCurlGridArgs : wn::PerlinGridFrame { // out: three consecutive volumes: vx, vy, vz
     CurlOffsets off;
-    int kind, depth;
-    int vec4_ok; // rows of every channel start 16-byte aligned
 };
 
 __device__ __forceinline__ void curl_vec3(const uint8_t *perm, int kind, int depth, const int *off, float px, float py, float pz,
@@ -48,29 +42,17 @@ __global__ __launch_bounds__(256) void perlin_curl_grid_generic_kernel(const Per
     wn::load_perm_lds(s_perm, a.perm);
     const uint8_t *perm = s_perm;
     const GridArgs &g = a.g;
-    const float den = (float)g.den;
-    const unsigned plane = (unsigned)g.nx * (unsigned)g.ny;
-    const size_t total = (size_t)plane * g.nz;
-    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
-        const unsigned z = (unsigned)(e / plane);
-        const unsigned r = (unsigned)(e - (size_t)z * plane);
-        const unsigned y = r / (unsigned)g.nx, x = r - y * (unsigned)g.nx;
-        const float px = wn::lattice_coord((int)x, den, g.base_range, g.octave_scale, g.post_scale);
-        const float py = wn::lattice_coord((int)y, den, g.base_range, g.octave_scale, g.post_scale);
-        const float pz = g.z_const_mode ? g.z_const
-                                        : wn::lattice_coord(g.z0 + (int)z, den, g.base_range, g.octave_scale, g.post_scale);
+    wn::perlin_for_each_sample(g, [&](size_t e, size_t total, float px, float py, float pz) {
         double v[3];
         curl_vec3(perm, a.kind, a.depth, a.off.o, px, py, pz, v);
         a.out[e] = (float)v[0] * g.out_scale;
         a.out[total + e] = (float)v[1] * g.out_scale;
         a.out[2 * total + e] = (float)v[2] * g.out_scale;
-    }
+    });
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
-// perlin_curl_grid_run_kernel -- the cell-sharing organisation of perlin_grad_grid_run_kernel (wn_perlin_grad.hip: per-axis
-// tables of the block in LDS, a lane walks a run of consecutive x samples, corner state once per cell the run enters),
-// carrying three potentials.
+// perlin_curl_grid_run_kernel -- the run form of wn_perlin_frame.hpp carrying three potentials.
 // Built once per block and shared by the potentials: the x / y / z axis tables {f, fade, fade'} and the cell-index tables.
 // Built once per wave, row and octave and shared: the {K, mm, t} table (wn::run_k_entry depends on h & 15, dy, dz only).
 // Per potential and cell: the eight corner hashes at ((X + ox_k) & 255, (Y + oy_k) & 255, (Z + oz_k) & 255), their K / mm /
@@ -85,17 +67,9 @@ __global__ __launch_bounds__(256) void perlin_curl_grid_generic_kernel(const Per
 // 1-KiB wave store straight from registers -- the per-wave stage of the 8-sample gradient kernel would be the identity
 // here -- with scalar stores when rows are not 16-byte aligned and at the row tail.
 // ------------------------------------------------------------------------------------------------------------------------
-constexpr int kRunMaxDepth = 8;
 constexpr int kRun = 4;           // samples per lane and row
 constexpr int kRunX = 64 * kRun;  // x samples per workgroup
-constexpr int kRunTY = 8;         // rows ...
-constexpr int kRunTZ = 8;         // ... and planes per workgroup
 constexpr int kRunWaves = 8;
-
-struct RunAxisEntryD {
-    double f, fade, dfade; // fractional part, fade() and fade'()
-};
-using wn::RunKEntry;
 
 __host__ __device__ constexpr size_t curl_run_lds_bytes(int depth)
 {
@@ -109,7 +83,7 @@ __global__ __launch_bounds__(64 * kRunWaves) void perlin_curl_grid_run_kernel(co
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char run_lds[];
     const GridArgs &g = a.g;
-    const int depth = (KIND == kNoise) ? 1 : a.depth; // fractal_noise: the host passes its 6 octaves
+    const int depth = wn::run_depth<KIND>(a);
     // LDS carve-up (16-byte aligned members first)
     RunKEntry *const ktab_all = reinterpret_cast<RunKEntry *>(run_lds);                       // [waves][64]
     double *const xtab = reinterpret_cast<double *>(ktab_all + kRunWaves * 64);               // [depth][3 (f, fade, fade')][kRunX]
@@ -124,25 +98,12 @@ __global__ __launch_bounds__(64 * kRunWaves) void perlin_curl_grid_run_kernel(co
     const int x_first = blockIdx.x * kRunX, y_first = blockIdx.y * kRunTY, z_first = blockIdx.z * kRunTZ;
     const float den = (float)g.den;
 
-    // ---- per-axis tables of the block (wn_perlin_grad.hip's) -------------------------------------------------------
-    for (int i = tid; i < 128; i += 64 * kRunWaves)
-        reinterpret_cast<uint32_t *>(perm)[i] = reinterpret_cast<const uint32_t *>(a.perm)[i];
-    auto tabulate = [&](float p, auto store) {
-        float cur = p;          // turb: the float point doubles per octave
-        double frequency = 1.0; // fractal_noise: float point times a double frequency
-        for (int i = 0; i < depth; ++i) {
-            const double c = (KIND == kFractal) ? (double)p * frequency : (double)cur;
-            const double fl = floor(c);
-            store(i, (int)fl & 255, c - fl);
-            cur *= 2.0f;
-            frequency *= 2.0;
-        }
-    };
+    // ---- per-axis tables of the block, with fade' ---------------------------------------------------------------------
+    wn::run_load_perm(perm, a.perm, tid, 64 * kRunWaves);
     // x entries are stored [octave][member][q][lane] (sample x = lane * kRun + q): the 64 lanes of a wave read adjacent doubles
     for (int xi = tid; xi < kRunX; xi += 64 * kRunWaves) {
-        const int x = min(x_first + xi, g.nx - 1);
         const int slot = (xi & (kRun - 1)) * 64 + (xi / kRun);
-        tabulate(wn::lattice_coord(x, den, g.base_range, g.octave_scale, g.post_scale), [&](int i, int cell, double f) {
+        wn::run_octave_walk<KIND>(wn::run_coord(g, den, x_first + xi, g.nx), depth, [&](int i, int cell, double f) {
             double *const e = xtab + (size_t)i * 3 * kRunX + slot;
             e[0] = f;
             e[kRunX] = wn::pfade(f);
@@ -150,29 +111,12 @@ __global__ __launch_bounds__(64 * kRunWaves) void perlin_curl_grid_run_kernel(co
             xcell[(size_t)i * kRunX + xi] = (uint8_t)cell;
         });
     }
-    if (tid >= 256 && tid < 256 + kRunTY) {
-        const int yi = tid - 256;
-        const int y = min(y_first + yi, g.ny - 1);
-        tabulate(wn::lattice_coord(y, den, g.base_range, g.octave_scale, g.post_scale), [&](int i, int cell, double f) {
-            ytab[i * kRunTY + yi] = RunAxisEntryD{f, wn::pfade(f), wn::pfade_d(f)};
-            ycell[i * kRunTY + yi] = cell;
-        });
-    } else if (tid >= 320 && tid < 320 + kRunTZ) {
-        const int zi = tid - 320;
-        const int z = g.z0 + min(z_first + zi, g.nz - 1);
-        const float pz = g.z_const_mode ? g.z_const : wn::lattice_coord(z, den, g.base_range, g.octave_scale, g.post_scale);
-        tabulate(pz, [&](int i, int cell, double f) {
-            ztab[i * kRunTZ + zi] = RunAxisEntryD{f, wn::pfade(f), wn::pfade_d(f)};
-            zcell[i * kRunTZ + zi] = cell;
-        });
-    }
+    wn::run_tabulate_yz<KIND>(g, den, depth, y_first, z_first, tid, ytab, ztab, ycell, zcell);
     __syncthreads();
 
     RunKEntry *const ktab = ktab_all + wave * 64;
     const int rows_y = min(kRunTY, g.ny - y_first), rows_z = min(kRunTZ, g.nz - z_first);
     const size_t total = (size_t)g.nx * g.ny * g.nz;
-    // this lane's entry of the per-row table: hash h, corner (cy, cz)
-    const int kh = lane & 15, kcy = (lane >> 4) & 1, kcz = lane >> 5;
     for (int r = wave; r < rows_y * rows_z; r += kRunWaves) {
         const int yi = r % rows_y, zi = r / rows_y;
         double amp_sum = 0.0, weight = 1.0; // fractal_noise: max_value and the amplitude
@@ -188,13 +132,7 @@ __global__ __launch_bounds__(64 * kRunWaves) void perlin_curl_grid_run_kernel(co
         for (int oc = 0; oc < depth; ++oc) {
             const RunAxisEntryD ye = ytab[oc * kRunTY + yi], ze = ztab[oc * kRunTZ + zi];
             const int Y = ycell[oc * kRunTY + yi], Z = zcell[oc * kRunTZ + zi];
-            { // per-row table: entry (cy, cz, h) -> {K, mm, t} (grad(), perlin.h:26-31), the same for every potential
-                const double dy = kcy ? ye.f - 1.0 : ye.f, dz = kcz ? ze.f - 1.0 : ze.f;
-                const RunKEntry mine = wn::run_k_entry(kh, dy, dz);
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); // the previous octave's reads are done
-                ktab[lane] = mine;
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            }
+            wn::run_publish_ktab(ktab, lane, ye.f, ze.f); // the same table for every potential
             const double v = ye.fade, w = ze.fade, dv = ye.dfade, dw = ze.dfade;
             // the run's x entries, shared by the potentials
             const double *const xe = xtab + (size_t)oc * 3 * kRunX + lane;
@@ -227,29 +165,17 @@ __global__ __launch_bounds__(64 * kRunWaves) void perlin_curl_grid_run_kernel(co
                     double K[8], P0[3], P1[3];
                     uint32_t mm[8], tt[8];
                     {
-                        const int Xk = (X + a.off.o[3 * k]) & 255, Yk = (Y + a.off.o[3 * k + 1]) & 255,
-                                  Zk = (Z + a.off.o[3 * k + 2]) & 255;
-                        const int A = perm[Xk] + Yk, AA = perm[A] + Zk, AB = perm[A + 1] + Zk;
-                        const int B = perm[Xk + 1] + Yk, BA = perm[B] + Zk, BB = perm[B + 1] + Zk;
-                        const int h[8] = {perm[AA], perm[BA], perm[AB], perm[BB], perm[AA + 1], perm[BA + 1], perm[AB + 1], perm[BB + 1]};
-#pragma unroll
-                        for (int c = 0; c < 8; ++c) {
-                            const RunKEntry e = ktab[(c >> 1) * 16 + (h[c] & 15)];
-                            K[c] = e.K;
-                            mm[c] = e.mm;
-                            tt[c] = e.t;
-                        }
+                        int h[8];
+                        wn::run_hash_cell(perm, (X + a.off.o[3 * k]) & 255, (Y + a.off.o[3 * k + 1]) & 255,
+                                          (Z + a.off.o[3 * k + 2]) & 255, ktab, h, K, mm, tt);
                         __builtin_amdgcn_sched_barrier(0); // the corner blend's decoded components after the table fetch
                         wn::perlin_corner_blend(h, v, w, P0, P1);
                     }
 #pragma unroll
                     for (int q = 0; q < kRun; ++q) {
                         if (__any(in[q])) {
-                            const double xm1 = xf[q] - 1.0;
-                            const uint64_t b0 = (uint64_t)__double_as_longlong(xf[q]), b1 = (uint64_t)__double_as_longlong(xm1);
                             double gr[8], gn[3];
-#pragma unroll
-                            for (int c = 0; c < 8; ++c) gr[c] = wn::run_gradient(K[c], mm[c], tt[c], (c & 1) ? b1 : b0);
+                            wn::run_corner_gradients(K, mm, tt, xf[q], gr);
                             wn::perlin_sample_grad(gr, xu[q], v, w, xdu[q], dv, dw, P0, P1, gn);
                             const double first = gn[k == 0 ? 1 : 0], second = gn[k == 2 ? 1 : 2];
                             double &sa = s[2 * k][q], &sb = s[2 * k + 1][q];
@@ -290,15 +216,8 @@ __global__ __launch_bounds__(64 * kRunWaves) void perlin_curl_grid_run_kernel(co
         const int xo = lane * kRun;
         float *const row = a.out + ((size_t)(z_first + zi) * g.ny + (y_first + yi)) * g.nx + x_first + xo;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            float *const dst = row + (size_t)c * total;
-            if (a.vec4_ok && x_first + xo + 4 <= g.nx) *reinterpret_cast<v4f *>(dst) = v4f{fin[c][0], fin[c][1], fin[c][2], fin[c][3]};
-            else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (x_first + xo + e < g.nx) dst[e] = fin[c][e];
-            }
-        }
+        for (int c = 0; c < 3; ++c)
+            wn::run_store4(row + (size_t)c * total, 0, a.vec4_ok, x_first + xo, g.nx, v4f{fin[c][0], fin[c][1], fin[c][2], fin[c][3]});
     }
 }
 
@@ -333,8 +252,6 @@ __global__ __launch_bounds__(256) void perlin_curl_points_kernel(const PerlinCur
     }
 }
 
-constexpr size_t kBlockCap = 256u * 8u * 8u; // workgroups of a grid-stride launch (wn::stride_blocks)
-
 int check_kind(int kind, int depth)
 {
     if (kind < kNoise || kind > kFractal) return wn::fail(WN_ERR_INVALID, "kind must be 0 (noise), 1 (turb) or 2 (fractal_noise)");
@@ -354,39 +271,16 @@ int perlin_curl_grid(const wn_perm *perm, const wn_grid *grid, int kind, int dep
 {
     int rc = check_kind(kind, depth);
     if (rc) return rc;
-    rc = wn::check_perm(perm, "perlin curl grid");
-    if (rc) return rc;
-    GridArgs g;
-    rc = wn::check_grid(grid, true, &g);
-    if (rc) return rc;
-    const size_t total = (size_t)g.nx * g.ny * g.nz;
-    if (total == 0) return WN_OK;
-    if (!out_dev) return wn::fail(WN_ERR_INVALID, "out_dev is NULL");
+    PerlinCurlGridArgs a;
+    if (!wn::perlin_grid_frame(perm, grid, kind, depth, out_dev, "perlin curl grid", &a, &rc)) return rc;
     if (!offsets9_host) return wn::fail(WN_ERR_INVALID, "offsets9_host is NULL");
-    if ((size_t)g.nx * g.ny > 0xffffffffull) return wn::fail(WN_ERR_INVALID, "plane too large");
-    PerlinCurlGridArgs a{perm->dev, out_dev, g, reduce_offsets(offsets9_host), kind, depth, 0};
-    a.vec4_ok = wn::vec4_ok(out_dev, g.nx); // nx % 4 == 0: every channel volume starts 16-byte aligned too
-    const int octaves = kind == kNoise ? 1 : (kind == kFractal ? 6 : depth);
-    if (kind == kFractal) a.depth = octaves;
-    const dim3 rgrid((g.nx + kRunX - 1) / kRunX, (g.ny + kRunTY - 1) / kRunTY, (g.nz + kRunTZ - 1) / kRunTZ);
-    // the run kernel: rows of >= 128 samples, 1..8 octaves (the gradient's rule)
-    if (g.nx >= 128 && octaves >= 1 && octaves <= kRunMaxDepth && rgrid.y <= 65535u && rgrid.z <= 65535u) {
-        const size_t lds = curl_run_lds_bytes(octaves);
-        const void *fn = kind == kNoise  ? reinterpret_cast<const void *>(&perlin_curl_grid_run_kernel<kNoise>)
-                         : kind == kTurb ? reinterpret_cast<const void *>(&perlin_curl_grid_run_kernel<kTurb>)
-                                         : reinterpret_cast<const void *>(&perlin_curl_grid_run_kernel<kFractal>);
-        if (lds <= 48 * 1024 || wn::ensure_dynamic_lds(fn, wn::current_device(), curl_run_lds_bytes(kRunMaxDepth))) {
-            void *params[] = {&a};
-            const hipError_t e = hipLaunchKernel(fn, rgrid, dim3(64 * kRunWaves), params, lds, wn::as_stream(stream));
-            if (e != hipSuccess) return wn::hip_fail(e, "perlin_curl_grid_run_kernel");
-            WN_LAUNCH_CHECK("perlin_curl_grid_run_kernel");
-            return WN_OK;
-        }
-    }
-    hipLaunchKernelGGL(perlin_curl_grid_generic_kernel, dim3(wn::stride_blocks(total, kBlockCap)), dim3(256), 0,
-                       wn::as_stream(stream), a);
-    WN_LAUNCH_CHECK("perlin_curl_grid_generic_kernel");
-    return WN_OK;
+    a.off = reduce_offsets(offsets9_host);
+    const void *fn = kind == kNoise  ? reinterpret_cast<const void *>(&perlin_curl_grid_run_kernel<kNoise>)
+                     : kind == kTurb ? reinterpret_cast<const void *>(&perlin_curl_grid_run_kernel<kTurb>)
+                                     : reinterpret_cast<const void *>(&perlin_curl_grid_run_kernel<kFractal>);
+    return wn::perlin_grid_launch(a, kRunX, fn, curl_run_lds_bytes(a.depth), curl_run_lds_bytes(kRunMaxDepth), 64 * kRunWaves,
+                                  "perlin_curl_grid_run_kernel", reinterpret_cast<const void *>(&perlin_curl_grid_generic_kernel),
+                                  "perlin_curl_grid_generic_kernel", stream);
 }
 
 int perlin_curl_points(const wn_perm *perm, const double *p64, const float *p32, size_t n, int kind, int depth,
@@ -399,7 +293,7 @@ int perlin_curl_points(const wn_perm *perm, const double *p64, const float *p32,
     if ((!p64 && !p32) || !out3_dev) return wn::fail(WN_ERR_INVALID, "points/out pointer is NULL");
     if (!offsets9_host) return wn::fail(WN_ERR_INVALID, "offsets9_host is NULL");
     PerlinCurlPointsArgs a{perm->dev, p64, p32, out3_dev, n, reduce_offsets(offsets9_host), kind, depth};
-    hipLaunchKernelGGL(perlin_curl_points_kernel, dim3(wn::stride_blocks(n, kBlockCap)), dim3(256), 0, wn::as_stream(stream), a);
+    hipLaunchKernelGGL(perlin_curl_points_kernel, dim3(wn::stride_blocks(n)), dim3(256), 0, wn::as_stream(stream), a);
     WN_LAUNCH_CHECK("perlin_curl_points_kernel");
     return WN_OK;
 }

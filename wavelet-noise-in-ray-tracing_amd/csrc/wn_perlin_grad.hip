@@ -4,25 +4,16 @@
 // The evaluators are wn_eval.hpp's perlin_grad_exact / perlin_turb_grad / perlin_fractal_grad: the value channel is
 // perlin_exact's arithmetic (the bits of the value kernels of wn_perlin.hip, which this file leaves alone), the gradient
 // blends the corner vectors over z, then y, and over x last.  fp64, contraction off: host and device return the same bits.
-#include "wn_internal.hpp"
-#include "wn_device_eval.hpp"
-#include "wn_perlin_run.hpp"
+#include "wn_perlin_frame.hpp"
 
 #include <cmath>
 
 namespace {
 
-using wn::GridArgs;
+using wn::GridArgs, wn::kNoise, wn::kTurb, wn::kFractal;
+using wn::kRunMaxDepth, wn::kRunTY, wn::kRunTZ, wn::RunAxisEntry, wn::RunAxisEntryD, wn::RunKEntry;
 
-enum { kNoise = 0, kTurb = 1, kFractal = 2 };
-
-struct PerlinGradGridArgs {
-    const uint8_t *perm;
-    float *out; // four consecutive volumes: value, d/dx, d/dy, d/dz
-    GridArgs g;
-    int kind, depth;
-    int vec4_ok; // rows of every channel start 16-byte aligned
-};
+struct PerlinGradGridArgs : wn::PerlinGridFrame {}; // out: four consecutive volumes: value, d/dx, d/dy, d/dz
 
 __device__ __forceinline__ double grad_vec3(const uint8_t *perm, int kind, int depth, float px, float py, float pz, double g[3])
 {
@@ -39,30 +30,18 @@ __global__ __launch_bounds__(256) void perlin_grad_grid_generic_kernel(const Per
     wn::load_perm_lds(s_perm, a.perm);
     const uint8_t *perm = s_perm;
     const GridArgs &g = a.g;
-    const float den = (float)g.den;
-    const unsigned plane = (unsigned)g.nx * (unsigned)g.ny;
-    const size_t total = (size_t)plane * g.nz;
-    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
-        const unsigned z = (unsigned)(e / plane);
-        const unsigned r = (unsigned)(e - (size_t)z * plane);
-        const unsigned y = r / (unsigned)g.nx, x = r - y * (unsigned)g.nx;
-        const float px = wn::lattice_coord((int)x, den, g.base_range, g.octave_scale, g.post_scale);
-        const float py = wn::lattice_coord((int)y, den, g.base_range, g.octave_scale, g.post_scale);
-        const float pz = g.z_const_mode ? g.z_const
-                                        : wn::lattice_coord(g.z0 + (int)z, den, g.base_range, g.octave_scale, g.post_scale);
+    wn::perlin_for_each_sample(g, [&](size_t e, size_t total, float px, float py, float pz) {
         double gr[3];
         const double v = grad_vec3(perm, a.kind, a.depth, px, py, pz, gr);
         a.out[e] = (float)v * g.out_scale;
         a.out[total + e] = (float)gr[0] * g.out_scale;
         a.out[2 * total + e] = (float)gr[1] * g.out_scale;
         a.out[3 * total + e] = (float)gr[2] * g.out_scale;
-    }
+    });
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
-// perlin_grad_grid_run_kernel -- the cell-sharing organisation of perlin_grid_run_kernel (wn_perlin.hip: per-axis tables
-// of the block in LDS, a lane walks a run of 8 consecutive x samples, corner hashes and the per-row {K, mm, t} table once
-// per cell the run enters), carrying the gradient:
+// perlin_grad_grid_run_kernel -- the run form of wn_perlin_frame.hpp carrying the gradient:
 //   * the axis tables gain fade'(f) per entry;
 //   * per cell and row the lane decodes the eight corner vectors from the hashes it already has and blends them over z,
 //     then y: the six constants P0_k, P1_k (wn::perlin_corner_blend);
@@ -76,20 +55,9 @@ __global__ __launch_bounds__(256) void perlin_grad_grid_generic_kernel(const Per
 // A finished row leaves channel by channel through a 2-KB stage per wave (fp32, x order): four contiguous 2-KiB wave
 // stores, one per channel volume.
 // ------------------------------------------------------------------------------------------------------------------------
-constexpr int kRunMaxDepth = 8;
 constexpr int kRunX = 512; // x samples per workgroup (64 lanes x 8)
-constexpr int kRunTY = 8;  // rows ...
-constexpr int kRunTZ = 8;  // ... and planes per workgroup
 constexpr int kRun = 8;    // samples per lane and row
 constexpr int kRunWaves = 8;
-
-struct RunAxisEntry {
-    double f, fade; // fractional part and its fade()
-};
-struct RunAxisEntryD {
-    double f, fade, dfade; // ... and fade'()
-};
-using wn::RunKEntry;
 
 __host__ __device__ constexpr size_t grad_run_lds_bytes(int depth)
 {
@@ -103,7 +71,7 @@ __global__ __launch_bounds__(64 * kRunWaves) void perlin_grad_grid_run_kernel(co
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char run_lds[];
     const GridArgs &g = a.g;
-    const int depth = (KIND == kNoise) ? 1 : a.depth; // fractal_noise: the host passes its 6 octaves
+    const int depth = wn::run_depth<KIND>(a);
     // LDS carve-up (16-byte aligned members first)
     RunKEntry *const ktab_all = reinterpret_cast<RunKEntry *>(run_lds);                    // [waves][64]
     RunAxisEntry *const xtab = reinterpret_cast<RunAxisEntry *>(ktab_all + kRunWaves * 64); // [depth][512]
@@ -120,53 +88,24 @@ __global__ __launch_bounds__(64 * kRunWaves) void perlin_grad_grid_run_kernel(co
     const int x_first = blockIdx.x * kRunX, y_first = blockIdx.y * kRunTY, z_first = blockIdx.z * kRunTZ;
     const float den = (float)g.den;
 
-    // ---- per-axis tables of the block (wn_perlin.hip's, plus fade') -------------------------------------------------
-    for (int i = tid; i < 128; i += 64 * kRunWaves)
-        reinterpret_cast<uint32_t *>(perm)[i] = reinterpret_cast<const uint32_t *>(a.perm)[i];
-    auto tabulate = [&](float p, auto store) {
-        float cur = p;          // turb: the float point doubles per octave
-        double frequency = 1.0; // fractal_noise: float point times a double frequency
-        for (int i = 0; i < depth; ++i) {
-            const double c = (KIND == kFractal) ? (double)p * frequency : (double)cur;
-            const double fl = floor(c);
-            store(i, (int)fl & 255, c - fl);
-            cur *= 2.0f;
-            frequency *= 2.0;
-        }
-    };
+    // ---- per-axis tables of the block, with fade' ---------------------------------------------------------------------
+    wn::run_load_perm(perm, a.perm, tid, 64 * kRunWaves);
     // x entries are stored [octave][q][lane] (sample x = lane*8 + q): the 64 lanes of a wave read adjacent entries
     for (int xi = tid; xi < kRunX; xi += 64 * kRunWaves) {
-        const int x = min(x_first + xi, g.nx - 1);
         const int slot = (xi & (kRun - 1)) * 64 + (xi >> 3);
-        tabulate(wn::lattice_coord(x, den, g.base_range, g.octave_scale, g.post_scale), [&](int i, int cell, double f) {
-            xtab[(size_t)i * kRunX + slot] = RunAxisEntry{f, wn::pfade(f)};
+        wn::run_octave_walk<KIND>(wn::run_coord(g, den, x_first + xi, g.nx), depth, [&](int i, int cell, double f) {
+            xtab[(size_t)i * kRunX + slot] = RunAxisEntry::of(f);
             xdf[(size_t)i * kRunX + slot] = wn::pfade_d(f);
             xcell[(size_t)i * kRunX + xi] = (uint8_t)cell;
         });
     }
-    if (tid < kRunTY) {
-        const int y = min(y_first + tid, g.ny - 1);
-        tabulate(wn::lattice_coord(y, den, g.base_range, g.octave_scale, g.post_scale), [&](int i, int cell, double f) {
-            ytab[i * kRunTY + tid] = RunAxisEntryD{f, wn::pfade(f), wn::pfade_d(f)};
-            ycell[i * kRunTY + tid] = cell;
-        });
-    } else if (tid >= 64 && tid < 64 + kRunTZ) {
-        const int zi = tid - 64;
-        const int z = g.z0 + min(z_first + zi, g.nz - 1);
-        const float pz = g.z_const_mode ? g.z_const : wn::lattice_coord(z, den, g.base_range, g.octave_scale, g.post_scale);
-        tabulate(pz, [&](int i, int cell, double f) {
-            ztab[i * kRunTZ + zi] = RunAxisEntryD{f, wn::pfade(f), wn::pfade_d(f)};
-            zcell[i * kRunTZ + zi] = cell;
-        });
-    }
+    wn::run_tabulate_yz<KIND>(g, den, depth, y_first, z_first, tid, ytab, ztab, ycell, zcell);
     __syncthreads();
 
     RunKEntry *const ktab = ktab_all + wave * 64;
     float *const stage = stage_all + wave * kRunX;
     const int rows_y = min(kRunTY, g.ny - y_first), rows_z = min(kRunTZ, g.nz - z_first);
     const size_t total = (size_t)g.nx * g.ny * g.nz;
-    // this lane's entry of the per-row table: hash h, corner (cy, cz)
-    const int kh = lane & 15, kcy = (lane >> 4) & 1, kcz = lane >> 5;
     for (int r = wave; r < rows_y * rows_z; r += kRunWaves) {
         const int yi = r % rows_y, zi = r / rows_y;
         double amp_sum = 0.0, weight = 1.0; // fractal max_value / turb weight, fractal amplitude
@@ -179,13 +118,7 @@ __global__ __launch_bounds__(64 * kRunWaves) void perlin_grad_grid_run_kernel(co
         for (int oc = 0; oc < depth; ++oc) {
             const RunAxisEntryD ye = ytab[oc * kRunTY + yi], ze = ztab[oc * kRunTZ + zi];
             const int Y = ycell[oc * kRunTY + yi], Z = zcell[oc * kRunTZ + zi];
-            { // per-row table: entry (cy, cz, h) -> {K, mm, t} (grad(), perlin.h:26-31)
-                const double dy = kcy ? ye.f - 1.0 : ye.f, dz = kcz ? ze.f - 1.0 : ze.f;
-                const RunKEntry mine = wn::run_k_entry(kh, dy, dz);
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); // the previous octave's reads are done
-                ktab[lane] = mine;
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            }
+            wn::run_publish_ktab(ktab, lane, ye.f, ze.f);
             const double v = ye.fade, w = ze.fade, dv = ye.dfade, dw = ze.dfade;
             const RunAxisEntry *const xe = xtab + (size_t)oc * kRunX + lane; // entry q at xe[q * 64]
             const double *const xd = xdf + (size_t)oc * kRunX + lane;
@@ -195,27 +128,16 @@ __global__ __launch_bounds__(64 * kRunWaves) void perlin_grad_grid_run_kernel(co
             double K[8], P0[3], P1[3];
             uint32_t mm[8], tt[8];
             auto hash_cell = [&](int X) {
-                const int A = perm[X] + Y, AA = perm[A] + Z, AB = perm[A + 1] + Z;
-                const int B = perm[X + 1] + Y, BA = perm[B] + Z, BB = perm[B + 1] + Z;
-                const int h[8] = {perm[AA], perm[BA], perm[AB], perm[BB], perm[AA + 1], perm[BA + 1], perm[AB + 1], perm[BB + 1]};
-#pragma unroll
-                for (int c = 0; c < 8; ++c) {
-                    const RunKEntry e = ktab[(c >> 1) * 16 + (h[c] & 15)];
-                    K[c] = e.K;
-                    mm[c] = e.mm;
-                    tt[c] = e.t;
-                }
+                int h[8];
+                wn::run_hash_cell(perm, X, Y, Z, ktab, h, K, mm, tt);
                 __builtin_amdgcn_sched_barrier(0); // the corner blend's 24 decoded components after the table fetch
                 wn::perlin_corner_blend(h, v, w, P0, P1);
             };
             // one sample; `in`: this lane's sample belongs to the cell that is hashed (else its channels stay)
             auto sample = [&](bool in, double &qv, double &qx, double &qy, double &qz, const RunAxisEntry &x, double du) {
-                const double xf = x.f, u = x.fade, xm1 = xf - 1.0;
-                const uint64_t b0 = (uint64_t)__double_as_longlong(xf), b1 = (uint64_t)__double_as_longlong(xm1);
                 double gr[8], gn[3];
-#pragma unroll
-                for (int c = 0; c < 8; ++c) gr[c] = wn::run_gradient(K[c], mm[c], tt[c], (c & 1) ? b1 : b0);
-                const double nv = wn::perlin_sample_grad(gr, u, v, w, du, dv, dw, P0, P1, gn);
+                wn::run_corner_gradients(K, mm, tt, x.f, gr);
+                const double nv = wn::perlin_sample_grad(gr, x.fade, v, w, du, dv, dw, P0, P1, gn);
                 if (KIND == kNoise) {
                     qv = in ? nv : qv;
                     qx = in ? gn[0] : qx;
@@ -280,7 +202,6 @@ __global__ __launch_bounds__(64 * kRunWaves) void perlin_grad_grid_run_kernel(co
             __builtin_amdgcn_sched_barrier(0); // one sample's four divisions at a time
         }
         // each channel's row leaves as contiguous wave stores through the wave's stage (x order)
-        typedef float v4f __attribute__((ext_vector_type(4)));
         float *const row = a.out + ((size_t)(z_first + zi) * g.ny + (y_first + yi)) * g.nx + x_first;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
@@ -292,13 +213,7 @@ __global__ __launch_bounds__(64 * kRunWaves) void perlin_grad_grid_run_kernel(co
 #pragma unroll
             for (int half = 0; half < 2; ++half) {
                 const int xo = half * 256 + lane * 4;
-                const v4f val = *reinterpret_cast<const v4f *>(stage + xo);
-                if (a.vec4_ok && x_first + xo + 4 <= g.nx) *reinterpret_cast<v4f *>(dst + xo) = val;
-                else {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        if (x_first + xo + e < g.nx) dst[xo + e] = val[e];
-                }
+                wn::run_store4(dst, xo, a.vec4_ok, x_first, g.nx, *reinterpret_cast<const v4f *>(stage + xo));
             }
         }
     }
@@ -334,42 +249,17 @@ __global__ __launch_bounds__(256) void perlin_grad_points_kernel(const PerlinGra
     }
 }
 
-constexpr size_t kBlockCap = 256u * 8u * 8u; // workgroups of a grid-stride launch (wn::stride_blocks)
-
 int perlin_grad_grid(const wn_perm *perm, const wn_grid *grid, int kind, int depth, float *out_dev, void *stream)
 {
-    int rc = wn::check_perm(perm, "perlin gradient grid");
-    if (rc) return rc;
-    GridArgs g;
-    rc = wn::check_grid(grid, true, &g);
-    if (rc) return rc;
-    const size_t total = (size_t)g.nx * g.ny * g.nz;
-    if (total == 0) return WN_OK;
-    if (!out_dev) return wn::fail(WN_ERR_INVALID, "out_dev is NULL");
-    if ((size_t)g.nx * g.ny > 0xffffffffull) return wn::fail(WN_ERR_INVALID, "plane too large");
-    PerlinGradGridArgs a{perm->dev, out_dev, g, kind, depth, 0};
-    a.vec4_ok = wn::vec4_ok(out_dev, g.nx); // nx % 4 == 0: every channel volume starts 16-byte aligned too
-    const int octaves = kind == kNoise ? 1 : (kind == kFractal ? 6 : depth);
-    if (kind == kFractal) a.depth = octaves;
-    const dim3 rgrid((g.nx + kRunX - 1) / kRunX, (g.ny + kRunTY - 1) / kRunTY, (g.nz + kRunTZ - 1) / kRunTZ);
-    // the run kernel: rows of >= 128 samples (a lane owns 8 consecutive x samples), 1..8 octaves
-    if (g.nx >= 128 && octaves >= 1 && octaves <= kRunMaxDepth && rgrid.y <= 65535u && rgrid.z <= 65535u) {
-        const size_t lds = grad_run_lds_bytes(octaves);
-        const void *fn = kind == kNoise  ? reinterpret_cast<const void *>(&perlin_grad_grid_run_kernel<kNoise>)
-                         : kind == kTurb ? reinterpret_cast<const void *>(&perlin_grad_grid_run_kernel<kTurb>)
-                                         : reinterpret_cast<const void *>(&perlin_grad_grid_run_kernel<kFractal>);
-        if (lds <= 48 * 1024 || wn::ensure_dynamic_lds(fn, wn::current_device(), grad_run_lds_bytes(kRunMaxDepth))) {
-            void *params[] = {&a};
-            const hipError_t e = hipLaunchKernel(fn, rgrid, dim3(64 * kRunWaves), params, lds, wn::as_stream(stream));
-            if (e != hipSuccess) return wn::hip_fail(e, "perlin_grad_grid_run_kernel");
-            WN_LAUNCH_CHECK("perlin_grad_grid_run_kernel");
-            return WN_OK;
-        }
-    }
-    hipLaunchKernelGGL(perlin_grad_grid_generic_kernel, dim3(wn::stride_blocks(total, kBlockCap)), dim3(256), 0,
-                       wn::as_stream(stream), a);
-    WN_LAUNCH_CHECK("perlin_grad_grid_generic_kernel");
-    return WN_OK;
+    int rc;
+    PerlinGradGridArgs a;
+    if (!wn::perlin_grid_frame(perm, grid, kind, depth, out_dev, "perlin gradient grid", &a, &rc)) return rc;
+    const void *fn = kind == kNoise  ? reinterpret_cast<const void *>(&perlin_grad_grid_run_kernel<kNoise>)
+                     : kind == kTurb ? reinterpret_cast<const void *>(&perlin_grad_grid_run_kernel<kTurb>)
+                                     : reinterpret_cast<const void *>(&perlin_grad_grid_run_kernel<kFractal>);
+    return wn::perlin_grid_launch(a, kRunX, fn, grad_run_lds_bytes(a.depth), grad_run_lds_bytes(kRunMaxDepth), 64 * kRunWaves,
+                                  "perlin_grad_grid_run_kernel", reinterpret_cast<const void *>(&perlin_grad_grid_generic_kernel),
+                                  "perlin_grad_grid_generic_kernel", stream);
 }
 
 int perlin_grad_points(const wn_perm *perm, const double *p64, const float *p32, size_t n, int kind, int depth,
@@ -380,7 +270,7 @@ int perlin_grad_points(const wn_perm *perm, const double *p64, const float *p32,
     if ((!p64 && !p32) || !out4_dev) return wn::fail(WN_ERR_INVALID, "points/out pointer is NULL");
     if (reinterpret_cast<uintptr_t>(out4_dev) & 15) return wn::fail(WN_ERR_INVALID, "out4_dev must be 16-byte aligned");
     PerlinGradPointsArgs a{perm->dev, p64, p32, out4_dev, n, kind, depth};
-    hipLaunchKernelGGL(perlin_grad_points_kernel, dim3(wn::stride_blocks(n, kBlockCap)), dim3(256), 0, wn::as_stream(stream), a);
+    hipLaunchKernelGGL(perlin_grad_points_kernel, dim3(wn::stride_blocks(n)), dim3(256), 0, wn::as_stream(stream), a);
     WN_LAUNCH_CHECK("perlin_grad_points_kernel");
     return WN_OK;
 }
