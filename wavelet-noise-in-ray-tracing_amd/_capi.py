@@ -1,4 +1,4 @@
-"""ctypes binding of libwnoise_hip.so (include/wnoise.h, include/wnoise_perlin_curl.h).
+"""ctypes binding of libwnoise_hip.so (include/wnoise.h, include/wnoise_perlin_curl.h, include/wnoise_footprint.h).
 
 The library is the product: if it is missing or fails to load this module raises, it never
 substitutes a CPU implementation.
@@ -124,6 +124,16 @@ PERLIN_CURL_SIGNATURES = {
     "wn_perlin_curl_grid": (_i, [_vp, _gp, _i, _i, _i32p, _vp, _vp]),
 }
 
+# name -> (restype, argtypes); every symbol include/wnoise_footprint.h declares.
+_fp = C.POINTER(C.c_float)
+FOOTPRINT_SIGNATURES = {
+    "wn_multiband3d_footprint_points": (_i, [_vp, _vp, _vp, _sz, _i, _i, _fp, _f, _i, _vp, _vp]),
+    "wn_multiband3d_projected_footprint_points": (_i, [_vp, _vp, _vp, _i, _vp, _sz, _i, _i, _fp, _f, _i, _vp, _vp]),
+    "wn_multiband3d_footprint_grad_points": (_i, [_vp, _vp, _vp, _sz, _i, _i, _fp, _f, _i, _vp, _vp]),
+    "wn_multiband3d_projected_footprint_grad_points": (_i, [_vp, _vp, _vp, _i, _vp, _sz, _i, _i, _fp, _f, _i, _vp, _vp]),
+    "wn_wavelet_multiband_texture_points": (_i, [_vp, _d, _i, _i, _fp, _f, _i, _vp, _vp, _vp, _sz, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -137,7 +147,7 @@ def load():
             f"{LIB_PATH} is missing: build it with `make -C {HERE}` (or "
             "__graft_entry__.build()).  This package has no CPU implementation.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in (*SIGNATURES.items(), *PERLIN_CURL_SIGNATURES.items()):
+    for name, (res, args) in (*SIGNATURES.items(), *PERLIN_CURL_SIGNATURES.items(), *FOOTPRINT_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

@@ -333,6 +333,93 @@ WN_EVAL_FN float multiband_exact(const A &a, const float p[3], const float *nrm,
     return v;
 }
 
+// ---- WMultibandNoise with a footprint per sample (include/wnoise_footprint.h) -------------------------------------------
+// The paper's loop stops at the first band with s + firstBand + b >= 0, s = log2 of the SAMPLE's footprint: here s is an
+// argument of the evaluation, not of the call.  FootprintBands carries what does not depend on the sample: all nbands
+// bands (band_scale[b] = 2^(first_band+b), band_w[b] = w[b], unfaded), first_band as a float, the fade switch, and the
+// division of multiband_exact -- out_div = sqrtf(sum over ALL nbands of w^2 * var_per_band), applied when that sum is
+// non-zero, whatever the sample's own band count.
+constexpr int kFootprintMaxBands = 8;
+struct FootprintBands {
+    int nbands; // all of them: the sample's s decides how many run
+    float first_f;
+    int fade;
+    float band_scale[kFootprintMaxBands], band_w[kFootprintMaxBands];
+    float out_div;
+    int apply_div;
+};
+
+// nbands in 0 .. kFootprintMaxBands and w valid (or nbands == 0): the callers check.
+inline void footprint_bands_fill(int first_band, int nbands, const float *w, float var_per_band, int fade, FootprintBands *a)
+{
+    float variance = 0.0f;
+    for (int b = 0; b < nbands; ++b) variance += w[b] * w[b];
+    a->nbands = nbands;
+    a->first_f = (float)first_band;
+    a->fade = fade ? 1 : 0;
+    for (int b = 0; b < nbands; ++b) {
+        a->band_scale[b] = ldexpf(1.0f, first_band + b);
+        a->band_w[b] = w[b];
+    }
+    a->apply_div = variance != 0.0f;
+    a->out_div = a->apply_div ? sqrtf(variance * var_per_band) : 1.0f;
+}
+
+// t_b = (s + first_band) + b, in this association: the expression wn::multiband_bands evaluates.  Band b runs iff t_b < 0
+// (a NaN or +inf s: no band; -inf: all of them); t_b does not decrease with b, so the first band that fails ends the loop.
+template <typename A>
+WN_EVAL_FN float footprint_t(const A &a, float s, int b)
+{
+    return (s + a.first_f) + (float)b;
+}
+
+// multiband_exact with the band limit taken from the sample's footprint s.  Band b runs while t_b < 0 and enters with the
+// one float product wb = w[b] * f_b: f_b = 1.0f without fade (the paper's hard cut), fminf(1.0f, -t_b) with it -- the
+// finest surviving band fades in linearly over one octave of footprint instead of popping.  The value adds wb * e_b, the
+// gradient (wb * (2 * 2^(first_band+b))) * grad e_b; the fade does not depend on p, so that is the gradient of the faded
+// sum.  Band order, the unfused arithmetic and the division are multiband_exact's: where f_b == 1 for every band that runs
+// (every sample without fade; with it, integer-valued s) the bits are those of multiband_exact at s.  No band: 0 (divided
+// like any other sum).  `a` carries coef, n, nmask and a FootprintBands.
+template <bool PADDED, bool PROJECTED, bool GRAD, typename A>
+WN_EVAL_FN float multiband_footprint_exact(const A &a, const float p[3], const float *nrm, float s, float *g)
+{
+    float v = 0.0f, gx = 0.0f, gy = 0.0f, gz = 0.0f;
+    for (int b = 0; b < a.nbands; ++b) {
+        const float t = footprint_t(a, s, b);
+        if (!(t < 0.0f)) break;
+        const float wb = a.band_w[b] * (a.fade ? fminf(1.0f, -t) : 1.0f);
+        const float bs = a.band_scale[b];
+        const float q[3] = {2.0f * p[0] * bs, 2.0f * p[1] * bs, 2.0f * p[2] * bs};
+        if constexpr (GRAD) {
+            float gb[3];
+            const float e = PROJECTED ? projected_grad_exact(a.coef, a.n, a.nmask, q, nrm, gb)
+                                      : eval3d_grad_exact<PADDED>(a.coef, a.n, a.nmask, q[0], q[1], q[2], gb);
+            v += wb * e;
+            const float f = wb * (2.0f * bs);
+            gx += f * gb[0];
+            gy += f * gb[1];
+            gz += f * gb[2];
+        } else {
+            v += wb * (PROJECTED ? projected_exact(a.coef, a.n, a.nmask, q, nrm)
+                                 : eval3d_exact<PADDED>(a.coef, a.n, a.nmask, q[0], q[1], q[2]));
+        }
+    }
+    if (a.apply_div) {
+        v /= a.out_div;
+        if constexpr (GRAD) {
+            gx /= a.out_div;
+            gy /= a.out_div;
+            gz /= a.out_div;
+        }
+    }
+    if constexpr (GRAD) {
+        g[0] = gx;
+        g[1] = gy;
+        g[2] = gz;
+    }
+    return v;
+}
+
 // ---- curl of a vector potential of three whole-cell shifts of one tile (absent from the reference) ---------------------
 // Psi = (psi0, psi1, psi2), psi_k = evaluate3D of the tile T_k[z][y][x] = C[Mod(z+oz_k)][Mod(y+oy_k)][Mod(x+ox_k)];
 // v = curl Psi = (d psi2/dy - d psi1/dz, d psi0/dz - d psi2/dx, d psi1/dx - d psi0/dy).  The shifts are whole cells, so the
@@ -770,6 +857,17 @@ WN_EVAL_FN float wavelet_texture_value(const A &a, float px, float py, float pz)
         v *= (double)a.inv_stddev;
     }
     return wavelet_texture_grey(v);
+}
+
+// wavelet_multiband_texture (absent from the reference): texture.h:71-75's coordinate without the octave multiply,
+// pos = (float)((double)p * scale) per axis; WMultibandNoise(pos, s) as multiband_footprint_exact forms it, promoted to
+// double; wavelet_texture's grey level.  s is the footprint in noise space (after scale).  An empty tile: 0.5.
+// `a` carries coef, n, nmask, a FootprintBands and scale (double).
+template <bool PADDED, typename A>
+WN_EVAL_FN float wavelet_multiband_texture_value(const A &a, float px, float py, float pz, float s)
+{
+    const float pos[3] = {(float)((double)px * a.scale), (float)((double)py * a.scale), (float)((double)pz * a.scale)};
+    return wavelet_texture_grey((double)multiband_footprint_exact<PADDED, false, false>(a, pos, nullptr, s, nullptr));
 }
 
 // noise_texture::value, texture.h:37-43: scaled_p = p * scale * octave_scale in float (vec3 * float,

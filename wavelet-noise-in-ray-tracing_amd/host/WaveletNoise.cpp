@@ -8,6 +8,7 @@
 
 #include "scalar_eval.h"
 #include "wn_host.hpp"
+#include "wnoise_footprint.h"
 
 using wnhost::check;
 
@@ -216,6 +217,75 @@ void WaveletNoise::WMultibandNoiseGradient(const float *xyz, const float *normal
     check(wn_multiband3d_projected_grad_points(tile(3), in.as<float>(), nr.as<float>(), oneNormal ? 1 : 0, n, sarg,
                                                firstBand, nbands, w, variance, res.as<float>(), nullptr),
           "wn_multiband3d_projected_grad_points");
+    res.download(out4);
+}
+
+// ---- WMultibandNoise with a footprint per sample (include/wnoise_footprint.h): the scalar members on the host
+// (bit-identical to the kernels), the batched ones on the device; a 2-D tile goes to the C ABI, which reports it
+float WaveletNoise::WMultibandNoise(const float p[3], float sarg, bool fade, const float *normal, int firstBand, int nbands,
+                                    const float *w, float variance) const
+{
+    if (tileDims != 2)
+        return wnhost_multiband3d_footprint(noiseCoefficients.empty() ? nullptr : noiseCoefficients.data(), tileSizeN, p,
+                                            normal, sarg, fade ? 1 : 0, firstBand, nbands, w, variance, nullptr);
+    float out = 0.0f;
+    WMultibandNoise(p, normal, true, 1, &sarg, fade, firstBand, nbands, w, variance, &out);
+    return out;
+}
+
+float WaveletNoise::WMultibandNoiseGradient(const float p[3], float sarg, bool fade, const float *normal, int firstBand,
+                                            int nbands, const float *w, float grad[3], float variance) const
+{
+    if (tileDims != 2)
+        return wnhost_multiband3d_footprint(noiseCoefficients.empty() ? nullptr : noiseCoefficients.data(), tileSizeN, p,
+                                            normal, sarg, fade ? 1 : 0, firstBand, nbands, w, variance, grad);
+    float out4[4];
+    WMultibandNoiseGradient(p, normal, true, 1, &sarg, fade, firstBand, nbands, w, variance, out4);
+    std::copy(out4 + 1, out4 + 4, grad);
+    return out4[0];
+}
+
+void WaveletNoise::WMultibandNoise(const float *xyz, const float *normals, bool oneNormal, size_t n, const float *sarg,
+                                   bool fade, int firstBand, int nbands, const float *w, float variance, float *out) const
+{
+    if (!n) return;
+    wnhost::DeviceBuffer in(3 * n * sizeof(float)), fp(n * sizeof(float)), res(n * sizeof(float));
+    in.upload(xyz);
+    fp.upload(sarg);
+    if (!normals) {
+        check(wn_multiband3d_footprint_points(tile(3), in.as<float>(), fp.as<float>(), n, firstBand, nbands, w, variance,
+                                              fade ? 1 : 0, res.as<float>(), nullptr), "wn_multiband3d_footprint_points");
+    } else {
+        wnhost::DeviceBuffer nr(3 * (oneNormal ? 1 : n) * sizeof(float));
+        nr.upload(normals);
+        check(wn_multiband3d_projected_footprint_points(tile(3), in.as<float>(), nr.as<float>(), oneNormal ? 1 : 0,
+                                                        fp.as<float>(), n, firstBand, nbands, w, variance, fade ? 1 : 0,
+                                                        res.as<float>(), nullptr),
+              "wn_multiband3d_projected_footprint_points");
+    }
+    res.download(out);
+}
+
+void WaveletNoise::WMultibandNoiseGradient(const float *xyz, const float *normals, bool oneNormal, size_t n,
+                                           const float *sarg, bool fade, int firstBand, int nbands, const float *w,
+                                           float variance, float *out4) const
+{
+    if (!n) return;
+    wnhost::DeviceBuffer in(3 * n * sizeof(float)), fp(n * sizeof(float)), res(4 * n * sizeof(float));
+    in.upload(xyz);
+    fp.upload(sarg);
+    if (!normals) {
+        check(wn_multiband3d_footprint_grad_points(tile(3), in.as<float>(), fp.as<float>(), n, firstBand, nbands, w, variance,
+                                                   fade ? 1 : 0, res.as<float>(), nullptr),
+              "wn_multiband3d_footprint_grad_points");
+    } else {
+        wnhost::DeviceBuffer nr(3 * (oneNormal ? 1 : n) * sizeof(float));
+        nr.upload(normals);
+        check(wn_multiband3d_projected_footprint_grad_points(tile(3), in.as<float>(), nr.as<float>(), oneNormal ? 1 : 0,
+                                                             fp.as<float>(), n, firstBand, nbands, w, variance,
+                                                             fade ? 1 : 0, res.as<float>(), nullptr),
+              "wn_multiband3d_projected_footprint_grad_points");
+    }
     res.download(out4);
 }
 

@@ -90,6 +90,21 @@ class WaveletNoise {
                                   float grad[3], float variance = 0.296f) const;
     void WMultibandNoiseGradient(const float *xyz, const float *normals, bool oneNormal, size_t n, float s, int firstBand,
                                  int nbands, const float *w, float variance, float *out4) const;
+    // WMultibandNoise with the band limit taken from a footprint PER SAMPLE (include/wnoise_footprint.h; absent from the
+    // reference): band b of a sample runs while (s + firstBand) + b < 0, s = log2 of that sample's footprint, with the
+    // weight w[b] (fade == false: the paper's hard cut) or w[b] * min(1, -((s + firstBand) + b)) (fade: the finest
+    // surviving band fades in over one octave of footprint).  The batched forms take one s per point and optional normals
+    // (nullptr: bands are evaluate3D; else evaluate3DProjected with one normal per point, or one for all when oneNormal)
+    // and run on the device (wn_multiband3d[_projected]_footprint[_grad]_points); out4: records {value, d/dx, d/dy, d/dz}.
+    // The scalar members are evaluated on the host (wnhost_multiband3d_footprint), bit-identical to the kernels.
+    float WMultibandNoise(const float p[3], float s, bool fade, const float *normal, int firstBand, int nbands,
+                          const float *w, float variance) const;
+    float WMultibandNoiseGradient(const float p[3], float s, bool fade, const float *normal, int firstBand, int nbands,
+                                  const float *w, float grad[3], float variance) const;
+    void WMultibandNoise(const float *xyz, const float *normals, bool oneNormal, size_t n, const float *s, bool fade,
+                         int firstBand, int nbands, const float *w, float variance, float *out) const;
+    void WMultibandNoiseGradient(const float *xyz, const float *normals, bool oneNormal, size_t n, const float *s, bool fade,
+                                 int firstBand, int nbands, const float *w, float variance, float *out4) const;
     // Divergence-free curl noise (absent from the reference; include/wnoise.h): the curl of the vector potential whose
     // components are evaluate3D (WMultibandNoiseCurl: WMultibandNoise, normal == NULL) of this tile shifted by the whole-cell
     // offsets offsets9 = (x, y, z) of psi0, psi1, psi2; nullptr: defaultCurlOffsets().  evaluate3DCurl(p, ., v) is

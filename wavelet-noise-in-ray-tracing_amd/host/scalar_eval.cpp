@@ -18,6 +18,25 @@ struct WaveletTexture { // what wn::wavelet_texture_value reads
     float octave_mul, inv_stddev;
 };
 
+struct Footprint : wn::FootprintBands { // what wn::multiband_footprint_exact and the texture adaptor read
+    const float *coef;
+    int n, nmask;
+    double scale;
+};
+
+// false: nothing to evaluate (nbands out of range)
+bool footprint_setup(Footprint &a, const float *coef, int n, int first_band, int nbands, const float *w, float var_per_band,
+                     int fade)
+{
+    if (nbands < 0 || nbands > wn::kFootprintMaxBands || (nbands && !w)) return false;
+    wn::footprint_bands_fill(first_band, nbands, w, var_per_band, fade, &a);
+    a.coef = coef;
+    a.n = (coef && n > 0) ? n : 0;
+    a.nmask = wn::pow2_mask(a.n);
+    a.scale = 1.0;
+    return true;
+}
+
 } // namespace
 
 extern "C" {
@@ -69,6 +88,28 @@ float wnhost_eval3d_projected_grad(const float *coef, int n, const float p[3], c
     grad[0] = grad[1] = grad[2] = 0.0f;
     if (!coef || n <= 0) return 0.0f;
     return wn::projected_grad_exact(coef, n, wn::pow2_mask(n), p, nrm, grad);
+}
+
+float wnhost_multiband3d_footprint(const float *coef, int n, const float p[3], const float *normal, float s, int fade,
+                                   int first_band, int nbands, const float *w, float var_per_band, float *grad)
+{
+    if (grad) grad[0] = grad[1] = grad[2] = 0.0f;
+    Footprint a;
+    if (!footprint_setup(a, coef, n, first_band, nbands, w, var_per_band, fade)) return 0.0f;
+    if (normal)
+        return grad ? wn::multiband_footprint_exact<false, true, true>(a, p, normal, s, grad)
+                    : wn::multiband_footprint_exact<false, true, false>(a, p, normal, s, nullptr);
+    return grad ? wn::multiband_footprint_exact<false, false, true>(a, p, nullptr, s, grad)
+                : wn::multiband_footprint_exact<false, false, false>(a, p, nullptr, s, nullptr);
+}
+
+float wnhost_wavelet_multiband_texture_value(const float *coef, int n, double scale, int first_band, int nbands,
+                                             const float *w, float var_per_band, int fade, const float xyz[3], float s)
+{
+    Footprint a;
+    if (!footprint_setup(a, coef, n, first_band, nbands, w, var_per_band, fade)) return wn::wavelet_texture_grey(0.0);
+    a.scale = scale;
+    return wn::wavelet_multiband_texture_value<false>(a, xyz[0], xyz[1], xyz[2], s);
 }
 
 double wnhost_perlin(const int *perm, double x, double y, double z) { return wn::perlin_exact(perm, x, y, z); }

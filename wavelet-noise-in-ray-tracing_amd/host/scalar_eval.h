@@ -50,6 +50,21 @@ WNHOST_API float wnhost_eval3d_projected(const float *coef, int n, const float p
 // box to grad (include/wnoise.h): the bits of wn_eval3d_projected_grad_points.  n == 0 or coef == NULL -> 0 in all four.
 WNHOST_API float wnhost_eval3d_projected_grad(const float *coef, int n, const float p[3], const float normal[3],
                                               float grad[3]);
+// WMultibandNoise (Cook & DeRose Appendix 2) at ONE footprint s (absent from the reference; include/wnoise_footprint.h):
+// band b runs while t_b = (s + first_band) + b < 0 and enters with the weight w[b] * f_b, f_b = 1 (fade == 0: the paper's
+// hard cut) or fminf(1, -t_b) (fade != 0); normal_or_null != NULL makes every band evaluate3DProjected; the sum is
+// divided by sqrtf(sum over all nbands of w^2 * var_per_band) when that sum is non-zero.  Returns the value;
+// grad_or_null != NULL also receives the gradient with respect to p (the value's bits do not change).  The first host
+// evaluator of a multiband function: the bits of wn_multiband3d_footprint_points and its twins, and -- where every
+// f_b == 1 -- of wn_multiband3d_points at s.  n == 0, coef == NULL or nbands outside 0..8 -> 0 in every channel.
+WNHOST_API float wnhost_multiband3d_footprint(const float *coef, int n, const float p[3], const float *normal_or_null,
+                                              float s, int fade, int first_band, int nbands, const float *w,
+                                              float var_per_band, float *grad_or_null);
+// grey level of wavelet_multiband_texture::value (texture.h; wn_wavelet_multiband_texture_points): the function above
+// (normal == NULL) at (float)((double)xyz * scale) and footprint s, through wavelet_texture's grey; coef == NULL: 0.5
+WNHOST_API float wnhost_wavelet_multiband_texture_value(const float *coef, int n, double scale, int first_band, int nbands,
+                                                        const float *w, float var_per_band, int fade, const float xyz[3],
+                                                        float s);
 // `perm`: the 512-entry table (perlin.h:34-39)
 WNHOST_API double wnhost_perlin(const int *perm, double x, double y, double z);      // perlin.h:42-62
 WNHOST_API double wnhost_perlin_fractal(const int *perm, const float q[3]);           // perlin.h:75-90

@@ -10,13 +10,16 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <limits>
 #include <memory>
+#include <vector>
 
 #include "WaveletNoise.h"
 #include "perlin.h"
 #include "scalar_eval.h"
 #include "vec3.h"
 #include "wn_host.hpp"
+#include "wnoise_footprint.h"
 
 using color = vec3;
 using point3 = vec3;
@@ -149,6 +152,59 @@ class wavelet_texture : public texture {
     double scale;
     int octave_level;
     bool use_3d_noise;
+};
+
+// WMultibandNoise as a texture, band-limited by each hit's footprint (absent from the reference; Cook & DeRose Appendix 2,
+// include/wnoise_footprint.h): pos = (float)(p * scale) per axis, n = WMultibandNoise(pos, s, NULL, firstBand, nbands, w)
+// normalised with `variance`, grey = 0.5 * (1 + clamp(n / 4, -1, 1)) as wavelet_texture.  s is the log2 of the hit's
+// footprint in noise space (after scale); band b runs while (s + firstBand) + b < 0, and with `fade` the finest surviving
+// band fades in over one octave.  value() is one sample on the host at the default footprint (-infinity: all bands, until
+// set_default_footprint); grey() is the batched GPU form with one footprint per hit.
+class wavelet_multiband_texture : public texture {
+  public:
+    wavelet_multiband_texture(double scale, int firstBand, int nbands, const float *w, float variance = 0.18402f,
+                              bool fade = true)
+        : scale(scale), first_band(firstBand), nbands(nbands), weights(w, w + (nbands > 0 ? nbands : 0)),
+          variance(variance), fade(fade)
+    {
+        noise_3d = std::make_unique<WaveletNoise>(128, 12345); // wavelet_texture's tile (texture.h:55-56)
+        noise_3d->generateNoiseTile3D();
+    }
+
+    void set_default_footprint(float s) { default_s = s; }
+    float default_footprint() const { return default_s; }
+
+    color value(double, double, const point3 &p) const override
+    {
+        const float xyz[3] = {p.x(), p.y(), p.z()};
+        const std::vector<float> &c = noise_3d->getNoiseCoefficients();
+        const float g = wnhost_wavelet_multiband_texture_value(c.empty() ? nullptr : c.data(), noise_3d->getTileSize(), scale,
+                                                               first_band, nbands, weights.data(), variance, fade ? 1 : 0,
+                                                               xyz, default_s);
+        return color(g, g, g);
+    }
+    // batched grey levels (host pointers): one footprint per hit; active == nullptr means every point, else inactive
+    // points keep the caller's value
+    void grey(const float *xyz, const float *s, const uint8_t *active, size_t n, float *out) const
+    {
+        if (!n) return;
+        wnhost::DeviceBuffer fp(n * sizeof(float));
+        fp.upload(s);
+        wnhost::texture_batch(xyz, active, n, out, [&](const float *in, const uint8_t *act, float *res) {
+            wnhost::check(wn_wavelet_multiband_texture_points(noise_3d->tile(3), scale, first_band, nbands, weights.data(),
+                                                              variance, fade ? 1 : 0, in, fp.as<float>(), act, n, res,
+                                                              nullptr), "wn_wavelet_multiband_texture_points");
+        });
+    }
+
+  private:
+    std::unique_ptr<WaveletNoise> noise_3d;
+    double scale;
+    int first_band, nbands;
+    std::vector<float> weights;
+    float variance;
+    bool fade;
+    float default_s = -std::numeric_limits<float>::infinity();
 };
 
 #endif

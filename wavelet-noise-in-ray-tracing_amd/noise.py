@@ -48,6 +48,11 @@ def _is_scalar_point(p, width):
     return a.ndim == 1 and a.size == width
 
 
+def _per_point(s):
+    """True for an array of footprints (one per point), False for a scalar."""
+    return s.dim() != 0 if isinstance(s, torch.Tensor) else np.ndim(s) != 0
+
+
 def device_info():
     name = C.create_string_buffer(256)
     cus, hbm = C.c_int(0), C.c_size_t(0)
@@ -192,10 +197,37 @@ class WaveletNoise:
             nr = nr.expand(pts.shape[0], 3).contiguous()
         return self._points(_lib.wn_eval3d_projected_points, 3, p, 3, extra=nr)
 
-    def WMultibandNoise(self, p, s, firstBand, nbands, w, variance=None, normal=None):
+    def _footprint(self, p, s, firstBand, nbands, w, variance, normal, fade, grad):
+        """WMultibandNoise / its gradient with one footprint per point (include/wnoise_footprint.h)."""
+        pts = _dev(p, torch.float32).reshape(-1, 3)
+        sd = _dev(s, torch.float32).reshape(-1)
+        if sd.shape[0] != pts.shape[0]:
+            raise ValueError("s: a scalar, or one footprint per point")
+        out = torch.empty((pts.shape[0], 4) if grad else pts.shape[0], dtype=torch.float32, device="cuda")
+        wa = (C.c_float * max(1, nbands))(*[float(x) for x in list(w)[:nbands]])
+        if normal is not None:
+            nr = _dev(normal, torch.float32).reshape(-1, 3)
+            one = nr.shape[0] == 1
+            if not one and nr.shape[0] != pts.shape[0]:
+                raise ValueError("normal: one vector, or one per point")
+            fn = _lib.wn_multiband3d_projected_footprint_grad_points if grad else _lib.wn_multiband3d_projected_footprint_points
+            check(fn(self._handle(3), _ptr(pts), _ptr(nr), int(one), _ptr(sd), pts.shape[0], int(firstBand), int(nbands), wa,
+                     float(0.296 if variance is None else variance), int(bool(fade)), _ptr(out), _stream()))
+            return out
+        fn = _lib.wn_multiband3d_footprint_grad_points if grad else _lib.wn_multiband3d_footprint_points
+        check(fn(self._handle(3), _ptr(pts), _ptr(sd), pts.shape[0], int(firstBand), int(nbands), wa,
+                 float(0.18402 if variance is None else variance), int(bool(fade)), _ptr(out), _stream()))
+        return out
+
+    def WMultibandNoise(self, p, s, firstBand, nbands, w, variance=None, normal=None, fade=False):
         """Cook & DeRose Appendix 2; absent from the reference.  normal=None: bands are WNoise = evaluate3D
         (variance defaults to the reference's empirical 0.18402); with a normal (one for all points, or one per
-        point) bands are WProjectedNoise = evaluate3DProjected (variance defaults to 0.296)."""
+        point) bands are WProjectedNoise = evaluate3DProjected (variance defaults to 0.296).
+        `s`: a scalar -- one footprint for the whole call (wn_multiband3d_points; `fade` is not read) -- or an array
+        with one footprint per point (include/wnoise_footprint.h): band b of a point runs while (s + firstBand) + b < 0,
+        and with fade=True the finest surviving band fades in over one octave of footprint."""
+        if _per_point(s):
+            return self._footprint(p, s, firstBand, nbands, w, variance, normal, fade, False)
         single = _is_scalar_point(p, 3)
         pts = _dev(p, torch.float32).reshape(-1, 3)
         out = torch.empty(pts.shape[0], dtype=torch.float32, device="cuda")
@@ -225,10 +257,13 @@ class WaveletNoise:
         check(_lib.wn_eval3d_grad_points(self._handle(3), _ptr(pts), pts.shape[0], _ptr(out), _stream()))
         return out
 
-    def WMultibandNoiseGradient(self, p, s, firstBand, nbands, w, variance=None, normal=None):
+    def WMultibandNoiseGradient(self, p, s, firstBand, nbands, w, variance=None, normal=None, fade=False):
         """WMultibandNoise and its gradient with respect to p.  normal=None: bands are evaluate3D
         (wn_multiband3d_grad_points; variance defaults to 0.18402); with a normal (one for all points, or one per point)
-        bands are evaluate3DProjected (wn_multiband3d_projected_grad_points; variance defaults to 0.296)."""
+        bands are evaluate3DProjected (wn_multiband3d_projected_grad_points; variance defaults to 0.296).
+        `s` and `fade` as in WMultibandNoise: an array s gives every point its own band limit."""
+        if _per_point(s):
+            return self._footprint(p, s, firstBand, nbands, w, variance, normal, fade, True)
         pts = _dev(p, torch.float32).reshape(-1, 3)
         out = torch.empty((pts.shape[0], 4), dtype=torch.float32, device="cuda")
         wa = (C.c_float * max(1, nbands))(*[float(x) for x in list(w)[:nbands]])
@@ -504,6 +539,42 @@ class wavelet_texture:
                                                  self.octave_level, a, C.byref(out)))
             return (out.value,) * 3
         g = self.grey(p)
+        return g[:, None].expand(-1, 3)
+
+
+class wavelet_multiband_texture:
+    """WMultibandNoise as a texture, band-limited by each hit's footprint (absent from the reference;
+    wn_wavelet_multiband_texture_points): pos = (float)(p * scale), n = WMultibandNoise(pos, s, firstBand, nbands, w),
+    grey = 0.5 * (1 + clamp(n / 4, -1, 1)).  `s`: log2 of the hit's footprint in noise space (after scale)."""
+
+    def __init__(self, scale, firstBand, nbands, w, variance=0.18402, fade=True):
+        self.scale, self.firstBand, self.nbands = float(scale), int(firstBand), int(nbands)
+        self.w = [float(x) for x in list(w)[:self.nbands]]
+        self.variance, self.fade = float(variance), bool(fade)
+        self.default_footprint = -math.inf  # value(): all bands
+        self.noise_3d = WaveletNoise(128, 12345)  # wavelet_texture's tile (texture.h:55-56)
+        self.noise_3d.generateNoiseTile3D()
+
+    def grey(self, p, s, active=None, out=None):
+        pts = _dev(p, torch.float32).reshape(-1, 3)
+        sd = _dev(s, torch.float32).reshape(-1)
+        if sd.shape[0] != pts.shape[0]:
+            raise ValueError("s: one footprint per point")
+        if out is None:
+            out = torch.zeros(pts.shape[0], dtype=torch.float32, device="cuda")
+        act = _dev(active, torch.uint8) if active is not None else None
+        wa = (C.c_float * max(1, self.nbands))(*self.w)
+        check(_lib.wn_wavelet_multiband_texture_points(self.noise_3d._handle(3), self.scale, self.firstBand, self.nbands, wa,
+                                                       self.variance, int(self.fade), _ptr(pts), _ptr(sd), _ptr(act),
+                                                       pts.shape[0], _ptr(out), _stream()))
+        return out
+
+    def value(self, u, v, p):
+        """One point: a 3-tuple at the default footprint; an (N, 3) batch: (N, 3), every point at the default footprint."""
+        pts = _dev(p, torch.float32).reshape(-1, 3)
+        g = self.grey(pts, torch.full((pts.shape[0],), self.default_footprint, dtype=torch.float32, device="cuda"))
+        if _is_scalar_point(p, 3):
+            return (float(g.item()),) * 3
         return g[:, None].expand(-1, 3)
 
 
