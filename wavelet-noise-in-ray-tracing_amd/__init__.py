@@ -19,7 +19,8 @@ from ._capi import WN_PERLIN_CURL_NOISE, WN_PERLIN_CURL_TURB, WN_PERLIN_CURL_FRA
 _capi.load()  # fail loudly when the HIP library is missing
 
 from .noise import (  # noqa: E402
-    WaveletNoise, perlin, PerlinNoise, noise_texture, wavelet_texture, wavelet_multiband_texture, GridSpec,
+    WaveletNoise, perlin, PerlinNoise, noise_texture, wavelet_texture, wavelet_multiband_texture,
+    noise_multiband_texture, GridSpec,
     generate2DOctaveBandNoise, generate3DSlicedOctaveBandNoise,
     generate3DProjectedOctaveBandNoise, generatePerlinNoise2D, generatePerlinNoise3DSliced,
     wavelet_volume, wavelet_volume_launcher, multiband_volume, perlin_volume, turb_volume, device_info, HipTimer,
@@ -32,7 +33,8 @@ from . import formats  # noqa: E402
 __all__ = [
     "WnError", "wn_grid", "WN_GRID_DEFAULT", "WN_GRID_EXACT", "WN_Z_CONST", "WN_Z_LATTICE",
     "WN_PERLIN_CURL_NOISE", "WN_PERLIN_CURL_TURB", "WN_PERLIN_CURL_FRACTAL",
-    "WaveletNoise", "perlin", "PerlinNoise", "noise_texture", "wavelet_texture", "wavelet_multiband_texture", "GridSpec",
+    "WaveletNoise", "perlin", "PerlinNoise", "noise_texture", "wavelet_texture", "wavelet_multiband_texture",
+    "noise_multiband_texture", "GridSpec",
     "generate2DOctaveBandNoise", "generate3DSlicedOctaveBandNoise",
     "generate3DProjectedOctaveBandNoise", "generatePerlinNoise2D", "generatePerlinNoise3DSliced",
     "wavelet_volume", "wavelet_volume_launcher", "multiband_volume", "perlin_volume", "turb_volume", "device_info",

@@ -1,4 +1,5 @@
-"""ctypes binding of libwnoise_hip.so (include/wnoise.h, include/wnoise_perlin_curl.h, include/wnoise_footprint.h).
+"""ctypes binding of libwnoise_hip.so (include/wnoise.h, include/wnoise_perlin_curl.h, include/wnoise_footprint.h,
+include/wnoise_perlin_footprint.h).
 
 The library is the product: if it is missing or fails to load this module raises, it never
 substitutes a CPU implementation.
@@ -134,6 +135,16 @@ FOOTPRINT_SIGNATURES = {
     "wn_wavelet_multiband_texture_points": (_i, [_vp, _d, _i, _i, _fp, _f, _i, _vp, _vp, _vp, _sz, _vp, _vp]),
 }
 
+# name -> (restype, argtypes); every symbol include/wnoise_perlin_footprint.h declares.
+_points_fp = (_i, [_vp, _vp, _vp, _sz, _i, _f, _i, _vp, _vp])  # perm, xyz, s, n, depth / octaves, bias, fade, out, stream
+PERLIN_FOOTPRINT_SIGNATURES = {
+    "wn_perlin_turb_footprint_points": _points_fp,
+    "wn_perlin_fractal_footprint_points": _points_fp,
+    "wn_perlin_turb_footprint_grad_points": _points_fp,
+    "wn_perlin_fractal_footprint_grad_points": _points_fp,
+    "wn_noise_multiband_texture_points": (_i, [_vp, _d, _i, _f, _i, _vp, _vp, _vp, _sz, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -147,7 +158,8 @@ def load():
             f"{LIB_PATH} is missing: build it with `make -C {HERE}` (or "
             "__graft_entry__.build()).  This package has no CPU implementation.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in (*SIGNATURES.items(), *PERLIN_CURL_SIGNATURES.items(), *FOOTPRINT_SIGNATURES.items()):
+    for name, (res, args) in (*SIGNATURES.items(), *PERLIN_CURL_SIGNATURES.items(), *FOOTPRINT_SIGNATURES.items(),
+                              *PERLIN_FOOTPRINT_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

@@ -732,6 +732,110 @@ WN_EVAL_FN double perlin_fractal_grad(const Table perm, float x, float y, float 
     return result / max_value;
 }
 
+// ---- turb and fractal_noise with the octave limit taken from a footprint per sample (include/wnoise_perlin_footprint.h) ----
+// Clamping the octave sum by the filter width is the classical way to antialias Perlin noise.  For a sample with footprint s
+// (log2 of the footprint in the noise space of p) and octave i in 0 .. octaves-1:
+//     t_i = (s + bias) + (float)i, in float and in this association;
+//     octave i is active iff t_i < 0; t_i does not decrease with i, so the first octave that fails ends the loop
+//         (a NaN or +inf s: no octave; -inf: all of them);
+//     f_i = 1.0f with fade == 0 (a hard cut), fminf(1.0f, -t_i) with fade != 0: the finest surviving octave fades in over
+//         one octave of footprint.
+// Octave i has cells of size 2^-i: bias = 0 cuts an octave when the footprint reaches one cell, bias = -1 at two cells --
+// the rule wn_multiband3d_footprint_points applies to its bands (band b has cells of 2^-(b+1) in p; it runs while
+// s + b < 0).  Where f_i == 1 for every active octave the products with f_i are exact: a turb sample with k active octaves
+// then has the bits of perlin_turb / perlin_turb_grad at depth k, a fractal sample with octaves == 6 and all six active
+// those of perlin_fractal / perlin_fractal_grad.
+constexpr int kPerlinFootprintMaxOctaves = 16; // depth / octaves of the footprint entry points: 0 .. 16
+
+WN_EVAL_FN float perlin_footprint_t(float s, float bias, int i) { return (s + bias) + (float)i; }
+WN_EVAL_FN double perlin_footprint_factor(float t, int fade) { return (double)(fade ? fminf(1.0f, -t) : 1.0f); }
+// the number of active octaves (what the sorted kernel bins by; the evaluators below run the same test octave by octave)
+WN_EVAL_FN int perlin_footprint_count(float s, float bias, int octaves)
+{
+    int k = 0;
+    while (k < octaves && perlin_footprint_t(s, bias, k) < 0.0f) ++k;
+    return k;
+}
+
+// perlin_turb's arithmetic (the float point doubles per octave, weight halves) with accum += (weight * f_i) * noise; the
+// value is fabs(accum).  GRAD: g += f_i * grad noise in octave order, times perlin_turb_grad's sign rule on the value's own
+// accum.  No active octave: +0 in all four channels.
+template <bool GRAD, typename Table>
+WN_EVAL_FN double perlin_turb_footprint(const Table perm, float x, float y, float z, int depth, float s, float bias, int fade,
+                                        double *g)
+{
+    double accum = 0.0, weight = 1.0, gx = 0.0, gy = 0.0, gz = 0.0;
+    for (int i = 0; i < depth; ++i) {
+        const float t = perlin_footprint_t(s, bias, i);
+        if (!(t < 0.0f)) break;
+        const double f = perlin_footprint_factor(t, fade);
+        if constexpr (GRAD) {
+            double gn[3];
+            accum += (weight * f) * perlin_grad_exact(perm, (double)x, (double)y, (double)z, gn);
+            gx += f * gn[0];
+            gy += f * gn[1];
+            gz += f * gn[2];
+        } else {
+            accum += (weight * f) * perlin_exact(perm, (double)x, (double)y, (double)z);
+        }
+        weight *= 0.5;
+        x *= 2.0f;
+        y *= 2.0f;
+        z *= 2.0f;
+    }
+    if constexpr (GRAD) {
+        const bool negative = accum < 0.0;
+        g[0] = negative ? -gx : gx;
+        g[1] = negative ? -gy : gy;
+        g[2] = negative ? -gz : gz;
+    }
+    return fabs(accum);
+}
+
+// perlin_fractal's arithmetic (float point times double frequency) for `octaves` octaves with
+// result += noise * (amplitude * f_i).  max_value is the sum of the amplitudes of ALL `octaves` octaves, however many run
+// (as out_div of multiband_footprint_exact: dropping an octave drops its energy, nothing is renormalised); every partial
+// sum of it is exact.  Value: result / max_value; GRAD: (sum_i f_i * grad noise) / max_value.  octaves == 0: 0 in every
+// channel and no division.
+template <bool GRAD, typename Table>
+WN_EVAL_FN double perlin_fractal_footprint(const Table perm, float x, float y, float z, int octaves, float s, float bias,
+                                           int fade, double *g)
+{
+    double result = 0.0, amplitude = 1.0, frequency = 1.0, max_value = 0.0, gx = 0.0, gy = 0.0, gz = 0.0;
+    int i = 0;
+    for (; i < octaves; ++i) {
+        const float t = perlin_footprint_t(s, bias, i);
+        if (!(t < 0.0f)) break;
+        const double f = perlin_footprint_factor(t, fade);
+        if constexpr (GRAD) {
+            double gn[3];
+            result += perlin_grad_exact(perm, x * frequency, y * frequency, z * frequency, gn) * (amplitude * f);
+            gx += f * gn[0];
+            gy += f * gn[1];
+            gz += f * gn[2];
+        } else {
+            result += perlin_exact(perm, x * frequency, y * frequency, z * frequency) * (amplitude * f);
+        }
+        max_value += amplitude;
+        amplitude *= 0.5;
+        frequency *= 2.0;
+    }
+    for (; i < octaves; ++i) { // the octaves that do not run still count
+        max_value += amplitude;
+        amplitude *= 0.5;
+    }
+    if (octaves <= 0) {
+        if constexpr (GRAD) g[0] = g[1] = g[2] = 0.0;
+        return 0.0;
+    }
+    if constexpr (GRAD) {
+        g[0] = gx / max_value;
+        g[1] = gy / max_value;
+        g[2] = gz / max_value;
+    }
+    return result / max_value;
+}
+
 // ---- curl of three Perlin potentials (include/wnoise_perlin_curl.h; absent from the reference) --------------------------
 // psi_k is noise / the signed turb sum / fractal_noise with the cell index shifted by off[3k .. 3k+2] (any integers, taken
 // & 255).  Of each potential's gradient two partials enter the curl; s holds the six in the order
@@ -881,6 +985,17 @@ WN_EVAL_FN float noise_texture_value(const Table perm, float fscale, float octav
     double v = perlin_exact(perm, (double)sx, (double)sy, (double)sz);
     v = 0.5 * (1.0 + v);
     return (float)v;
+}
+
+// noise_multiband_texture (absent from the reference): the point scaled per axis in float, pos = fscale * p, as
+// noise_texture_value scales it but without the octave factor; n = perlin_fractal_footprint(pos, s); 0.5 * (1 + n).  s is
+// the footprint in noise space (after scale).
+template <typename Table>
+WN_EVAL_FN float noise_multiband_texture_value(const Table perm, float fscale, int octaves, float bias, int fade, float px,
+                                               float py, float pz, float s)
+{
+    const double n = perlin_fractal_footprint<false>(perm, fscale * px, fscale * py, fscale * pz, octaves, s, bias, fade, nullptr);
+    return (float)(0.5 * (1.0 + n));
 }
 
 } // namespace wn

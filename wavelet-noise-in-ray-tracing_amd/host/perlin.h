@@ -5,7 +5,8 @@
 // wn_perm_create_seeded) and lives on the device as 512 bytes.  The batched forms run as HIP kernels in fp64 with the
 // reference's operation order; the scalar members are evaluated on the host from the mirrored table (scalar_eval.h;
 // WN_SCALAR_ON_DEVICE=1: by the resident scalar kernel).  Bit-identical either way.
-// Additive: turb() (RTOW; absent from the reference), batched overloads, analytic gradients and curl noise.
+// Additive: turb() (RTOW; absent from the reference), batched overloads, analytic gradients, curl noise
+// and octave limiting by a footprint per sample.
 #ifndef PERLIN_H
 #define PERLIN_H
 
@@ -17,6 +18,7 @@
 #include "vec3.h"
 #include "wn_host.hpp"
 #include "wnoise_perlin_curl.h"
+#include "wnoise_perlin_footprint.h"
 
 using point3 = vec3;
 
@@ -140,6 +142,53 @@ class perlin {
     void turb_curl(const float *xyz, size_t n, double *out3, int depth = 7, const int *offsets9 = nullptr) const { curl_vec3(xyz, n, WN_PERLIN_CURL_TURB, depth, offsets9, out3); }
     void fractal_noise_curl(const float *xyz, size_t n, double *out3, const int *offsets9 = nullptr) const { curl_vec3(xyz, n, WN_PERLIN_CURL_FRACTAL, 0, offsets9, out3); }
 
+    // ---- additive: octave limiting by a footprint per sample (absent from the reference; include/wnoise_perlin_footprint.h)
+    // s = log2 of the sample's footprint in the noise space of q: octave i runs while (s + bias) + i < 0; fade: the finest
+    // surviving octave enters with min(1, -t_i) instead of popping.  Scalar members: evaluated on the host, bit-identical
+    // to the kernels; the gradient forms return the value and write d/dx, d/dy, d/dz to grad.
+    double turb_footprint(const point3 &q, float s, int depth = 7, float bias = 0.0f, bool fade = false) const
+    {
+        const float xyz[3] = {q.x(), q.y(), q.z()};
+        return wnhost_perlin_turb_footprint(p.data(), xyz, depth, s, bias, fade ? 1 : 0, nullptr);
+    }
+    double fractal_noise_footprint(const point3 &q, float s, int octaves = 6, float bias = 0.0f, bool fade = false) const
+    {
+        const float xyz[3] = {q.x(), q.y(), q.z()};
+        return wnhost_perlin_fractal_footprint(p.data(), xyz, octaves, s, bias, fade ? 1 : 0, nullptr);
+    }
+    double turb_footprint_gradient(const point3 &q, float s, double grad[3], int depth = 7, float bias = 0.0f, bool fade = false) const
+    {
+        const float xyz[3] = {q.x(), q.y(), q.z()};
+        return wnhost_perlin_turb_footprint(p.data(), xyz, depth, s, bias, fade ? 1 : 0, grad);
+    }
+    double fractal_noise_footprint_gradient(const point3 &q, float s, double grad[3], int octaves = 6, float bias = 0.0f,
+                                            bool fade = false) const
+    {
+        const float xyz[3] = {q.x(), q.y(), q.z()};
+        return wnhost_perlin_fractal_footprint(p.data(), xyz, octaves, s, bias, fade ? 1 : 0, grad);
+    }
+    // Batched overloads (host pointers, through the GPU): one footprint per point; n doubles to out, or n records
+    // {value, d/dx, d/dy, d/dz} of four doubles to out4.
+    void turb_footprint(const float *xyz, const float *s, size_t n, double *out, int depth = 7, float bias = 0.0f, bool fade = false) const
+    {
+        footprint_vec3(xyz, s, n, 0, depth, bias, fade, out);
+    }
+    void fractal_noise_footprint(const float *xyz, const float *s, size_t n, double *out, int octaves = 6, float bias = 0.0f,
+                                 bool fade = false) const
+    {
+        footprint_vec3(xyz, s, n, 1, octaves, bias, fade, out);
+    }
+    void turb_footprint_gradient(const float *xyz, const float *s, size_t n, double *out4, int depth = 7, float bias = 0.0f,
+                                 bool fade = false) const
+    {
+        footprint_vec3(xyz, s, n, 2, depth, bias, fade, out4);
+    }
+    void fractal_noise_footprint_gradient(const float *xyz, const float *s, size_t n, double *out4, int octaves = 6,
+                                          float bias = 0.0f, bool fade = false) const
+    {
+        footprint_vec3(xyz, s, n, 3, octaves, bias, fade, out4);
+    }
+
     const std::vector<int> &table() const { return p; }
     const wn_perm *perm() const { return perm_; }
 
@@ -153,6 +202,20 @@ class perlin {
         else if (kind == 1) wnhost::check(wn_perlin_turb_grad_points(perm_, in.as<float>(), n, depth, res.as<double>(), nullptr), "wn_perlin_turb_grad_points");
         else wnhost::check(wn_perlin_fractal_grad_points(perm_, in.as<float>(), n, res.as<double>(), nullptr), "wn_perlin_fractal_grad_points");
         res.download(out4);
+    }
+    // kind 0: turb, 1: fractal_noise, 2 / 3: their gradients
+    void footprint_vec3(const float *xyz, const float *s, size_t n, int kind, int octaves, float bias, bool fade, double *out) const
+    {
+        if (!n) return;
+        wnhost::DeviceBuffer in(3 * n * sizeof(float)), fp(n * sizeof(float)), res((kind >= 2 ? 4 : 1) * n * sizeof(double));
+        in.upload(xyz);
+        fp.upload(s);
+        const int f = fade ? 1 : 0;
+        if (kind == 0) wnhost::check(wn_perlin_turb_footprint_points(perm_, in.as<float>(), fp.as<float>(), n, octaves, bias, f, res.as<double>(), nullptr), "wn_perlin_turb_footprint_points");
+        else if (kind == 1) wnhost::check(wn_perlin_fractal_footprint_points(perm_, in.as<float>(), fp.as<float>(), n, octaves, bias, f, res.as<double>(), nullptr), "wn_perlin_fractal_footprint_points");
+        else if (kind == 2) wnhost::check(wn_perlin_turb_footprint_grad_points(perm_, in.as<float>(), fp.as<float>(), n, octaves, bias, f, res.as<double>(), nullptr), "wn_perlin_turb_footprint_grad_points");
+        else wnhost::check(wn_perlin_fractal_footprint_grad_points(perm_, in.as<float>(), fp.as<float>(), n, octaves, bias, f, res.as<double>(), nullptr), "wn_perlin_fractal_footprint_grad_points");
+        res.download(out);
     }
     static const int32_t *curl_offsets(const int *offsets9)
     {

@@ -136,6 +136,30 @@ double wnhost_perlin_turb_grad(const int *perm, const float q[3], int depth, dou
     return wn::perlin_turb_grad(perm, q[0], q[1], q[2], depth, grad);
 }
 
+double wnhost_perlin_turb_footprint(const int *perm, const float q[3], int depth, float s, float bias, int fade, double *grad)
+{
+    if (grad) grad[0] = grad[1] = grad[2] = 0.0;
+    if (depth < 0 || depth > wn::kPerlinFootprintMaxOctaves) return 0.0;
+    return grad ? wn::perlin_turb_footprint<true>(perm, q[0], q[1], q[2], depth, s, bias, fade, grad)
+                : wn::perlin_turb_footprint<false>(perm, q[0], q[1], q[2], depth, s, bias, fade, nullptr);
+}
+
+double wnhost_perlin_fractal_footprint(const int *perm, const float q[3], int octaves, float s, float bias, int fade,
+                                       double *grad)
+{
+    if (grad) grad[0] = grad[1] = grad[2] = 0.0;
+    if (octaves < 0 || octaves > wn::kPerlinFootprintMaxOctaves) return 0.0;
+    return grad ? wn::perlin_fractal_footprint<true>(perm, q[0], q[1], q[2], octaves, s, bias, fade, grad)
+                : wn::perlin_fractal_footprint<false>(perm, q[0], q[1], q[2], octaves, s, bias, fade, nullptr);
+}
+
+float wnhost_noise_multiband_texture_value(const int *perm, double scale, int octaves, float bias, int fade,
+                                           const float xyz[3], float s)
+{
+    if (octaves < 0 || octaves > wn::kPerlinFootprintMaxOctaves) return 0.5f;
+    return wn::noise_multiband_texture_value(perm, (float)scale, octaves, bias, fade, xyz[0], xyz[1], xyz[2], s);
+}
+
 void wnhost_perlin_curl(const int *perm, double x, double y, double z, const int offsets9[9], double v[3])
 {
     wn::perlin_curl_exact(perm, x, y, z, offsets9, v);

@@ -77,6 +77,23 @@ WNHOST_API double wnhost_perlin_turb(const int *perm, const float q[3], int dept
 WNHOST_API double wnhost_perlin_grad(const int *perm, double x, double y, double z, double grad[3]);
 WNHOST_API double wnhost_perlin_fractal_grad(const int *perm, const float q[3], double grad[3]);
 WNHOST_API double wnhost_perlin_turb_grad(const int *perm, const float q[3], int depth, double grad[3]);
+// turb and fractal_noise with the octave limit taken from ONE footprint s (absent from the reference;
+// include/wnoise_perlin_footprint.h): octave i runs while t_i = (s + bias) + i < 0 and enters with the factor f_i = 1
+// (fade == 0: a hard cut) or fminf(1, -t_i) (fade != 0).  turb: accum += (2^-i * f_i) * noise, the value fabs(accum), the
+// gradient sum_i f_i * grad noise times wnhost_perlin_turb_grad's sign.  fractal: result += noise * (2^-i * f_i) over
+// `octaves` octaves, divided -- like sum_i f_i * grad noise -- by the amplitudes of ALL `octaves` octaves.  Each returns the
+// value; grad_or_null != NULL also receives the gradient (the value's bits do not change).  The bits of
+// wn_perlin_*_footprint_points and their _grad_ twins and -- where every f_i == 1 -- of wnhost_perlin_turb at the sample's
+// octave count / of wnhost_perlin_fractal at six of six octaves.  depth / octaves outside 0..16, or no active octave -> 0 in
+// every channel.
+WNHOST_API double wnhost_perlin_turb_footprint(const int *perm, const float q[3], int depth, float s, float bias, int fade,
+                                               double *grad_or_null);
+WNHOST_API double wnhost_perlin_fractal_footprint(const int *perm, const float q[3], int octaves, float s, float bias,
+                                                  int fade, double *grad_or_null);
+// grey level of noise_multiband_texture::value (texture.h; wn_noise_multiband_texture_points): the fractal form above at
+// (float)scale * xyz per axis and footprint s, through 0.5 * (1 + n); octaves outside 0..16: 0.5
+WNHOST_API float wnhost_noise_multiband_texture_value(const int *perm, double scale, int octaves, float bias, int fade,
+                                                      const float xyz[3], float s);
 // The curl of three Perlin potentials (absent from the reference; include/wnoise_perlin_curl.h): psi_k is noise / the signed
 // turb sum (no fabs) / fractal_noise with the cell index shifted by offsets9[3k .. 3k+2] = (ox, oy, oz)_k (any integers, taken
 // & 255); writes v = (d psi2/dy - d psi1/dz, d psi0/dz - d psi2/dx, d psi1/dx - d psi0/dy) -- six of the partial sums the

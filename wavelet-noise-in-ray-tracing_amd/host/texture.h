@@ -20,6 +20,7 @@
 #include "vec3.h"
 #include "wn_host.hpp"
 #include "wnoise_footprint.h"
+#include "wnoise_perlin_footprint.h"
 
 using color = vec3;
 using point3 = vec3;
@@ -203,6 +204,51 @@ class wavelet_multiband_texture : public texture {
     int first_band, nbands;
     std::vector<float> weights;
     float variance;
+    bool fade;
+    float default_s = -std::numeric_limits<float>::infinity();
+};
+
+// fractal_noise as a texture, octave-limited by each hit's footprint (absent from the reference;
+// include/wnoise_perlin_footprint.h): the band-limited Perlin twin of wavelet_multiband_texture.  pos = (float)scale * p per
+// axis in float (noise_texture's scaling without its octave factor), n = fractal_noise over `octaves` octaves of which
+// octave i runs while (s + bias) + i < 0, grey = 0.5 * (1 + n).  s is the log2 of the hit's footprint in noise space (after
+// scale); with `fade` the finest surviving octave fades in over one octave.  value() is one sample on the host at the
+// default footprint (-infinity: all octaves, until set_default_footprint); grey() is the batched GPU form with one
+// footprint per hit.
+class noise_multiband_texture : public texture {
+  public:
+    noise_multiband_texture(double scale, int octaves = 6, float bias = 0.0f, bool fade = true)
+        : scale(scale), octaves(octaves), bias(bias), fade(fade)
+    {
+    }
+
+    void set_default_footprint(float s) { default_s = s; }
+    float default_footprint() const { return default_s; }
+
+    color value(double, double, const point3 &p) const override
+    {
+        const float xyz[3] = {p.x(), p.y(), p.z()};
+        const float g = wnhost_noise_multiband_texture_value(noise.table().data(), scale, octaves, bias, fade ? 1 : 0, xyz, default_s);
+        return color(g, g, g);
+    }
+    // batched grey levels (host pointers): one footprint per hit; active == nullptr means every point, else inactive
+    // points keep the caller's value
+    void grey(const float *xyz, const float *s, const uint8_t *active, size_t n, float *out) const
+    {
+        if (!n) return;
+        wnhost::DeviceBuffer fp(n * sizeof(float));
+        fp.upload(s);
+        wnhost::texture_batch(xyz, active, n, out, [&](const float *in, const uint8_t *act, float *res) {
+            wnhost::check(wn_noise_multiband_texture_points(noise.perm(), scale, octaves, bias, fade ? 1 : 0, in, fp.as<float>(),
+                                                            act, n, res, nullptr), "wn_noise_multiband_texture_points");
+        });
+    }
+
+  private:
+    perlin noise; // default seed, as noise_texture
+    double scale;
+    int octaves;
+    float bias;
     bool fade;
     float default_s = -std::numeric_limits<float>::infinity();
 };

@@ -477,6 +477,35 @@ class perlin:
         """noise_curl with fractal_noise potentials (six octaves)."""
         return self._curl(_dev(p, torch.float32).reshape(-1, 3), _capi.WN_PERLIN_CURL_FRACTAL, 0, offsets)
 
+    # -- octave limiting by a footprint per sample (absent from the reference; include/wnoise_perlin_footprint.h)
+    def _footprint(self, fn, p, s, octaves, bias, fade, channels):
+        pts = _dev(p, torch.float32).reshape(-1, 3)
+        sd = _dev(s, torch.float32).reshape(-1)
+        if sd.shape[0] != pts.shape[0]:
+            raise ValueError("s: one footprint per point")
+        out = torch.empty((pts.shape[0], channels) if channels > 1 else pts.shape[0], dtype=torch.float64, device="cuda")
+        check(fn(self._h, _ptr(pts), _ptr(sd), pts.shape[0], int(octaves), float(bias), int(bool(fade)), _ptr(out), _stream()))
+        return out
+
+    def turb_footprint(self, p, s, depth=7, bias=0.0, fade=False):
+        """turb(p, depth) with the octaves each sample's footprint can carry (wn_perlin_turb_footprint_points): `s`, one
+        per point, is the log2 of the footprint in the noise space of p; octave i runs while (s + bias) + i < 0, and with
+        `fade` the finest surviving octave enters with min(1, -t_i).  (N,) float64."""
+        return self._footprint(_lib.wn_perlin_turb_footprint_points, p, s, depth, bias, fade, 1)
+
+    def fractal_noise_footprint(self, p, s, octaves=6, bias=0.0, fade=False):
+        """fractal_noise over `octaves` octaves, limited per sample as turb_footprint; the normalisation sums all
+        `octaves` amplitudes, however many run (wn_perlin_fractal_footprint_points)."""
+        return self._footprint(_lib.wn_perlin_fractal_footprint_points, p, s, octaves, bias, fade, 1)
+
+    def turb_footprint_gradient(self, p, s, depth=7, bias=0.0, fade=False):
+        """turb_footprint and its gradient: (N, 4) float64 of {value, d/dx, d/dy, d/dz}."""
+        return self._footprint(_lib.wn_perlin_turb_footprint_grad_points, p, s, depth, bias, fade, 4)
+
+    def fractal_noise_footprint_gradient(self, p, s, octaves=6, bias=0.0, fade=False):
+        """fractal_noise_footprint and its gradient: (N, 4) float64 of {value, d/dx, d/dy, d/dz}."""
+        return self._footprint(_lib.wn_perlin_fractal_footprint_grad_points, p, s, octaves, bias, fade, 4)
+
 
 PerlinNoise = perlin  # experient/PerlinNoise.hpp is the same algorithm with an explicit seed
 
@@ -567,6 +596,37 @@ class wavelet_multiband_texture:
         check(_lib.wn_wavelet_multiband_texture_points(self.noise_3d._handle(3), self.scale, self.firstBand, self.nbands, wa,
                                                        self.variance, int(self.fade), _ptr(pts), _ptr(sd), _ptr(act),
                                                        pts.shape[0], _ptr(out), _stream()))
+        return out
+
+    def value(self, u, v, p):
+        """One point: a 3-tuple at the default footprint; an (N, 3) batch: (N, 3), every point at the default footprint."""
+        pts = _dev(p, torch.float32).reshape(-1, 3)
+        g = self.grey(pts, torch.full((pts.shape[0],), self.default_footprint, dtype=torch.float32, device="cuda"))
+        if _is_scalar_point(p, 3):
+            return (float(g.item()),) * 3
+        return g[:, None].expand(-1, 3)
+
+
+class noise_multiband_texture:
+    """fractal_noise as a texture, octave-limited by each hit's footprint (absent from the reference;
+    wn_noise_multiband_texture_points): pos = (float)scale * p, n = fractal_noise over `octaves` octaves of which octave i
+    runs while (s + bias) + i < 0, grey = 0.5 * (1 + n).  `s`: log2 of the hit's footprint in noise space (after scale)."""
+
+    def __init__(self, scale, octaves=6, bias=0.0, fade=True):
+        self.noise = perlin()  # default-seeded member, as noise_texture
+        self.scale, self.octaves, self.bias, self.fade = float(scale), int(octaves), float(bias), bool(fade)
+        self.default_footprint = -math.inf  # value(): all octaves
+
+    def grey(self, p, s, active=None, out=None):
+        pts = _dev(p, torch.float32).reshape(-1, 3)
+        sd = _dev(s, torch.float32).reshape(-1)
+        if sd.shape[0] != pts.shape[0]:
+            raise ValueError("s: one footprint per point")
+        if out is None:
+            out = torch.zeros(pts.shape[0], dtype=torch.float32, device="cuda")
+        act = _dev(active, torch.uint8) if active is not None else None
+        check(_lib.wn_noise_multiband_texture_points(self.noise._h, self.scale, self.octaves, self.bias, int(self.fade),
+                                                     _ptr(pts), _ptr(sd), _ptr(act), pts.shape[0], _ptr(out), _stream()))
         return out
 
     def value(self, u, v, p):
