@@ -1,5 +1,5 @@
 """ctypes binding of libwnoise_hip.so (include/wnoise.h, include/wnoise_perlin_curl.h, include/wnoise_footprint.h,
-include/wnoise_perlin_footprint.h).
+include/wnoise_perlin_footprint.h, include/wnoise_multiband2d.h).
 
 The library is the product: if it is missing or fails to load this module raises, it never
 substitutes a CPU implementation.
@@ -145,6 +145,19 @@ PERLIN_FOOTPRINT_SIGNATURES = {
     "wn_noise_multiband_texture_points": (_i, [_vp, _d, _i, _f, _i, _vp, _vp, _vp, _sz, _vp, _vp]),
 }
 
+# name -> (restype, argtypes); every symbol include/wnoise_multiband2d.h declares.
+_grid_mb2d = (_i, [_vp, _gp, _f, _i, _i, _fp, _f, _vp, _vp])            # tile, grid, s, first_band, nbands, w, var, out, stream
+_points_mb2d = (_i, [_vp, _vp, _sz, _f, _i, _i, _fp, _f, _vp, _vp])     # tile, xy, n, s, first_band, nbands, w, var, out, stream
+_points_fp_mb2d = (_i, [_vp, _vp, _vp, _sz, _i, _i, _fp, _f, _i, _vp, _vp])  # tile, xy, s, n, first_band, nbands, w, var, fade, out, stream
+MULTIBAND2D_SIGNATURES = {
+    "wn_multiband2d_grid": _grid_mb2d,
+    "wn_multiband2d_grad_grid": _grid_mb2d,
+    "wn_multiband2d_points": _points_mb2d,
+    "wn_multiband2d_grad_points": _points_mb2d,
+    "wn_multiband2d_footprint_points": _points_fp_mb2d,
+    "wn_multiband2d_footprint_grad_points": _points_fp_mb2d,
+}
+
 _lib = None
 
 
@@ -159,7 +172,7 @@ def load():
             "__graft_entry__.build()).  This package has no CPU implementation.")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (*SIGNATURES.items(), *PERLIN_CURL_SIGNATURES.items(), *FOOTPRINT_SIGNATURES.items(),
-                              *PERLIN_FOOTPRINT_SIGNATURES.items()):
+                              *PERLIN_FOOTPRINT_SIGNATURES.items(), *MULTIBAND2D_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

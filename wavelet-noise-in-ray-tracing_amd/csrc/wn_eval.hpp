@@ -53,7 +53,10 @@ WN_EVAL_FN void bspline_grad(float p, int &mid, float w[3], float d[3])
 // WaveletNoise::evaluate2D, WaveletNoise.cpp:111-140 (f1 outer, f0 inner; weight = w0*w1).
 // GRAD: beside the value's sum (unchanged: the same bits) the two derivative sums over the same 9 coefficients, tap
 // weights d_x*w_y and w_x*d_y, each accumulated f1 -> f0, unfused; d/dx, d/dy go to g.
-template <bool GRAD = false>
+// PADDED: `coef` has row stride n+2 with two wrap-around columns (padded[y][x] = tile[y][x mod n] for x in [0, n+2)), the
+// layout the 2-D multiband kernels stage in LDS: the three x taps of a row are adjacent; the values, the arithmetic and its
+// order are those of the linear layout.
+template <bool GRAD = false, bool PADDED = false>
 WN_EVAL_FN float eval2d_exact(const float *coef, int n, int nmask, float px, float py, float *g = nullptr)
 {
     if (n == 0) { // :112-114; the empty tile: 0 in every channel
@@ -73,7 +76,7 @@ WN_EVAL_FN float eval2d_exact(const float *coef, int n, int nmask, float px, flo
     WN_UNROLL
     for (int f = 0; f < 3; ++f) {
         cx[f] = dmod(mx + f - 1, n, nmask);
-        cy[f] = dmod(my + f - 1, n, nmask) * n;
+        cy[f] = dmod(my + f - 1, n, nmask) * (PADDED ? n + 2 : n);
     }
     float result = 0.0f, gx = 0.0f, gy = 0.0f;
     WN_UNROLL
@@ -81,7 +84,7 @@ WN_EVAL_FN float eval2d_exact(const float *coef, int n, int nmask, float px, flo
         WN_UNROLL
         for (int fx = 0; fx < 3; ++fx) {
             const float weight = wx[fx] * wy[fy];
-            const float c = coef[cx[fx] + cy[fy]];
+            const float c = PADDED ? coef[cx[0] + fx + cy[fy]] : coef[cx[fx] + cy[fy]];
             result += weight * c;
             if constexpr (GRAD) {
                 gx += dx[fx] * wy[fy] * c;
@@ -416,6 +419,50 @@ WN_EVAL_FN float multiband_footprint_exact(const A &a, const float p[3], const f
         g[0] = gx;
         g[1] = gy;
         g[2] = gz;
+    }
+    return v;
+}
+
+// ---- 2-D WMultibandNoise (include/wnoise_multiband2d.h; absent from the reference) ----------------------------------------
+// multiband_footprint_exact on a 2-D tile: band b runs while t_b = footprint_t(a, s, b) < 0 and enters with the one float
+// product wb = w[b] * f_b (f_b = 1.0f without fade, fminf(1.0f, -t_b) with it); the value adds wb * evaluate2D(q_b), the
+// gradient with respect to p (wb * (2 * 2^(first_band+b))) * grad evaluate2D(q_b), q_b = 2 * p * 2^(first_band+b); band
+// order, the unfused arithmetic and the division by out_div (when apply_div) are multiband_footprint_exact's.  The uniform-s
+// entry points are this function at the call's s with fade 0, so a footprint sample whose active bands all have f_b == 1
+// has the bits of the uniform call at its s by construction.  No active band, or an empty tile: 0 in every channel.
+// `a` carries n, nmask and a FootprintBands; `coef` is passed beside it because the kernels that stage the tile in LDS
+// read it there (PADDED: the padded layout of eval2d_exact).
+template <bool GRAD, bool PADDED = false, typename A>
+WN_EVAL_FN float multiband2d_footprint_exact(const A &a, const float *coef, const float p[2], float s, float *g)
+{
+    float v = 0.0f, gx = 0.0f, gy = 0.0f;
+    for (int b = 0; b < a.nbands; ++b) {
+        const float t = footprint_t(a, s, b);
+        if (!(t < 0.0f)) break;
+        const float wb = a.band_w[b] * (a.fade ? fminf(1.0f, -t) : 1.0f);
+        const float bs = a.band_scale[b];
+        const float qx = 2.0f * p[0] * bs, qy = 2.0f * p[1] * bs;
+        if constexpr (GRAD) {
+            float gb[2];
+            const float e = eval2d_exact<true, PADDED>(coef, a.n, a.nmask, qx, qy, gb);
+            v += wb * e;
+            const float f = wb * (2.0f * bs);
+            gx += f * gb[0];
+            gy += f * gb[1];
+        } else {
+            v += wb * eval2d_exact<false, PADDED>(coef, a.n, a.nmask, qx, qy);
+        }
+    }
+    if (a.apply_div) {
+        v /= a.out_div;
+        if constexpr (GRAD) {
+            gx /= a.out_div;
+            gy /= a.out_div;
+        }
+    }
+    if constexpr (GRAD) {
+        g[0] = gx;
+        g[1] = gy;
     }
     return v;
 }

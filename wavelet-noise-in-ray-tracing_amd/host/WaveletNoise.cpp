@@ -9,6 +9,7 @@
 #include "scalar_eval.h"
 #include "wn_host.hpp"
 #include "wnoise_footprint.h"
+#include "wnoise_multiband2d.h"
 
 using wnhost::check;
 
@@ -287,6 +288,78 @@ void WaveletNoise::WMultibandNoiseGradient(const float *xyz, const float *normal
               "wn_multiband3d_projected_footprint_grad_points");
     }
     res.download(out4);
+}
+
+// ---- WMultibandNoise on the 2-D tile (include/wnoise_multiband2d.h): the one-sample members on the host (bit-identical to
+// the kernels), the batched ones on the device; a 3-D tile goes to the C ABI, which reports it
+float WaveletNoise::WMultibandNoise2D(const float p[2], float sarg, int firstBand, int nbands, const float *w, float variance,
+                                      bool fade) const
+{
+    if (tileDims != 3)
+        return wnhost_multiband2d_footprint(noiseCoefficients.empty() ? nullptr : noiseCoefficients.data(), tileSizeN, p, sarg,
+                                            fade ? 1 : 0, firstBand, nbands, w, variance, nullptr);
+    float out = 0.0f;
+    WMultibandNoise2D(p, 1, &sarg, fade, firstBand, nbands, w, variance, &out);
+    return out;
+}
+
+float WaveletNoise::WMultibandNoise2DGradient(const float p[2], float sarg, int firstBand, int nbands, const float *w,
+                                              float grad[2], float variance, bool fade) const
+{
+    if (tileDims != 3)
+        return wnhost_multiband2d_footprint(noiseCoefficients.empty() ? nullptr : noiseCoefficients.data(), tileSizeN, p, sarg,
+                                            fade ? 1 : 0, firstBand, nbands, w, variance, grad);
+    float out3[3];
+    WMultibandNoise2DGradient(p, 1, &sarg, fade, firstBand, nbands, w, variance, out3);
+    std::copy(out3 + 1, out3 + 3, grad);
+    return out3[0];
+}
+
+void WaveletNoise::WMultibandNoise2D(const float *xy, size_t n, float sarg, int firstBand, int nbands, const float *w,
+                                     float variance, float *out) const
+{
+    if (!n) return;
+    wnhost::DeviceBuffer in(2 * n * sizeof(float)), res(n * sizeof(float));
+    in.upload(xy);
+    check(wn_multiband2d_points(tile(2), in.as<float>(), n, sarg, firstBand, nbands, w, variance, res.as<float>(), nullptr),
+          "wn_multiband2d_points");
+    res.download(out);
+}
+
+void WaveletNoise::WMultibandNoise2DGradient(const float *xy, size_t n, float sarg, int firstBand, int nbands, const float *w,
+                                             float variance, float *out3) const
+{
+    if (!n) return;
+    wnhost::DeviceBuffer in(2 * n * sizeof(float)), res(3 * n * sizeof(float));
+    in.upload(xy);
+    check(wn_multiband2d_grad_points(tile(2), in.as<float>(), n, sarg, firstBand, nbands, w, variance, res.as<float>(),
+                                     nullptr), "wn_multiband2d_grad_points");
+    res.download(out3);
+}
+
+void WaveletNoise::WMultibandNoise2D(const float *xy, size_t n, const float *sarg, bool fade, int firstBand, int nbands,
+                                     const float *w, float variance, float *out) const
+{
+    if (!n) return;
+    wnhost::DeviceBuffer in(2 * n * sizeof(float)), fp(n * sizeof(float)), res(n * sizeof(float));
+    in.upload(xy);
+    fp.upload(sarg);
+    check(wn_multiband2d_footprint_points(tile(2), in.as<float>(), fp.as<float>(), n, firstBand, nbands, w, variance,
+                                          fade ? 1 : 0, res.as<float>(), nullptr), "wn_multiband2d_footprint_points");
+    res.download(out);
+}
+
+void WaveletNoise::WMultibandNoise2DGradient(const float *xy, size_t n, const float *sarg, bool fade, int firstBand,
+                                             int nbands, const float *w, float variance, float *out3) const
+{
+    if (!n) return;
+    wnhost::DeviceBuffer in(2 * n * sizeof(float)), fp(n * sizeof(float)), res(3 * n * sizeof(float));
+    in.upload(xy);
+    fp.upload(sarg);
+    check(wn_multiband2d_footprint_grad_points(tile(2), in.as<float>(), fp.as<float>(), n, firstBand, nbands, w, variance,
+                                               fade ? 1 : 0, res.as<float>(), nullptr),
+          "wn_multiband2d_footprint_grad_points");
+    res.download(out3);
 }
 
 // ---- curl noise: the scalar member on the host (bit-identical to the point kernel), the multiband one a batch of one on

@@ -105,6 +105,24 @@ class WaveletNoise {
                          int firstBand, int nbands, const float *w, float variance, float *out) const;
     void WMultibandNoiseGradient(const float *xyz, const float *normals, bool oneNormal, size_t n, const float *s, bool fade,
                                  int firstBand, int nbands, const float *w, float variance, float *out4) const;
+    // WMultibandNoise on the 2-D tile (include/wnoise_multiband2d.h; absent from the reference): bands are evaluate2D at
+    // 2 * p * 2^(firstBand+b), band b runs while (s + firstBand) + b < 0, the sum is divided by sqrt(sum w^2 * variance)
+    // (0.19686: the reference's 2-D constant).  The gradient is taken with respect to p.  The one-sample members are
+    // evaluated on the host (wnhost_multiband2d_footprint), bit-identical to the kernels; the batched forms run on the
+    // device: one s for the call (wn_multiband2d_points / _grad_points), or one per point with the hard cut or the fade
+    // (wn_multiband2d_footprint_points / _grad_points).  out3: records {value, d/dx, d/dy}.
+    float WMultibandNoise2D(const float p[2], float s, int firstBand, int nbands, const float *w, float variance = 0.19686f,
+                            bool fade = false) const;
+    float WMultibandNoise2DGradient(const float p[2], float s, int firstBand, int nbands, const float *w, float grad[2],
+                                    float variance = 0.19686f, bool fade = false) const;
+    void WMultibandNoise2D(const float *xy, size_t n, float s, int firstBand, int nbands, const float *w, float variance,
+                           float *out) const;
+    void WMultibandNoise2DGradient(const float *xy, size_t n, float s, int firstBand, int nbands, const float *w,
+                                   float variance, float *out3) const;
+    void WMultibandNoise2D(const float *xy, size_t n, const float *s, bool fade, int firstBand, int nbands, const float *w,
+                           float variance, float *out) const;
+    void WMultibandNoise2DGradient(const float *xy, size_t n, const float *s, bool fade, int firstBand, int nbands,
+                                   const float *w, float variance, float *out3) const;
     // Divergence-free curl noise (absent from the reference; include/wnoise.h): the curl of the vector potential whose
     // components are evaluate3D (WMultibandNoiseCurl: WMultibandNoise, normal == NULL) of this tile shifted by the whole-cell
     // offsets offsets9 = (x, y, z) of psi0, psi1, psi2; nullptr: defaultCurlOffsets().  evaluate3DCurl(p, ., v) is

@@ -13,6 +13,7 @@
 #include "PerlinNoise.hpp"
 #include "WaveletNoise.h"
 #include "wn_host.hpp"
+#include "wnoise_multiband2d.h"
 
 namespace wnhost {
 
@@ -59,6 +60,20 @@ inline void generate2DOctaveBandNoise(int imageSize, int octave, const std::stri
         wnhost::check(wn_eval2d_grid(noise.tile(2), &g, out, nullptr), "wn_eval2d_grid");
     });
     std::cout << "Generated Wavelet 2D Octave " << octave << " noise: " << outputFile << std::endl;
+}
+
+// A fractal 2-D image in one launch (absent from the reference; include/wnoise_multiband2d.h): WMultibandNoise with
+// evaluate2D bands at p = (i / imageSize) * 4 on both axes, bands while (s + firstBand) + b < 0, divided by
+// sqrt(sum w^2 * variance); the file format of the generators above.
+inline void generate2DMultibandNoise(int imageSize, float s, int firstBand, int nbands, const float *w,
+                                     const std::string &outputFile, WaveletNoise &noise, float variance = 0.19686f)
+{
+    wn_grid g = wnhost::lattice2d(imageSize, 0, 1.0f, 1.0f, WN_GRID_DEFAULT);
+    wnhost::run_grid(imageSize, outputFile, [&](float *out) {
+        wnhost::check(wn_multiband2d_grid(noise.tile(2), &g, s, firstBand, nbands, w, variance, out, nullptr),
+                      "wn_multiband2d_grid");
+    });
+    std::cout << "Generated Wavelet 2D Multiband (" << nbands << " bands) noise: " << outputFile << std::endl;
 }
 
 inline void generate3DSlicedOctaveBandNoise(int imageSize, int octave, const std::string &outputFile,

@@ -103,6 +103,16 @@ float wnhost_multiband3d_footprint(const float *coef, int n, const float p[3], c
                 : wn::multiband_footprint_exact<false, false, false>(a, p, nullptr, s, nullptr);
 }
 
+float wnhost_multiband2d_footprint(const float *coef, int n, const float p[2], float s, int fade, int first_band, int nbands,
+                                   const float *w, float var_per_band, float *grad)
+{
+    if (grad) grad[0] = grad[1] = 0.0f;
+    Footprint a;
+    if (!footprint_setup(a, coef, n, first_band, nbands, w, var_per_band, fade)) return 0.0f;
+    return grad ? wn::multiband2d_footprint_exact<true>(a, a.coef, p, s, grad)
+                : wn::multiband2d_footprint_exact<false>(a, a.coef, p, s, nullptr);
+}
+
 float wnhost_wavelet_multiband_texture_value(const float *coef, int n, double scale, int first_band, int nbands,
                                              const float *w, float var_per_band, int fade, const float xyz[3], float s)
 {

@@ -60,6 +60,13 @@ WNHOST_API float wnhost_eval3d_projected_grad(const float *coef, int n, const fl
 WNHOST_API float wnhost_multiband3d_footprint(const float *coef, int n, const float p[3], const float *normal_or_null,
                                               float s, int fade, int first_band, int nbands, const float *w,
                                               float var_per_band, float *grad_or_null);
+// 2-D WMultibandNoise at ONE footprint s (absent from the reference; include/wnoise_multiband2d.h): the function above on
+// a 2-D tile -- bands are evaluate2D at q_b = 2 * p * 2^(first_band+b), the gradient has two components.  The bit
+// reference of wn_multiband2d_footprint_points and its _grad_ twin and -- at the call's s with fade == 0 -- of the
+// uniform wn_multiband2d_* entry points.  `coef`: n^2 coefficients.  n == 0, coef == NULL or nbands outside 0..8 -> 0 in
+// every channel.
+WNHOST_API float wnhost_multiband2d_footprint(const float *coef, int n, const float p[2], float s, int fade, int first_band,
+                                              int nbands, const float *w, float var_per_band, float *grad_or_null);
 // grey level of wavelet_multiband_texture::value (texture.h; wn_wavelet_multiband_texture_points): the function above
 // (normal == NULL) at (float)((double)xyz * scale) and footprint s, through wavelet_texture's grey; coef == NULL: 0.5
 WNHOST_API float wnhost_wavelet_multiband_texture_value(const float *coef, int n, double scale, int first_band, int nbands,

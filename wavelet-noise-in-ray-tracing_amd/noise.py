@@ -324,6 +324,40 @@ class WaveletNoise:
         check(_lib.wn_eval2d_grad_points(self._handle(2), _ptr(pts), pts.shape[0], _ptr(out), _stream()))
         return out
 
+    # -- WMultibandNoise on the 2-D tile (include/wnoise_multiband2d.h; absent from the reference)
+    def _multiband2d(self, p, s, firstBand, nbands, w, variance, fade, grad):
+        single = _is_scalar_point(p, 2) and not grad
+        pts = _dev(p, torch.float32).reshape(-1, 2)
+        n = pts.shape[0]
+        out = torch.empty((n, 3) if grad else n, dtype=torch.float32, device="cuda")
+        wa = (C.c_float * max(1, nbands))(*[float(x) for x in list(w)[:nbands]])
+        if _per_point(s):
+            sd = _dev(s, torch.float32).reshape(-1)
+            if sd.shape[0] != n:
+                raise ValueError("s: a scalar, or one footprint per point")
+            fn = _lib.wn_multiband2d_footprint_grad_points if grad else _lib.wn_multiband2d_footprint_points
+            check(fn(self._handle(2), _ptr(pts), _ptr(sd), n, int(firstBand), int(nbands), wa, float(variance),
+                     int(bool(fade)), _ptr(out), _stream()))
+            return out
+        fn = _lib.wn_multiband2d_grad_points if grad else _lib.wn_multiband2d_points
+        check(fn(self._handle(2), _ptr(pts), n, float(s), int(firstBand), int(nbands), wa, float(variance), _ptr(out),
+                 _stream()))
+        return float(out.item()) if single else out
+
+    def WMultibandNoise2D(self, p, s, firstBand, nbands, w, variance=0.19686, fade=False):
+        """WMultibandNoise with evaluate2D bands on the 2-D tile, at one point or an (N, 2) batch: sum_b w[b] *
+        evaluate2D(2 * p * 2^(firstBand+b)) over the bands with (s + firstBand) + b < 0, divided by
+        sqrt(sum w^2 * variance) (variance defaults to the reference's 2-D constant 0.19686).  `s`: a scalar -- one
+        footprint for the whole call (wn_multiband2d_points; `fade` is not read) -- or one footprint per point
+        (wn_multiband2d_footprint_points): with fade=True the finest surviving band of a point fades in over one octave."""
+        return self._multiband2d(p, s, firstBand, nbands, w, variance, fade, False)
+
+    def WMultibandNoise2DGradient(self, p, s, firstBand, nbands, w, variance=0.19686, fade=False):
+        """WMultibandNoise2D and its gradient with respect to p: an (N, 3) CUDA tensor of {value, d/dx, d/dy}
+        (wn_multiband2d_grad_points / wn_multiband2d_footprint_grad_points); the value column has the bits of
+        WMultibandNoise2D."""
+        return self._multiband2d(p, s, firstBand, nbands, w, variance, fade, True)
+
     def evaluate3DProjectedGradient(self, p, normal):
         """evaluate3DProjected and its gradient with respect to p, the normal held fixed (wn_eval3d_projected_grad_points):
         (N, 4).  `normal`: one for all points, or one per point.  The value column has the bits of evaluate3DProjected;
@@ -697,6 +731,39 @@ def generate2DOctaveBandNoise(imageSize, octave, outputFile, noise, flags=WN_GRI
     out = out.view(imageSize, imageSize)
     _write(out, outputFile)
     return out
+
+
+def _multiband2d_image(fn, planes, noise, image_size, s, firstBand, nbands, w, variance, den, out):
+    """[planes, ny, nx] from one launch of a wn_multiband2d_*grid entry point; image_size: an int or (nx, ny)."""
+    nx, ny = (int(image_size),) * 2 if np.ndim(image_size) == 0 else (int(image_size[0]), int(image_size[1]))
+    w = [1.0] * nbands if w is None else list(w)
+    g = GridSpec(nx if den is None else int(den), nx, ny)
+    n = planes * ny * nx
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device="cuda")
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= n
+    gc = g.c()
+    wa = (C.c_float * max(1, nbands))(*[float(x) for x in w[:nbands]])
+    check(fn(noise._handle(2), C.byref(gc), float(s), int(firstBand), int(nbands), wa, float(variance), _ptr(out), _stream()))
+    return out[:n].view(planes, ny, nx)
+
+
+def generate2DMultibandNoise(noise, image_size, s=-16.0, firstBand=0, nbands=5, w=None, variance=0.19686, den=None,
+                             outputFile=None, out=None):
+    """A fractal 2-D image in one launch (wn_multiband2d_grid): WMultibandNoise with evaluate2D bands at p = (i/den)*4 on
+    both axes (generate2DOctaveBandNoise's lattice before its octave scaling), [ny, nx].  image_size: an int (a square
+    image) or (nx, ny); den defaults to nx; w to unit weights; outputFile: the raw float32 format of the other generators."""
+    img = _multiband2d_image(_lib.wn_multiband2d_grid, 1, noise, image_size, s, firstBand, nbands, w, variance, den, out)[0]
+    _write(img, outputFile)
+    return img
+
+
+def generate2DMultibandNoiseGradient(noise, image_size, s=-16.0, firstBand=0, nbands=5, w=None, variance=0.19686,
+                                     den=None, out=None):
+    """generate2DMultibandNoise with the gradient with respect to p (wn_multiband2d_grad_grid): [3, ny, nx] -- value, d/dx,
+    d/dy; the value plane has the bits of generate2DMultibandNoise."""
+    return _multiband2d_image(_lib.wn_multiband2d_grad_grid, 3, noise, image_size, s, firstBand, nbands, w, variance, den,
+                              out)
 
 
 def generate3DSlicedOctaveBandNoise(imageSize, octave, outputFile, noise, flags=WN_GRID_EXACT, out=None):
