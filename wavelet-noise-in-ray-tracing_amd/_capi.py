@@ -1,5 +1,5 @@
 """ctypes binding of libwnoise_hip.so (include/wnoise.h, include/wnoise_perlin_curl.h, include/wnoise_footprint.h,
-include/wnoise_perlin_footprint.h, include/wnoise_multiband2d.h).
+include/wnoise_perlin_footprint.h, include/wnoise_multiband2d.h, include/wnoise_advect.h).
 
 The library is the product: if it is missing or fails to load this module raises, it never
 substitutes a CPU implementation.
@@ -158,6 +158,22 @@ MULTIBAND2D_SIGNATURES = {
     "wn_multiband2d_footprint_grad_points": _points_fp_mb2d,
 }
 
+# name -> (restype, argtypes); every symbol include/wnoise_advect.h declares, and its wn_advect.
+WN_ADVECT_EULER, WN_ADVECT_MIDPOINT, WN_ADVECT_RK4 = range(3)
+
+
+class wn_advect(C.Structure):
+    _fields_ = [("method", C.c_int32), ("steps", C.c_int32), ("h", C.c_float), ("gain", C.c_float),
+                ("drift", C.c_float * 3), ("traj_every", C.c_int32)]
+
+
+_ap = C.POINTER(wn_advect)
+ADVECT_SIGNATURES = {
+    "wn_eval3d_curl_advect_points": (_i, [_vp, _vp, _sz, _i32p, _ap, _vp, _vp, _vp]),
+    "wn_multiband3d_curl_advect_points": (_i, [_vp, _vp, _sz, _i32p, _f, _i, _i, _fp, _f, _ap, _vp, _vp, _vp]),
+    "wn_advect_launch_steps": (_i, []),
+}
+
 _lib = None
 
 
@@ -172,7 +188,8 @@ def load():
             "__graft_entry__.build()).  This package has no CPU implementation.")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (*SIGNATURES.items(), *PERLIN_CURL_SIGNATURES.items(), *FOOTPRINT_SIGNATURES.items(),
-                              *PERLIN_FOOTPRINT_SIGNATURES.items(), *MULTIBAND2D_SIGNATURES.items()):
+                              *PERLIN_FOOTPRINT_SIGNATURES.items(), *MULTIBAND2D_SIGNATURES.items(),
+                              *ADVECT_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

@@ -172,6 +172,29 @@ inline int multiband_bands(float s, int first_band, int nbands, const float *w_h
     return WN_OK;
 }
 
+// What wn::eval3d_curl_exact / multiband_curl_exact read (wn_wavelet_curl.hip, wn_wavelet_advect.hip).
+struct CurlEval : Bands {
+    const float *coef;
+    int n, nmask;
+    int off[9]; // (x, y, z) of psi0, psi1, psi2, each in [0, n)
+    int mb;     // 0: evaluate3D potentials; 1: WMultibandNoise potentials (nbands may be 0: no band is active)
+};
+
+// The first checks of a curl entry point, then the tile's fields of CurlEval (its padded copy when it has one) and the
+// offsets reduced with the reference's Mod.
+inline int curl_eval_args(const wn_tile *tile, const int32_t *offsets9_host, const char *entry, CurlEval *e)
+{
+    const int rc = check_tile(tile, 3, entry);
+    if (rc) return rc;
+    if (!offsets9_host) return fail(WN_ERR_INVALID, "%s: offsets9_host is NULL", entry);
+    *e = CurlEval{};
+    e->coef = tile->dev_padded ? tile->dev_padded : tile->dev;
+    e->n = tile->n;
+    e->nmask = pow2_mask(tile->n);
+    for (int i = 0; i < 9; ++i) e->off[i] = tile->n > 0 ? dmod(offsets9_host[i], tile->n, e->nmask) : 0;
+    return WN_OK;
+}
+
 // The *_try functions below launch their kernel when the lattice is in its regime and return WN_OK (or the launch's
 // error); outside it they launch nothing and return kDeclined, and the caller offers the lattice to the next kernel.
 constexpr int kDeclined = -1;

@@ -26,15 +26,9 @@
 namespace {
 
 using wn::GridArgs;
+using wn::CurlEval;
+using wn::curl_eval_args;
 using wn::kMaxBands;
-
-// What wn::eval3d_curl_exact / multiband_curl_exact read.
-struct CurlEval : wn::Bands {
-    const float *coef;
-    int n, nmask;
-    int off[9]; // (x, y, z) of psi0, psi1, psi2, each in [0, n)
-    int mb;     // 0: evaluate3D potentials; 1: WMultibandNoise potentials (nbands may be 0: no band is active)
-};
 
 // ---- point lists -----------------------------------------------------------------------------------------------------
 struct CurlPointsArgs {
@@ -256,20 +250,6 @@ int curl_sep_try(const wn_tile *tile, const GridArgs &g, const int off[9], int n
         WN_LAUNCH_CHECK("curl3d_grid_sep_kernel");
         return (int)WN_OK;
     });
-}
-
-// The tile's fields of CurlEval (its padded copy when it has one) and the offsets reduced with the reference's Mod.
-int curl_eval_args(const wn_tile *tile, const int32_t *offsets9_host, const char *entry, CurlEval *e)
-{
-    const int rc = wn::check_tile(tile, 3, entry);
-    if (rc) return rc;
-    if (!offsets9_host) return wn::fail(WN_ERR_INVALID, "%s: offsets9_host is NULL", entry);
-    *e = CurlEval{};
-    e->coef = tile->dev_padded ? tile->dev_padded : tile->dev;
-    e->n = tile->n;
-    e->nmask = wn::pow2_mask(tile->n);
-    for (int i = 0; i < 9; ++i) e->off[i] = tile->n > 0 ? wn::dmod(offsets9_host[i], tile->n, e->nmask) : 0;
-    return WN_OK;
 }
 
 int launch_curl_points(const wn_tile *tile, const CurlEval &e, const float *xyz_dev, size_t n, float *out3_dev,

@@ -8,6 +8,7 @@
 
 #include "scalar_eval.h"
 #include "wn_host.hpp"
+#include "wnoise_advect.h"
 #include "wnoise_footprint.h"
 #include "wnoise_multiband2d.h"
 
@@ -415,6 +416,65 @@ void WaveletNoise::WMultibandNoiseCurl(const float *xyz, size_t n, const int *of
     check(wn_multiband3d_curl_points(tile(3), in.as<float>(), n, offsets9 ? offsets9 : def, sarg, firstBand, nbands, w,
                                      variance, res.as<float>(), nullptr), "wn_multiband3d_curl_points");
     res.download(out3);
+}
+
+// ---- particles through the curl field: the scalar member traced on the host (bit-identical to the kernel), the batched ones
+// one call of the C ABI, which checks `a`; the trajectory buffer exists only when a.traj_every asks for it
+namespace {
+
+template <typename Call>
+void advect_batch(const float *xyz, size_t n, const wn_advect &a, float *xyz_out, float *traj, Call call, const char *what)
+{
+    if (!n) return;
+    const bool snaps = a.traj_every >= 1 && a.steps >= 0 && traj;
+    const size_t traj_bytes = snaps ? ((size_t)(a.steps / a.traj_every) + 1) * 3 * n * sizeof(float) : 0;
+    wnhost::DeviceBuffer pos(3 * n * sizeof(float)), path(traj_bytes ? traj_bytes : sizeof(float));
+    pos.upload(xyz);
+    check(call(pos.as<float>(), snaps ? path.as<float>() : nullptr), what); // in place on the device
+    if (snaps) check(wn_copy_d2h(traj, path.get(), traj_bytes, nullptr), "wn_copy_d2h");
+    pos.download(xyz_out);
+}
+
+} // namespace
+
+void WaveletNoise::advectCurl(const float p[3], const wn_advect &a, const int *offsets9, float p_out[3], float *traj) const
+{
+    if (tileDims == 2) return advectCurl(p, 1, a, offsets9, p_out, traj);
+    int def[9];
+    if (!offsets9) defaultCurlOffsets(def);
+    if (wnhost_eval3d_curl_advect(noiseCoefficients.empty() ? nullptr : noiseCoefficients.data(), tileSizeN, p,
+                                  offsets9 ? offsets9 : def, &a, p_out, traj))
+        throw std::runtime_error("advectCurl: a method outside 0..2, negative steps or traj_every, a non-finite h, gain or "
+                                 "drift, or a trajectory without a buffer");
+}
+
+void WaveletNoise::advectCurl(const float *xyz, size_t n, const wn_advect &a, const int *offsets9, float *xyz_out,
+                              float *traj) const
+{
+    int def[9];
+    if (!offsets9) defaultCurlOffsets(def);
+    advect_batch(xyz, n, a, xyz_out, traj, [&](float *pos, float *path) {
+        return wn_eval3d_curl_advect_points(tile(3), pos, n, offsets9 ? offsets9 : def, &a, pos, path, nullptr);
+    }, "wn_eval3d_curl_advect_points");
+}
+
+void WaveletNoise::WMultibandNoiseAdvectCurl(const float p[3], const wn_advect &a, const int *offsets9, float sarg,
+                                             int firstBand, int nbands, const float *w, float p_out[3], float *traj,
+                                             float variance) const
+{
+    WMultibandNoiseAdvectCurl(p, 1, a, offsets9, sarg, firstBand, nbands, w, variance, p_out, traj);
+}
+
+void WaveletNoise::WMultibandNoiseAdvectCurl(const float *xyz, size_t n, const wn_advect &a, const int *offsets9, float sarg,
+                                             int firstBand, int nbands, const float *w, float variance, float *xyz_out,
+                                             float *traj) const
+{
+    int def[9];
+    if (!offsets9) defaultCurlOffsets(def);
+    advect_batch(xyz, n, a, xyz_out, traj, [&](float *pos, float *path) {
+        return wn_multiband3d_curl_advect_points(tile(3), pos, n, offsets9 ? offsets9 : def, sarg, firstBand, nbands, w,
+                                                 variance, &a, pos, path, nullptr);
+    }, "wn_multiband3d_curl_advect_points");
 }
 
 // ---- batched members ----------------------------------------------------------------------------------

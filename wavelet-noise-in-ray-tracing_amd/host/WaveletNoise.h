@@ -20,7 +20,8 @@
 #include <string>
 #include <vector>
 
-struct wn_tile; // include/wnoise.h
+struct wn_tile;   // include/wnoise.h
+struct wn_advect; // include/wnoise_advect.h
 
 // Statistical analysis structure (WaveletNoise.h:11-18)
 struct DataStats {
@@ -134,6 +135,21 @@ class WaveletNoise {
                              float v[3], float variance = 0.18402f) const;
     void WMultibandNoiseCurl(const float *xyz, size_t n, const int *offsets9, float s, int firstBand, int nbands,
                              const float *w, float variance, float *out3) const;
+    // Particles moved through that curl field (absent from the reference; include/wnoise_advect.h, whose wn_advect `a`
+    // carries method, steps, h, gain, drift and traj_every): the position after a.steps time steps through
+    // gain * curl + drift goes to p_out / xyz_out (which may be the input), and with a.traj_every = e >= 1 the positions after
+    // steps 0, e, 2e, ... to traj, a.steps / e + 1 snapshots of n points each ([snapshot][n][3]).  advectCurl(p, ., p_out)
+    // is traced on the host (scalar_eval.h), bit-identical to wn_eval3d_curl_advect_points, which the batched form calls;
+    // WMultibandNoiseAdvectCurl is batched (wn_multiband3d_curl_advect_points), its scalar form a batch of one.
+    void advectCurl(const float p[3], const wn_advect &a, const int *offsets9, float p_out[3], float *traj = nullptr) const;
+    void advectCurl(const float *xyz, size_t n, const wn_advect &a, const int *offsets9, float *xyz_out,
+                    float *traj = nullptr) const;
+    void WMultibandNoiseAdvectCurl(const float p[3], const wn_advect &a, const int *offsets9, float s, int firstBand,
+                                   int nbands, const float *w, float p_out[3], float *traj = nullptr,
+                                   float variance = 0.18402f) const;
+    void WMultibandNoiseAdvectCurl(const float *xyz, size_t n, const wn_advect &a, const int *offsets9, float s,
+                                   int firstBand, int nbands, const float *w, float variance, float *xyz_out,
+                                   float *traj = nullptr) const;
     // (0,0,0), (n/3,)*3, (2n/3,)*3 with integer division: a default only, not a measured decorrelation.
     void defaultCurlOffsets(int offsets9[9]) const;
     // The device-resident tile (an empty tile before generate*); for the C-ABI grid entry points.

@@ -8,6 +8,7 @@
 #include <cstdlib>
 
 #include "wn_eval.hpp"
+#include "wnoise_advect.h"
 
 namespace {
 
@@ -75,6 +76,34 @@ void wnhost_eval3d_curl(const float *coef, int n, const float p[3], const int of
     int off[9];
     for (int i = 0; i < 9; ++i) off[i] = wn::dmod(offsets9[i], n, nmask);
     wn::eval3d_curl_exact(coef, n, nmask, off, p[0], p[1], p[2], v);
+}
+
+int wnhost_eval3d_curl_advect(const float *coef, int n, const float p_in[3], const int offsets9[9], const wn_advect *a,
+                              float p_out[3], float *traj)
+{
+    if (!a || a->method < WN_ADVECT_EULER || a->method > WN_ADVECT_RK4 || a->steps < 0 || a->traj_every < 0) return 1;
+    if (!std::isfinite(a->h) || !std::isfinite(a->gain) || !std::isfinite(a->drift[0]) || !std::isfinite(a->drift[1]) ||
+        !std::isfinite(a->drift[2]) || (a->traj_every && !traj))
+        return 1;
+    if (!coef || n <= 0) n = 0;
+    const int nmask = wn::pow2_mask(n);
+    int off[9];
+    for (int i = 0; i < 9; ++i) off[i] = n ? wn::dmod(offsets9[i], n, nmask) : 0;
+    const auto velocity = [&](const float q[3], float v[3]) { wn::eval3d_curl_exact(coef, n, nmask, off, q[0], q[1], q[2], v); };
+    const float h = a->h, h2 = 0.5f * a->h, h6 = a->h / 6.0f;
+    float p[3] = {p_in[0], p_in[1], p_in[2]};
+    if (a->traj_every) traj[0] = p[0], traj[1] = p[1], traj[2] = p[2];
+    for (int t = 1; t <= a->steps; ++t) {
+        if (a->method == WN_ADVECT_EULER) wn::advect_step<WN_ADVECT_EULER>(p, h, h2, h6, a->gain, a->drift, velocity);
+        else if (a->method == WN_ADVECT_MIDPOINT) wn::advect_step<WN_ADVECT_MIDPOINT>(p, h, h2, h6, a->gain, a->drift, velocity);
+        else wn::advect_step<WN_ADVECT_RK4>(p, h, h2, h6, a->gain, a->drift, velocity);
+        if (a->traj_every && t % a->traj_every == 0) {
+            float *snap = traj + 3 * (size_t)(t / a->traj_every);
+            snap[0] = p[0], snap[1] = p[1], snap[2] = p[2];
+        }
+    }
+    p_out[0] = p[0], p_out[1] = p[1], p_out[2] = p[2];
+    return 0;
 }
 
 float wnhost_eval3d_projected(const float *coef, int n, const float p[3], const float nrm[3])

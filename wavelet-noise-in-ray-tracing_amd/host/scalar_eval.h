@@ -44,6 +44,14 @@ WNHOST_API float wnhost_eval3d_grad(const float *coef, int n, const float p[3], 
 // over the offset coefficients and one subtraction per component: the bits of wn_eval3d_curl_points.
 // n == 0 or coef == NULL -> 0 in all three.
 WNHOST_API void wnhost_eval3d_curl(const float *coef, int n, const float p[3], const int offsets9[9], float v[3]);
+// One particle traced through that curl field (include/wnoise_advect.h, whose wn_advect `a` is: method, steps, h, gain, drift,
+// traj_every): p_out receives the position after a->steps steps of wn::advect_step, the step the device kernel runs, around
+// wnhost_eval3d_curl -- the bits of wn_eval3d_curl_advect_points.  traj (read only when a->traj_every >= 1; may then not
+// be NULL): a->steps / a->traj_every + 1 packed triples, the positions after steps 0, e, 2e, ...  p_out may be p_in.
+// n == 0 or coef == NULL: v = 0, pure drift.  Returns 0, or 1 and writes nothing when `a` is one that entry point refuses.
+struct wn_advect;
+WNHOST_API int wnhost_eval3d_curl_advect(const float *coef, int n, const float p_in[3], const int offsets9[9],
+                                         const struct wn_advect *a, float p_out[3], float *traj);
 WNHOST_API float wnhost_eval3d_projected(const float *coef, int n, const float p[3], const float normal[3]); // WaveletNoise.cpp:218-265
 // evaluate3DProjected and its gradient with respect to p, the normal held fixed (absent from the reference): returns the
 // value (the bits of wnhost_eval3d_projected, its 1e-6 cut included), writes the gradient of the uncut sum over the same

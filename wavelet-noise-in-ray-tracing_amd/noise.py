@@ -316,6 +316,42 @@ class WaveletNoise:
                                               float(0.18402 if variance is None else variance), _ptr(out), _stream()))
         return out
 
+    # -- particles moved through that curl field (include/wnoise_advect.h; absent from the reference)
+    _ADVECT_METHODS = {"euler": _capi.WN_ADVECT_EULER, "midpoint": _capi.WN_ADVECT_MIDPOINT, "rk4": _capi.WN_ADVECT_RK4}
+
+    def _advect(self, call, pts, h, steps, method, gain, drift, trajectory_every):
+        if method not in self._ADVECT_METHODS:
+            raise ValueError(f"method: one of {sorted(self._ADVECT_METHODS)}")
+        pts = _dev(pts, torch.float32).reshape(-1, 3)
+        n, steps, every = pts.shape[0], int(steps), int(trajectory_every)
+        a = _capi.wn_advect(self._ADVECT_METHODS[method], steps, float(h), float(gain),
+                            (C.c_float * 3)(*([0.0] * 3 if drift is None else [float(x) for x in drift])), every)
+        out = torch.empty((n, 3), dtype=torch.float32, device="cuda")
+        traj = torch.empty((steps // every + 1, n, 3), dtype=torch.float32, device="cuda") if every >= 1 and steps >= 0 else None
+        check(call(_ptr(pts), n, C.byref(a), _ptr(out), _ptr(traj)))
+        return out if traj is None else (out, traj)
+
+    def advectCurl(self, pts, h, steps, method="rk4", offsets=None, gain=1.0, drift=None, trajectory_every=0):
+        """An (N, 3) batch of particles moved `steps` time steps of size h (negative: backwards) through the velocity
+        gain * evaluate3DCurl(., offsets) + drift, all steps inside the kernel (wn_eval3d_curl_advect_points).  method:
+        "euler", "midpoint" or "rk4".  Returns the final (N, 3) positions; with trajectory_every = e >= 1 also the
+        (steps // e + 1, N, 3) positions after steps 0, e, 2e, ...  Float32 with every operation rounded on its own: the
+        bits of stepping with evaluate3DCurl and separately rounded float32 tensor operations."""
+        off = self._curl_offsets(offsets)
+        return self._advect(lambda p, n, a, out, traj: _lib.wn_eval3d_curl_advect_points(
+            self._handle(3), p, n, off, a, out, traj, _stream()), pts, h, steps, method, gain, drift, trajectory_every)
+
+    def WMultibandNoiseAdvectCurl(self, pts, h, steps, s, firstBand, nbands, w, variance=None, method="rk4", offsets=None,
+                                  gain=1.0, drift=None, trajectory_every=0):
+        """advectCurl through gain * WMultibandNoiseCurl(., s, firstBand, nbands, w, variance, offsets) + drift
+        (wn_multiband3d_curl_advect_points)."""
+        off = self._curl_offsets(offsets)
+        wa = (C.c_float * max(1, nbands))(*[float(x) for x in list(w)[:nbands]])
+        var = float(0.18402 if variance is None else variance)
+        return self._advect(lambda p, n, a, out, traj: _lib.wn_multiband3d_curl_advect_points(
+            self._handle(3), p, n, off, float(s), int(firstBand), int(nbands), wa, var, a, out, traj, _stream()),
+            pts, h, steps, method, gain, drift, trajectory_every)
+
     def evaluate2DGradient(self, p):
         """evaluate2D and its gradient at one point or an (N, 2) batch (wn_eval2d_grad_points): an (N, 3) CUDA tensor of
         {value, d/dx, d/dy}; the value column has the bits of evaluate2D."""
