@@ -185,7 +185,9 @@ PERLIN_GRAD_GRIDS = [("turb1", "wn_perlin_turb_grad_grid"), ("noise_coarse", "wn
 # ---- section 5: point lists and textures ---------------------------------------------------------------------------------
 # Reaches the plane-ordered kernels; ragged.  Only wn_eval3d_points, wn_multiband3d_points and the 3-D wavelet texture have
 # such a second path for long lists (csrc/wn_wavelet_points.hip); the projected, 2-D gradient, curl, Perlin and noise-texture
-# lists are one grid-stride kernel at every length, so they stop at 1000 or 5003 points (more than one workgroup, ragged).
+# lists are one grid-stride kernel at every length, and stop here at 1000 or 5003 points (more than one workgroup, ragged):
+# one trip through that kernel's loop.  The lists past its workgroup cap (4,194,304 points and more), where a lane takes a
+# second trip, are in tests/test_gpu_stride_pass.py, in guard frames of the same kind.
 LONG = tp.SORT_MIN + 4097
 SLAB_N = tp.SLAB_MIN + 4097   # reaches the row-slab kernel
 W8 = tg.W8
