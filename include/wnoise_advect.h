@@ -9,7 +9,7 @@
  *     k(q) = gain * v(q) + drift
  * inside ONE kernel launch per kAdvectLaunchSteps steps (csrc/wn_wavelet_advect.hip; launches are chained on `stream`):
  * the position and the stage sums stay in registers between steps.  The field does not depend on time and has no
- * boundaries; Perlin potentials are not served.
+ * boundaries; Perlin potentials are served by wnoise_perlin_advect.h.
  *
  * Arithmetic, which is the contract.  Everything is float32; every product and every sum is rounded on its own (unfused).
  * Per component:

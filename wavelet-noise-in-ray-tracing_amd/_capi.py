@@ -1,5 +1,6 @@
 """ctypes binding of libwnoise_hip.so (include/wnoise.h, include/wnoise_perlin_curl.h, include/wnoise_footprint.h,
-include/wnoise_perlin_footprint.h, include/wnoise_multiband2d.h, include/wnoise_advect.h).
+include/wnoise_perlin_footprint.h, include/wnoise_multiband2d.h, include/wnoise_advect.h,
+include/wnoise_perlin_advect.h).
 
 The library is the product: if it is missing or fails to load this module raises, it never
 substitutes a CPU implementation.
@@ -174,6 +175,12 @@ ADVECT_SIGNATURES = {
     "wn_advect_launch_steps": (_i, []),
 }
 
+# name -> (restype, argtypes); every symbol include/wnoise_perlin_advect.h declares.
+PERLIN_ADVECT_SIGNATURES = {
+    "wn_perlin_curl_advect_points": (_i, [_vp, _vp, _sz, _i, _i, _i32p, _ap, _vp, _vp, _vp]),
+    "wn_perlin_advect_launch_steps": (_i, [_i, _i, _i]),
+}
+
 _lib = None
 
 
@@ -189,7 +196,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (*SIGNATURES.items(), *PERLIN_CURL_SIGNATURES.items(), *FOOTPRINT_SIGNATURES.items(),
                               *PERLIN_FOOTPRINT_SIGNATURES.items(), *MULTIBAND2D_SIGNATURES.items(),
-                              *ADVECT_SIGNATURES.items()):
+                              *ADVECT_SIGNATURES.items(), *PERLIN_ADVECT_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

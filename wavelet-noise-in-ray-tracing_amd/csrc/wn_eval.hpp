@@ -586,44 +586,45 @@ WN_EVAL_FN void multiband_curl_exact(const A &a, const float p[3], float v[3])
 }
 
 // ---- one explicit time step of a particle through a velocity field (include/wnoise_advect.h; absent from the reference) --
-// METHOD: WN_ADVECT_EULER / _MIDPOINT / _RK4 (0, 1, 2).  velocity(q, v) writes the field's v(q); the stage velocity is
-// k(q) = gain * v(q) + drift, one multiply, then one add per component.  h2 = 0.5f * h and h6 = h / 6.0f come from the caller,
-// formed once.  Every product and every sum below rounds on its own (float32, unfused), so p' has the bits of the same
-// operations written out with separately rounded float32 arithmetic around the field's own entry point:
+// METHOD: WN_ADVECT_EULER / _MIDPOINT / _RK4 (0, 1, 2).  T: float (the wavelet potentials, include/wnoise_advect.h) or double
+// (the Perlin potentials, include/wnoise_perlin_advect.h).  velocity(q, v) writes the field's v(q); the stage velocity is
+// k(q) = gain * v(q) + drift, one multiply, then one add per component.  h2 = T(0.5) * h and h6 = h / T(6) come from the
+// caller, formed once.  Every product and every sum below rounds on its own (in T, unfused), so p' has the bits of the same
+// operations written out with separately rounded arithmetic of that type around the field's own entry point:
 //     Euler     p' = p + h * k(p)
 //     midpoint  p' = p + h * k(p + h2 * k1),                                  k1 = k(p)
 //     RK4       p' = p + h6 * (((k1 + 2 * k2) + 2 * k3) + k4),                k2 = k(p + h2 * k1), k3 = k(p + h2 * k2),
 //                                                                              k4 = k(p + h * k3)
 // RK4 keeps one running sum of the stage velocities beside p and the stage point.
-template <int METHOD, typename V>
-WN_EVAL_FN void advect_step(float p[3], float h, float h2, float h6, float gain, const float drift[3], const V &velocity)
+template <int METHOD, typename T, typename V>
+WN_EVAL_FN void advect_step(T p[3], T h, T h2, T h6, T gain, const T drift[3], const V &velocity)
 {
     static_assert(METHOD >= 0 && METHOD <= 2, "Euler, midpoint or RK4");
-    auto stage = [&](const float q[3], float k[3]) {
-        float v[3];
+    auto stage = [&](const T q[3], T k[3]) {
+        T v[3];
         velocity(q, v);
         WN_UNROLL
         for (int c = 0; c < 3; ++c) k[c] = gain * v[c] + drift[c];
     };
-    auto from_p = [&](float f, const float k[3], float q[3]) {
+    auto from_p = [&](T f, const T k[3], T q[3]) {
         WN_UNROLL
         for (int c = 0; c < 3; ++c) q[c] = p[c] + f * k[c];
     };
-    float k[3], q[3];
+    T k[3], q[3];
     stage(p, k);
     if constexpr (METHOD == 1) {
         from_p(h2, k, q);
         stage(q, k);
     } else if constexpr (METHOD == 2) {
-        float sum[3] = {k[0], k[1], k[2]};
+        T sum[3] = {k[0], k[1], k[2]};
         from_p(h2, k, q);
         stage(q, k);
         WN_UNROLL
-        for (int c = 0; c < 3; ++c) sum[c] = sum[c] + 2.0f * k[c];
+        for (int c = 0; c < 3; ++c) sum[c] = sum[c] + T(2) * k[c];
         from_p(h2, k, q);
         stage(q, k);
         WN_UNROLL
-        for (int c = 0; c < 3; ++c) sum[c] = sum[c] + 2.0f * k[c];
+        for (int c = 0; c < 3; ++c) sum[c] = sum[c] + T(2) * k[c];
         from_p(h, k, q);
         stage(q, k);
         WN_UNROLL

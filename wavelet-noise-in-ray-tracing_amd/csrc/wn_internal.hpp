@@ -13,6 +13,7 @@
 
 #include "wn_eval.hpp" // dmod, pow2_mask, bspline and the exact evaluators, shared with host/scalar_eval.cpp
 #include "wnoise.h"
+#include "wnoise_advect.h"
 
 typedef float v4f __attribute__((ext_vector_type(4)));
 
@@ -192,6 +193,20 @@ inline int curl_eval_args(const wn_tile *tile, const int32_t *offsets9_host, con
     e->n = tile->n;
     e->nmask = pow2_mask(tile->n);
     for (int i = 0; i < 9; ++i) e->off[i] = tile->n > 0 ? dmod(offsets9_host[i], tile->n, e->nmask) : 0;
+    return WN_OK;
+}
+
+// The checks of an advection call's wn_advect (wn_wavelet_advect.hip, wn_perlin_advect.hip).
+inline int check_advect(const wn_advect *a)
+{
+    if (!a) return fail(WN_ERR_INVALID, "wn_advect is NULL");
+    if (a->method < WN_ADVECT_EULER || a->method > WN_ADVECT_RK4)
+        return fail(WN_ERR_INVALID, "wn_advect.method must be 0 (Euler), 1 (midpoint) or 2 (RK4) (got %d)", a->method);
+    if (a->steps < 0) return fail(WN_ERR_INVALID, "wn_advect.steps must be >= 0 (got %d)", a->steps);
+    if (a->traj_every < 0) return fail(WN_ERR_INVALID, "wn_advect.traj_every must be >= 0 (got %d)", a->traj_every);
+    if (!std::isfinite(a->h) || !std::isfinite(a->gain) || !std::isfinite(a->drift[0]) || !std::isfinite(a->drift[1]) ||
+        !std::isfinite(a->drift[2]))
+        return fail(WN_ERR_INVALID, "wn_advect.h, gain and drift must be finite");
     return WN_OK;
 }
 

@@ -89,25 +89,12 @@ void launch_method(int method, dim3 grid, hipStream_t stream, const AdvectArgs &
     else hipLaunchKernelGGL((curl3d_advect_kernel<PADDED, MB, WN_ADVECT_RK4>), grid, block, 0, stream, a);
 }
 
-int check_advect(const wn_advect *a)
-{
-    if (!a) return wn::fail(WN_ERR_INVALID, "wn_advect is NULL");
-    if (a->method < WN_ADVECT_EULER || a->method > WN_ADVECT_RK4)
-        return wn::fail(WN_ERR_INVALID, "wn_advect.method must be 0 (Euler), 1 (midpoint) or 2 (RK4) (got %d)", a->method);
-    if (a->steps < 0) return wn::fail(WN_ERR_INVALID, "wn_advect.steps must be >= 0 (got %d)", a->steps);
-    if (a->traj_every < 0) return wn::fail(WN_ERR_INVALID, "wn_advect.traj_every must be >= 0 (got %d)", a->traj_every);
-    if (!std::isfinite(a->h) || !std::isfinite(a->gain) || !std::isfinite(a->drift[0]) || !std::isfinite(a->drift[1]) ||
-        !std::isfinite(a->drift[2]))
-        return wn::fail(WN_ERR_INVALID, "wn_advect.h, gain and drift must be finite");
-    return WN_OK;
-}
-
 // The entry points after their tile, offset and band checks: the checks of `a` and of the three buffers, then the chain of
 // launches.
 int advect_points(const wn_tile *tile, const CurlEval &e, const float *in_dev, size_t n, const wn_advect *adv, float *out_dev,
                   float *traj_dev, hipStream_t stream)
 {
-    const int rc = check_advect(adv);
+    const int rc = wn::check_advect(adv);
     if (rc || n == 0) return rc;
     if (!in_dev || !out_dev) return wn::fail(WN_ERR_INVALID, "xyz_in_dev / xyz_out_dev is NULL");
     const int every = adv->traj_every;

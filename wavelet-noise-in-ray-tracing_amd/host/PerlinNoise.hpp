@@ -9,6 +9,7 @@
 
 #include "scalar_eval.h"
 #include "wn_host.hpp"
+#include "wnoise_perlin_advect.h"
 #include "wnoise_perlin_curl.h"
 
 class PerlinNoise {
@@ -64,6 +65,24 @@ class PerlinNoise {
         wnhost::check(wn_perlin_curl_points(perm_, in.as<double>(), n, reinterpret_cast<const int32_t *>(curl_offsets(offsets9)),
                                             res.as<double>(), nullptr), "wn_perlin_curl_points");
         res.download(out3);
+    }
+
+    // additive: particles moved through that curl field (include/wnoise_perlin_advect.h, whose wn_advect `a` is: method,
+    // steps, h, gain, drift, traj_every); this class serves noise_curl only, so the potentials are WN_PERLIN_CURL_NOISE.
+    // With a.traj_every = e >= 1 the positions after steps 0, e, 2e, ... go to traj ([snapshot][n][3]).  Scalar traced on
+    // the host, batched through the GPU; bit-identical to each other.
+    void advect_curl(double x, double y, double z, const wn_advect &a, const int *offsets9, double p_out[3],
+                     double *traj = nullptr) const
+    {
+        const double xyz[3] = {x, y, z};
+        if (wnhost_perlin_curl_advect(p.data(), WN_PERLIN_CURL_NOISE, 0, xyz, curl_offsets(offsets9), &a, p_out, traj))
+            throw std::runtime_error("advect_curl: a method outside 0..2, negative steps or traj_every, a non-finite h, gain or "
+                                     "drift, or a trajectory without a buffer");
+    }
+    void advect_curl(const double *xyz, size_t n, const wn_advect &a, const int *offsets9, double *xyz_out,
+                     double *traj = nullptr) const
+    {
+        wnhost::perlin_advect_batch(perm_, xyz, n, WN_PERLIN_CURL_NOISE, 0, curl_offsets(offsets9), a, xyz_out, traj);
     }
 
     const std::vector<int> &table() const { return p; }

@@ -6,7 +6,7 @@
 // reference's operation order; the scalar members are evaluated on the host from the mirrored table (scalar_eval.h;
 // WN_SCALAR_ON_DEVICE=1: by the resident scalar kernel).  Bit-identical either way.
 // Additive: turb() (RTOW; absent from the reference), batched overloads, analytic gradients, curl noise
-// and octave limiting by a footprint per sample.
+// particles advected through it, and octave limiting by a footprint per sample.
 #ifndef PERLIN_H
 #define PERLIN_H
 
@@ -17,6 +17,7 @@
 #include "scalar_eval.h"
 #include "vec3.h"
 #include "wn_host.hpp"
+#include "wnoise_perlin_advect.h"
 #include "wnoise_perlin_curl.h"
 #include "wnoise_perlin_footprint.h"
 
@@ -141,6 +142,31 @@ class perlin {
     void noise_curl(const float *xyz, size_t n, double *out3, const int *offsets9 = nullptr) const { curl_vec3(xyz, n, WN_PERLIN_CURL_NOISE, 0, offsets9, out3); }
     void turb_curl(const float *xyz, size_t n, double *out3, int depth = 7, const int *offsets9 = nullptr) const { curl_vec3(xyz, n, WN_PERLIN_CURL_TURB, depth, offsets9, out3); }
     void fractal_noise_curl(const float *xyz, size_t n, double *out3, const int *offsets9 = nullptr) const { curl_vec3(xyz, n, WN_PERLIN_CURL_FRACTAL, 0, offsets9, out3); }
+
+    // ---- additive: particles moved through that curl field (absent from the reference; include/wnoise_perlin_advect.h,
+    // whose wn_advect `a` is: method, steps, h, gain, drift, traj_every).  kind: WN_PERLIN_CURL_NOISE / _TURB / _FRACTAL, depth
+    // read by TURB only; positions are doubles, TURB and FRACTAL evaluate at the stage point rounded to float.  With
+    // a.traj_every = e >= 1 the positions after steps 0, e, 2e, ... go to traj, a.steps / e + 1 snapshots of n points each
+    // ([snapshot][n][3]).  The scalar member is traced on the host (scalar_eval.h), bit-identical to
+    // wn_perlin_curl_advect_points, which the batched one calls.
+    void advect_curl(const point3 &q, const wn_advect &a, int kind, int depth, const int *offsets9, double p_out[3],
+                     double *traj = nullptr) const
+    {
+        const double xyz[3] = {q.x(), q.y(), q.z()};
+        advect_curl(xyz, a, kind, depth, offsets9, p_out, traj);
+    }
+    void advect_curl(const double xyz[3], const wn_advect &a, int kind, int depth, const int *offsets9, double p_out[3],
+                     double *traj = nullptr) const
+    {
+        if (wnhost_perlin_curl_advect(p.data(), kind, depth, xyz, offsets9 ? offsets9 : default_curl_offsets(), &a, p_out, traj))
+            throw std::runtime_error("advect_curl: a kind or method outside 0..2, a negative depth, steps or traj_every, a "
+                                     "non-finite h, gain or drift, or a trajectory without a buffer");
+    }
+    void advect_curl(const double *xyz, size_t n, const wn_advect &a, int kind, int depth, const int *offsets9, double *xyz_out,
+                     double *traj = nullptr) const
+    {
+        wnhost::perlin_advect_batch(perm_, xyz, n, kind, depth, offsets9 ? offsets9 : default_curl_offsets(), a, xyz_out, traj);
+    }
 
     // ---- additive: octave limiting by a footprint per sample (absent from the reference; include/wnoise_perlin_footprint.h)
     // s = log2 of the sample's footprint in the noise space of q: octave i runs while (s + bias) + i < 0; fade: the finest

@@ -9,6 +9,7 @@
 
 #include "wn_eval.hpp"
 #include "wnoise_advect.h"
+#include "wnoise_perlin_curl.h"
 
 namespace {
 
@@ -212,6 +213,36 @@ void wnhost_perlin_turb_curl(const int *perm, const float q[3], int depth, const
 void wnhost_perlin_fractal_curl(const int *perm, const float q[3], const int offsets9[9], double v[3])
 {
     wn::perlin_fractal_curl(perm, q[0], q[1], q[2], offsets9, v);
+}
+
+int wnhost_perlin_curl_advect(const int *perm, int kind, int depth, const double p_in[3], const int offsets9[9],
+                              const wn_advect *a, double p_out[3], double *traj)
+{
+    if (kind < WN_PERLIN_CURL_NOISE || kind > WN_PERLIN_CURL_FRACTAL || (kind == WN_PERLIN_CURL_TURB && depth < 0)) return 1;
+    if (!a || a->method < WN_ADVECT_EULER || a->method > WN_ADVECT_RK4 || a->steps < 0 || a->traj_every < 0) return 1;
+    if (!std::isfinite(a->h) || !std::isfinite(a->gain) || !std::isfinite(a->drift[0]) || !std::isfinite(a->drift[1]) ||
+        !std::isfinite(a->drift[2]) || (a->traj_every && !traj))
+        return 1;
+    const auto velocity = [&](const double q[3], double v[3]) {
+        if (kind == WN_PERLIN_CURL_NOISE) wn::perlin_curl_exact(perm, q[0], q[1], q[2], offsets9, v);
+        else if (kind == WN_PERLIN_CURL_TURB) wn::perlin_turb_curl(perm, (float)q[0], (float)q[1], (float)q[2], depth, offsets9, v);
+        else wn::perlin_fractal_curl(perm, (float)q[0], (float)q[1], (float)q[2], offsets9, v);
+    };
+    const double h = (double)a->h, h2 = 0.5 * (double)a->h, h6 = (double)a->h / 6.0, gain = (double)a->gain;
+    const double drift[3] = {(double)a->drift[0], (double)a->drift[1], (double)a->drift[2]};
+    double p[3] = {p_in[0], p_in[1], p_in[2]};
+    if (a->traj_every) traj[0] = p[0], traj[1] = p[1], traj[2] = p[2];
+    for (int t = 1; t <= a->steps; ++t) {
+        if (a->method == WN_ADVECT_EULER) wn::advect_step<WN_ADVECT_EULER, double>(p, h, h2, h6, gain, drift, velocity);
+        else if (a->method == WN_ADVECT_MIDPOINT) wn::advect_step<WN_ADVECT_MIDPOINT, double>(p, h, h2, h6, gain, drift, velocity);
+        else wn::advect_step<WN_ADVECT_RK4, double>(p, h, h2, h6, gain, drift, velocity);
+        if (a->traj_every && t % a->traj_every == 0) {
+            double *snap = traj + 3 * (size_t)(t / a->traj_every);
+            snap[0] = p[0], snap[1] = p[1], snap[2] = p[2];
+        }
+    }
+    p_out[0] = p[0], p_out[1] = p[1], p_out[2] = p[2];
+    return 0;
 }
 
 float wnhost_wavelet_texture_value(const float *coef, int n, int use_3d, double scale, int octave, const float xyz[3])

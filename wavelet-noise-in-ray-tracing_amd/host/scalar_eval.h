@@ -117,6 +117,15 @@ WNHOST_API float wnhost_noise_multiband_texture_value(const int *perm, double sc
 WNHOST_API void wnhost_perlin_curl(const int *perm, double x, double y, double z, const int offsets9[9], double v[3]);
 WNHOST_API void wnhost_perlin_turb_curl(const int *perm, const float q[3], int depth, const int offsets9[9], double v[3]);
 WNHOST_API void wnhost_perlin_fractal_curl(const int *perm, const float q[3], const int offsets9[9], double v[3]);
+// One particle traced through one of those curl fields (include/wnoise_perlin_advect.h; `kind`: WN_PERLIN_CURL_NOISE / _TURB /
+// _FRACTAL of include/wnoise_perlin_curl.h, `depth` read by TURB only): p_out receives the position after a->steps steps of
+// wn::advect_step in double, the step the device kernel runs, around wnhost_perlin_curl at the double stage point (NOISE) or
+// wnhost_perlin_turb_curl / _fractal_curl at the stage point rounded to float (TURB, FRACTAL) -- the bits of
+// wn_perlin_curl_advect_points.  traj (read only when a->traj_every >= 1; may then not be NULL): a->steps / a->traj_every + 1
+// packed triples [snapshot][3], the positions after steps 0, e, 2e, ...  p_out may be p_in.  Returns 0, or 1 (WN_ERR_INVALID)
+// and writes nothing when kind, depth or `a` is one that entry point refuses.
+WNHOST_API int wnhost_perlin_curl_advect(const int *perm, int kind, int depth, const double p_in[3], const int offsets9[9],
+                                         const struct wn_advect *a, double p_out[3], double *traj);
 // grey level of texture::value (texture.h); use_3d = 0: the 2-D tile and branch; coef == NULL: the no-tile grey
 WNHOST_API float wnhost_wavelet_texture_value(const float *coef, int n, int use_3d, double scale, int octave,
                                               const float xyz[3]);                    // texture.h:67-107

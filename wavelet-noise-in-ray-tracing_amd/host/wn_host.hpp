@@ -12,6 +12,7 @@
 #include <string>
 
 #include "wnoise.h"
+#include "wnoise_perlin_advect.h"
 
 namespace wnhost {
 
@@ -73,5 +74,23 @@ class DeviceBuffer {
     void *p_ = nullptr;
     size_t bytes_;
 };
+
+// The batched advect_curl members of perlin and PerlinNoise (host pointers): one call of wn_perlin_curl_advect_points, in
+// place on the device; the trajectory buffer exists only when a.traj_every asks for it and traj is given.
+inline void perlin_advect_batch(const wn_perm *perm, const double *xyz, size_t n, int kind, int depth, const int *offsets9,
+                                const wn_advect &a, double *xyz_out, double *traj)
+{
+    static_assert(sizeof(int) == sizeof(int32_t), "offsets are int32");
+    if (!n) return;
+    const bool snaps = a.traj_every >= 1 && a.steps >= 0 && traj;
+    const size_t traj_bytes = snaps ? ((size_t)(a.steps / a.traj_every) + 1) * 3 * n * sizeof(double) : 0;
+    DeviceBuffer pos(3 * n * sizeof(double)), path(traj_bytes ? traj_bytes : sizeof(double));
+    pos.upload(xyz);
+    check(wn_perlin_curl_advect_points(perm, pos.as<double>(), n, kind, depth, reinterpret_cast<const int32_t *>(offsets9), &a,
+                                       pos.as<double>(), snaps ? path.as<double>() : nullptr, nullptr),
+          "wn_perlin_curl_advect_points");
+    if (snaps) check(wn_copy_d2h(traj, path.get(), traj_bytes, nullptr), "wn_copy_d2h");
+    pos.download(xyz_out);
+}
 
 } // namespace wnhost

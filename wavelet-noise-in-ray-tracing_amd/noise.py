@@ -547,6 +547,34 @@ class perlin:
         """noise_curl with fractal_noise potentials (six octaves)."""
         return self._curl(_dev(p, torch.float32).reshape(-1, 3), _capi.WN_PERLIN_CURL_FRACTAL, 0, offsets)
 
+    # -- particles moved through that curl field (include/wnoise_perlin_advect.h; absent from the reference)
+    _CURL_KINDS = {"noise": _capi.WN_PERLIN_CURL_NOISE, "turb": _capi.WN_PERLIN_CURL_TURB,
+                   "fractal": _capi.WN_PERLIN_CURL_FRACTAL}
+
+    def advect_curl(self, pts, h, steps, kind="noise", depth=7, method="rk4", offsets=None, gain=1.0, drift=None,
+                    trajectory_every=0):
+        """An (N, 3) batch of particles moved `steps` time steps of size h (negative: backwards) through the velocity
+        gain * v + drift, all steps inside the kernel (wn_perlin_curl_advect_points).  kind: "noise" (v = noise_curl at the
+        float64 stage point), "turb" (turb_curl with `depth` octaves) or "fractal" (fractal_noise_curl), the last two at the
+        stage point rounded to float32.  method: "euler", "midpoint" or "rk4".  Returns the final (N, 3) float64 positions;
+        with trajectory_every = e >= 1 also the (steps // e + 1, N, 3) positions after steps 0, e, 2e, ...  Float64 with
+        every operation rounded on its own: the bits of stepping with the curl members and separately rounded float64
+        tensor operations."""
+        methods = WaveletNoise._ADVECT_METHODS
+        if method not in methods:
+            raise ValueError(f"method: one of {sorted(methods)}")
+        if kind not in self._CURL_KINDS:
+            raise ValueError(f"kind: one of {sorted(self._CURL_KINDS)}")
+        pts = _dev(pts, torch.float64).reshape(-1, 3)
+        n, steps, every = pts.shape[0], int(steps), int(trajectory_every)
+        a = _capi.wn_advect(methods[method], steps, float(h), float(gain),
+                            (C.c_float * 3)(*([0.0] * 3 if drift is None else [float(x) for x in drift])), every)
+        out = torch.empty((n, 3), dtype=torch.float64, device="cuda")
+        traj = torch.empty((steps // every + 1, n, 3), dtype=torch.float64, device="cuda") if every >= 1 and steps >= 0 else None
+        check(_lib.wn_perlin_curl_advect_points(self._h, _ptr(pts), n, self._CURL_KINDS[kind], int(depth),
+                                                self._curl_offsets(offsets), C.byref(a), _ptr(out), _ptr(traj), _stream()))
+        return out if traj is None else (out, traj)
+
     # -- octave limiting by a footprint per sample (absent from the reference; include/wnoise_perlin_footprint.h)
     def _footprint(self, fn, p, s, octaves, bias, fade, channels):
         pts = _dev(p, torch.float32).reshape(-1, 3)
