@@ -105,12 +105,10 @@ def call_tol(call):
     return 2.0 * tg.call_tol(call)
 
 
-# The gradient test's routes, kernel for kernel (the regime is the same), and: the two brick instantiations its table
-# leaves out, and the LDS edge -- boxes up to 48 KB are launched as they are (mb5: 35 KB), larger ones after the kernel
-# opts in to them (mb5_step_in: 63 KB; lds_66k: eight bands from step .3325, 66 KB); both sides reach the brick kernel.
+# The gradient test's routes, kernel for kernel (the regime is the same), and the LDS edge -- boxes up to 48 KB are launched
+# as they are (mb5: 35 KB), larger ones after the kernel opts in to them (mb5_step_in: 63 KB; lds_66k: eight bands from step
+# .3325, 66 KB); both sides reach the brick kernel.
 ROUTES = [(name, call, kernel.replace("grad3d_", "curl3d_")) for name, call, kernel in tg.ROUTES] + [
-    ("mb6", ("m", "t128", 512, 300, 6, 2, 11, -16.0, -1, 6, W8[:6]), "curl3d_grid_sep_kernel<6>"),
-    ("mb7", ("m", "t128", 1024, 300, 6, 2, 11, -16.0, -1, 7, W8[:7]), "curl3d_grid_sep_kernel<7>"),
     ("lds_66k", ("m", "t128", 385, 256, 5, 0, 9, -16.0, -3, 8, W8), "curl3d_grid_sep_kernel<8>"),
 ]
 SEP, DIRECT_PADDED, DIRECT_LINEAR = "curl3d_grid_sep_kernel<{}>", "curl3d_grid_direct_kernel<true>", "curl3d_grid_direct_kernel<false>"

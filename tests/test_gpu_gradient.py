@@ -173,6 +173,8 @@ ROUTES = [
     ("mb3", ("m", "t128", 512, 300, 6, 2, 11, -16.0, -2, 3, W8[:3]), SEP.format(3)),
     ("mb4", ("m", "t128", 512, 300, 6, 2, 11, -16.0, 0, 4, W8[:4]), SEP.format(4)),
     ("mb5", ("m", "t128", 512, 512, 8, 0, 9, -16.0, 0, 5, W8[:5]), SEP.format(5)),
+    ("mb6", ("m", "t128", 512, 300, 6, 2, 11, -16.0, -1, 6, W8[:6]), SEP.format(6)),
+    ("mb7", ("m", "t128", 1024, 300, 6, 2, 11, -16.0, -1, 7, W8[:7]), SEP.format(7)),
     ("mb8", ("m", "t128", 4096, 300, 6, -4, 5, -16.0, 0, 8, W8), SEP.format(8)),
     ("mb_s_cut", ("m", "t128", 512, 300, 6, 0, 9, -2.5, 0, 5, W8[:5]), SEP.format(3)),   # s stops after 3 bands
     ("mb_none", ("m", "t128", 512, 300, 6, 0, 9, 0.0, 0, 5, W8[:5]), DIRECT_PADDED),    # s: no band runs
@@ -225,7 +227,7 @@ def test_kernel_label_parses_both_name_forms():
 
 
 def test_route_table_covers_every_kernel():
-    want = {SEP.format(nb) for nb in range(1, 9) if nb not in (6, 7)} | {DIRECT_PADDED, DIRECT_LINEAR} | \
+    want = {SEP.format(nb) for nb in range(1, 9)} | {DIRECT_PADDED, DIRECT_LINEAR} | \
            {POINTS.format(p, m) for p in ("true", "false") for m in ("true", "false")}
     assert want <= {k for _, _, k in ROUTES}, want - {k for _, _, k in ROUTES}
     assert len({n for n, _, _ in ROUTES}) == len(ROUTES)

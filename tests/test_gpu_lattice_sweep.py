@@ -1,0 +1,431 @@
+"""Random lattices through every grid planner and its exact twin (the case generators: tests/_sweep.py).
+
+CPU (not marked gpu): what the committed seeds reach -- every kernel label, declining check, step class and shape class at
+least as often as stated below, classified with the restated planners (tests/_far_plan.py, tests/_sweep.py); the constants
+those restatements mirror, read out of csrc/; the brick planner's LDS cap, shown to be a guard no lattice inside two_mids
+can reach.
+
+GPU, every call writing into a guarded Frame (tests/_frame.py: every sample written, no guard touched):
+ * gradient and curl bricks, per (family, seed, part): the default tier within the family's bound of WN_GRID_EXACT on
+   every channel (G of tests/_ref64_grad.py; curl 2 G, as tests/test_gpu_curl.py); the exact tier with the bits of the
+   point entry at the lattice's float32 coordinates on the first, the last and two random planes; those two planes of the
+   default tier within the bound of the float64 reference; and, over the cases the model sends to a brick kernel, a
+   default-versus-exact difference that is not zero (the brick kernels ran: their sums are ordered differently);
+ * Perlin value, gradient and curl grids: the bits of (float)(point entry) * out_scale, run form and generic kernel;
+ * multiband2d grids: the bits of the point entry sent in slices below kPointsLdsMinPoints (the global-gather point
+   kernel, whose bits tests/test_gpu_multiband2d.py holds to the host evaluator), in full up to 300 k samples, else around
+   every trip boundary, at the end and at 8,192 random samples.
+The sweep traces no kernel: its routes come from the CPU model, which tests/test_gpu_gradient.py, test_gpu_curl.py,
+test_gpu_point_dispatch.py and test_gpu_far_lattice.py pin against traced kernels.
+"""
+import collections
+import ctypes as C
+import importlib
+import os
+import re
+import sys
+
+import numpy as np
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+for _p in (ROOT, HERE):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+import _far_plan as fp  # noqa: E402
+import _ref64  # noqa: E402
+import _ref64_curl  # noqa: E402
+import _ref64_grad  # noqa: E402
+import _ref64_multiband2d as M  # noqa: E402
+import _sweep as S  # noqa: E402
+from _frame import Frame  # noqa: E402
+
+VAR = 0.18402
+MI355X_CUS = 256
+FAMILIES = ("grad", "curl")
+CHANNELS = {"grad": 4, "curl": 3}
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+# ---- CPU: what the generators reach --------------------------------------------------------------------------------------
+@pytest.mark.parametrize("family", FAMILIES)
+def test_deriv_sweep_reaches_every_kernel_and_shape_class(family):
+    cases = [c for seed in S.SEEDS for c in S.deriv_cases(family, seed)]
+    assert len(cases) == 60 and len({c.name for c in cases}) == 60
+    labels = collections.Counter(c.label for c in cases)
+    why = collections.Counter(c.why for c in cases)
+    near = collections.Counter(S.near_third(c) for c in cases)
+    for nb in range(1, 9):
+        assert labels[f"{family}3d_grid_sep_kernel<{nb}>"] >= 3, labels
+    assert labels[f"{family}3d_grid_direct_kernel<true>"] >= 3 and labels[f"{family}3d_grid_direct_kernel<false>"] >= 3, labels
+    assert why["static"] >= 3 and why["two_mids"] >= 3 and set(why) == {None, "static", "two_mids"}, why   # no gate, no lds
+    assert near["below"] >= 3 and near["at_above"] >= 3, near
+    # 385 and 384 at a numerator of 128 are among them, on both kinds of call
+    for den128, sep in ((385, True), (384, False)):
+        kinds = {c.bands is None for c in cases if abs(S.top_step(c) * den128 - 128.0) < 1e-9}
+        assert kinds == {True, False}, (den128, kinds)
+        assert all(("_sep_" in c.label) == sep for c in cases if abs(S.top_step(c) * den128 - 128.0) < 1e-9 and c.tile != "empty")
+    brick = [c for c in cases if "_sep_" in c.label]
+    classes = collections.Counter(k for c in brick for k in S.deriv_classes(c))
+    want = ["nx%4", "ragged_x", "ragged_y", "ragged_z", "ragged_xyz", "z0<0", "z_const", "den_np2", "neg_out", "lead0", "lead1",
+            "lead2", "lead3", "tile_t128", "tile_t32", "tile_t8", "tile_t6", "s_cut", "first_neg", "first_pos", "zero_w"]
+    if family == "curl":
+        want += ["off_neg", "off_ge_n"]
+        assert classes["off_default"] >= 1
+    short = {k: classes[k] for k in want if classes[k] < 3}
+    assert not short, short
+    assert sum(c.tile == "empty" for c in cases) >= 3
+    for c in cases:
+        assert 0 < c.nx * c.ny * c.nz <= S.CAP
+        g = S.deriv_grid(c)
+        assert S.top_step(c) * max(c.nx, c.ny, abs(c.z0) + c.nz) + abs(g.z_const) < 1e4   # nowhere near the 1e6 gate
+        # the exact tier's route: the direct kernel
+        assert fp.deriv_route(g, S.TILE_N[c.tile], True, family, None if c.bands is None else c.bands[:3])[0] == \
+            f"{family}3d_grid_direct_kernel<{'true' if S.TILE_N[c.tile] else 'false'}>"
+    # every part of a seed holds brick cases (each part asserts a non-zero default-versus-exact difference of its own)
+    for seed in S.SEEDS:
+        for part in range(S.PARTS):
+            assert sum("_sep_" in c.label for c in S.deriv_cases(family, seed)[part::S.PARTS]) >= 5
+
+
+def test_deriv_sweep_is_deterministic():
+    a, b = S.deriv_cases("curl", S.SEEDS[0]), S.deriv_cases("curl", S.SEEDS[0])
+    assert [S.describe(x) for x in a] == [S.describe(x) for x in b]
+    assert [S.describe(x) for x in a] != [S.describe(x) for x in S.deriv_cases("curl", S.SEEDS[1])]
+
+
+@pytest.mark.parametrize("variant", list(S.PERLIN_CHANNELS))
+def test_perlin_sweep_reaches_both_forms_and_every_step_class(variant):
+    cases = S.perlin_cases(variant)
+    forms = collections.Counter(c.form for c in cases)
+    assert forms["run"] >= 5 and forms["generic"] >= 5, forms
+    assert {127, 128, 129} <= {c.nx for c in cases}
+    assert {c.form for c in cases if c.nx == 127} == {"generic"} and "run" in {c.form for c in cases if c.nx == 128}
+    steps = collections.Counter(S.perlin_step_class(c) for c in cases if c.form == "run")
+    assert steps["small"] >= 3 and steps["mid"] >= 3 and steps["big"] >= 3, steps
+    assert any(c.base_range < 0 for c in cases) and any(c.z_const is not None for c in cases)
+    assert any(np.log2(c.octave_scale) % 1 for c in cases)
+    assert {c.depth for c in cases if c.kind == "turb"} >= {0, 1, 8, 9, 12}
+    assert {c.kind for c in cases} == {"noise", "turb", "fractal"}
+    assert {c.form for c in cases if c.kind == "turb" and c.depth in (0, 9, 12)} == {"generic"}
+    assert {c.form for c in cases if c.kind == "turb" and c.depth in (1, 8) and c.nx >= 128} == {"run"}
+    assert {c.lead for c in cases} == {0, 1, 2, 3}
+    assert all(0 < c.nx * c.ny * c.nz <= S.CAP for c in cases)
+    if variant == "curl":
+        assert any(c.offsets is None for c in cases) and any(c.offsets is not None and min(min(o) for o in c.offsets) < 0 for c in cases)
+
+
+@pytest.mark.parametrize("cus", [MI355X_CUS, 304, 64])
+def test_multiband2d_sweep_reaches_every_row_length_and_trip_class(cus):
+    cases = S.mb2d_cases(cus)
+    trip = S.mb2d_trip(cus)
+    assert {c.nx for c in cases} == {1, 3, 67, 1023, 1024, 1025, 1500, 4099}
+    for nx in (1, 3, 67, 1023, 1024, 1025, 1500, 4099):
+        assert {c.cls for c in cases if c.nx == nx} >= {"one", "multi"}
+    assert sum(c.cls == "boundary" for c in cases) >= 2
+    for c in cases:
+        total = c.nx * c.ny
+        assert 0 < total <= S.CAP
+        assert (c.cls == "one" and total < trip) or (c.cls == "boundary" and total == trip) or \
+            (c.cls == "multi" and 2 * trip < total <= 3 * trip)
+        idx = S.mb2d_check_indices(c, cus)
+        assert idx.size == total if total <= S.MB2D_FULL else (idx.size <= S.MB2D_LDS_MIN_POINTS // 2 and idx[-1] == total - 1)
+        if c.cls == "multi":     # both sides of both trip boundaries
+            assert {trip - 1, trip, 2 * trip - 1, 2 * trip} <= set(idx.tolist()) or total <= S.MB2D_FULL
+    assert {c.form for c in cases if c.tile in ("t128", "t6", "t16")} == {"lds"}
+    assert {c.form for c in cases if c.tile == "t256"} == {"gather"}
+    assert {c.nbands for c in cases} == set(range(1, 9)) and {c.grad for c in cases} == {False, True}
+    for tile in S.MB2D_TILES:
+        assert {c.grad for c in cases if c.tile == tile} == {False, True}, tile
+        assert {c.cls for c in cases if c.tile == tile} >= {"one", "multi"}, tile
+
+
+def test_the_mirrored_constants_are_those_of_the_sources():
+    frame = S.csrc("wn_perlin_frame.hpp")
+    assert S.constexpr_int("kRunMaxDepth", frame) == S.RUN_MAX_DEPTH
+    assert S.constexpr_int("kFractalOctaves", frame) == S.FRACTAL_OCTAVES
+    assert S.constexpr_int("kRunTY", frame) == 8 and S.constexpr_int("kRunTZ", frame) == 8
+    found = re.findall(r"return g\.nx >= (\d+) && octaves >= 1 && octaves <= kRunMaxDepth && rgrid->y <= 65535u && "
+                       r"rgrid->z <= 65535u;", frame)
+    assert found == [str(S.RUN_MIN_NX)], found
+    brick = S.csrc("wn_brick.hpp")
+    got = re.findall(r"constexpr int kGX = (\d+), kGY = (\d+), kGZ = (\d+);", brick)
+    assert got == [tuple(str(v) for v in S.BRICK)], got
+    mb = S.csrc("wn_wavelet_multiband2d.hip")
+    for name, want in (("WN_MB2D_WORKGROUP", S.MB2D_WORKGROUP), ("WN_MB2D_LDS_TILE_MAX_BYTES", S.MB2D_LDS_TILE_MAX_BYTES),
+                       ("WN_MB2D_POINTS_LDS_MIN_POINTS", S.MB2D_LDS_MIN_POINTS)):
+        found = re.findall(r"^#define\s+" + name + r"\s+(.+)$", mb, re.M)
+        assert len(found) == 1 and S.int_product(found[0]) == want, (name, found)
+    assert S.constexpr_int("kWorkgroupsPerCu", mb) == S.MB2D_WORKGROUPS_PER_CU
+
+
+def test_the_brick_planners_lds_cap_cannot_decline_inside_two_mids():
+    """brick_plan's `box_total > max_floats` is a guard, not a route: _sweep.brick_box_bound derives 6,843 floats for the
+    gradient's one box per band and 20,529 for the curl's three, from extent(256) + 1 <= 90 and extent(8) <= 6 at
+    3 step + slack <= 1 with bands halving below, against caps of 12,288 and 36,864."""
+    grad_cap = S.constexpr_int("kGMaxBoxFloats", S.csrc("wn_wavelet_grad.hip"))
+    curl_cap = S.constexpr_int("kCMaxBoxFloats", S.csrc("wn_wavelet_curl.hip"))
+    assert (grad_cap, curl_cap) == (12 * 1024, 36 * 1024)
+    assert S.brick_box_bound(1) == 6843 and S.brick_box_bound(3) == 20529
+    assert S.brick_box_bound(1) < grad_cap and S.brick_box_bound(3) < curl_cap
+    # the premises, on a scan of steps up to the edge and of slacks up to the gate's
+    for pmax in (1.0, 300.0, 1.0e4, 1.0e6):
+        slack = pmax * fp.SLACK_PER_CELL
+        for step in np.concatenate([np.linspace(0.0, (1.0 - slack) / 3.0, 4001), [(1.0 - slack) / 3.0]]):
+            ls = fp.LatticeStep(float(step), pmax, slack)
+            assert ls.two_mids() and ls.extent(256) + 1 <= 90 and ls.extent(8) <= 6, (pmax, step)
+            for k in range(1, fp.MAX_BANDS):
+                lk = fp.LatticeStep(float(step) / 2 ** k, pmax, slack)
+                assert lk.extent(256) + 1 <= int(np.floor(85.0 / 2 ** k + 1.0)) + 5
+                assert lk.extent(8) <= int(np.floor(7.0 / (3.0 * 2 ** k) + 1.0)) + 4
+    # the largest lattice of the route tables: eight bands from a step just under 1/3 (test_gpu_curl's lds_66k)
+    g = fp.Grid(385, 256, 5, 0, 9)
+    q = [2.0 * 2.0 ** (-3 + b) for b in range(8)]
+    assert fp.brick_plan(g, 128, q, 1, grad_cap) is None and fp.brick_plan(g, 128, q, 3, curl_cap) is None
+    assert (S.brick_box_floats(g, q, 1), S.brick_box_floats(g, q, 3)) == (5483, 16449)
+    assert S.brick_box_floats(g, q, 1) <= S.brick_box_bound(1) and S.brick_box_floats(g, q, 3) <= S.brick_box_bound(3)
+    # and no case of the sweep is declined by it
+    for family, boxes in (("grad", 1), ("curl", 3)):
+        for seed in S.SEEDS:
+            for c in S.deriv_cases(family, seed):
+                if c.why is None:
+                    nb = S.deriv_active(c)
+                    qm = [1.0] if c.bands is None else [2.0 * 2.0 ** (c.bands[1] + b) for b in range(nb)]
+                    assert S.brick_box_floats(S.deriv_grid(c), qm, boxes) <= S.brick_box_bound(boxes)
+
+
+# ---- GPU -------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def wn():
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need a GPU (the product has no CPU path)"
+    return importlib.import_module("wavelet-noise-in-ray-tracing_amd")
+
+
+@pytest.fixture(scope="module")
+def nm(wn):
+    return importlib.import_module("wavelet-noise-in-ray-tracing_amd.noise")
+
+
+@pytest.fixture(scope="module")
+def tiles(wn):
+    """test_gpu_gradient.load_tiles' tiles and the 32^3 tile of test_gpu_point_dispatch.py (seed 4242)."""
+    import test_gpu_gradient as tg
+    import test_gpu_point_dispatch as tp
+    objs, coefs = tg.load_tiles(wn)
+    t32 = wn.WaveletNoise(32, tp.SEED32)
+    t32.generateNoiseTile3D()
+    objs["t32"], coefs["t32"] = t32, t32.getNoiseCoefficients()
+    assert set(objs) == set(S.TILE_N)
+    return objs, coefs
+
+
+def _np(t):
+    return t.detach().cpu().numpy()
+
+
+def _cuda(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def grid_spec(nm, c, exact=False):
+    return nm.GridSpec(c.den, c.nx, c.ny, c.z0, c.z0 + c.nz, base_range=c.base_range, octave_scale=c.octave_scale,
+                       post_scale=c.post_scale, z_mode=nm.WN_Z_LATTICE if c.z_const is None else nm.WN_Z_CONST,
+                       z_const=0.0 if c.z_const is None else c.z_const, out_scale=c.out_scale,
+                       flags=nm.WN_GRID_EXACT if exact else nm.WN_GRID_DEFAULT)
+
+
+def lattice_axes(c):
+    """float32 coordinates (px, py, pz) in the order lattice_coord forms them."""
+    px, py = (_ref64.lattice_coords(np.arange(k), c.den, c.base_range, c.octave_scale, c.post_scale) for k in (c.nx, c.ny))
+    if c.z_const is not None:
+        return px, py, np.float32([c.z_const])
+    return px, py, _ref64.lattice_coords(np.arange(c.z0, c.z0 + c.nz), c.den, c.base_range, c.octave_scale, c.post_scale)
+
+
+def plane_points(px, py, pz):
+    pts = np.stack(np.broadcast_arrays(px[None, None, :], py[None, :, None], pz[:, None, None]), -1).reshape(-1, 3)
+    return np.ascontiguousarray(pts, np.float32)
+
+
+# ---- gradient and curl -------------------------------------------------------------------------------------------------------
+def run_deriv(nm, objs, c, exact):
+    """One tier of a case inside a Frame: [channels, nz, ny, nx] after the frame check."""
+    lib, st = nm._lib, nm._stream()
+    ch = CHANNELS[c.family]
+    tile = objs[c.tile]
+    gc = grid_spec(nm, c, exact).c()
+    out = Frame(ch * c.nz * c.ny * c.nx, c.lead)
+    h = tile._handle(3)
+    off = tile._curl_offsets(c.offsets) if c.family == "curl" else None
+    if c.bands is None:
+        rc = lib.wn_eval3d_grad_grid(h, C.byref(gc), out.ptr, st) if off is None else \
+            lib.wn_eval3d_curl_grid(h, C.byref(gc), off, out.ptr, st)
+    else:
+        s, first, nb, w = c.bands
+        wa = (C.c_float * nb)(*w)
+        rc = lib.wn_multiband3d_grad_grid(h, C.byref(gc), float(s), first, nb, wa, VAR, out.ptr, st) if off is None else \
+            lib.wn_multiband3d_curl_grid(h, C.byref(gc), off, float(s), first, nb, wa, VAR, out.ptr, st)
+    assert rc == 0, (c.name, lib.wn_last_error())
+    got = out.result(what=f"{c.name} {'exact' if exact else 'default'} tier ({c.label})")
+    return got.reshape(ch, c.nz, c.ny, c.nx)
+
+
+def deriv_points(objs, c, pts):
+    """The point entry of the case's family at pts, times out_scale in float32: (N, channels)."""
+    tile, td = objs[c.tile], _cuda(pts)
+    if c.family == "grad":
+        rec = tile.evaluate3DGradient(td) if c.bands is None else tile.WMultibandNoiseGradient(td, *c.bands)
+    else:
+        rec = tile.evaluate3DCurl(td, c.offsets) if c.bands is None else tile.WMultibandNoiseCurl(td, *c.bands, offsets=c.offsets)
+    return _np(rec) * np.float32(c.out_scale)
+
+
+def deriv_ref64(coefs, c, px, py, pz):
+    """The float64 reference on planes pz: [channels, len(pz), ny, nx]."""
+    coef = coefs[c.tile]
+    scale = float(np.float32(c.out_scale))
+    if coef.size == 0:
+        return np.zeros((CHANNELS[c.family], pz.size, py.size, px.size))
+    if c.family == "grad":
+        if c.bands is None:
+            return _ref64_grad.evaluate_lattice_grad(coef, px, py, pz) * scale
+        return _ref64_grad.multiband_lattice_grad(coef, px, py, pz, *c.bands, VAR) * scale
+    off = _ref64_curl.default_offsets(S.TILE_N[c.tile]) if c.offsets is None else c.offsets
+    if c.bands is None:
+        return _ref64_curl.evaluate_lattice_curl(coef, px, py, pz, off) * scale
+    return _ref64_curl.multiband_lattice_curl(coef, px, py, pz, off, *c.bands, VAR) * scale
+
+
+def deriv_tolerance(c):
+    """G (curl: 2 G) at the case's out_scale and bands."""
+    mod = _ref64_grad if c.family == "grad" else _ref64_curl
+    return mod.tolerance(c.out_scale, None if c.bands is None else c.bands + (VAR,))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("part", range(S.PARTS))
+@pytest.mark.parametrize("seed", S.SEEDS)
+@pytest.mark.parametrize("family", FAMILIES)
+def test_gradient_and_curl_sweep(wn, nm, tiles, family, seed, part):
+    objs, coefs = tiles
+    cases = S.deriv_cases(family, seed)[part::S.PARTS]
+    ch = CHANNELS[family]
+    worst_brick = 0.0
+    for c in cases:
+        rng = np.random.default_rng([seed, int(c.name[-2:])])
+        tol = deriv_tolerance(c)
+        fast, exact = run_deriv(nm, objs, c, False), run_deriv(nm, objs, c, True)                 # (a)
+        e_fe = np.abs(fast.astype(np.float64) - exact.astype(np.float64)).reshape(ch, -1).max(1)
+        drawn = sorted({int(z) for z in rng.integers(0, c.nz, 2)})
+        planes = sorted({0, c.nz - 1, *drawn})
+        px, py, pz = lattice_axes(c)
+        ref = deriv_ref64(coefs, c, px, py, pz[drawn])
+        e_fr = np.abs(fast[:, drawn].astype(np.float64) - ref).reshape(ch, -1).max(1)
+        print(f"sweep {c.name} {c.label} why={c.why} tile={c.tile} {c.nx}x{c.ny}x{c.nz} den={c.den} bands={c.bands and c.bands[:3]} "
+              f"|default-exact| {e_fe.max():.3e} |default-ref64| {e_fr.max():.3e} bound {tol:.3e}")
+        assert (e_fe <= tol).all(), (S.describe(c), e_fe.tolist(), tol)                            # (b)
+        pk = deriv_points(objs, c, plane_points(px, py, pz[planes]))                                # (c)
+        same = bits(exact[:, planes].reshape(ch, -1).T) == bits(pk)
+        assert same.all(), (S.describe(c), int((~same).sum()), np.argwhere(~same)[:5].tolist())
+        assert (e_fr <= tol).all(), (S.describe(c), e_fr.tolist(), tol)                            # (d)
+        if c.tile == "empty":
+            assert (fast == 0.0).all() and (exact == 0.0).all()
+        if "_sep_" in c.label:
+            worst_brick = max(worst_brick, float(e_fe.max()))
+    assert worst_brick > 0.0                                                                      # (e)
+
+
+# ---- Perlin --------------------------------------------------------------------------------------------------------------------
+PERLIN_KINDS = {"noise": 0, "turb": 1, "fractal": 2}
+
+
+def run_perlin(nm, p, c):
+    lib, st = nm._lib, nm._stream()
+    ch = S.PERLIN_CHANNELS[c.variant]
+    gc = grid_spec(nm, c).c()
+    out = Frame(ch * c.nz * c.ny * c.nx, c.lead)
+    if c.variant == "curl":
+        rc = lib.wn_perlin_curl_grid(p._h, C.byref(gc), PERLIN_KINDS[c.kind], c.depth, p._curl_offsets(c.offsets), out.ptr, st)
+    else:
+        mid = "" if c.variant == "value" else "grad_"
+        if c.kind == "noise":
+            rc = getattr(lib, f"wn_perlin_{mid}grid")(p._h, C.byref(gc), out.ptr, st)
+        elif c.kind == "turb":
+            rc = getattr(lib, f"wn_perlin_turb_{mid}grid")(p._h, C.byref(gc), c.depth, out.ptr, st)
+        else:
+            rc = getattr(lib, f"wn_perlin_fractal_{mid}grid")(p._h, C.byref(gc), out.ptr, st)
+    assert rc == 0, (c.name, lib.wn_last_error())
+    return out.result(what=f"{c.name} ({c.form})").reshape(ch, -1)
+
+
+def perlin_points(p, c, pts):
+    """The float64 records of the point entry: (N, channels)."""
+    td = _cuda(pts)
+    if c.variant == "value":
+        rec = p.noise(td) if c.kind == "noise" else (p.turb(td, c.depth) if c.kind == "turb" else p.fractal_noise(td))
+        return rec.reshape(-1, 1)
+    if c.variant == "grad":
+        return p.noise_gradient(td) if c.kind == "noise" else (p.turb_gradient(td, c.depth) if c.kind == "turb" else
+                                                                p.fractal_noise_gradient(td))
+    return p.noise_curl(td, c.offsets) if c.kind == "noise" else (p.turb_curl(td, c.depth, c.offsets) if c.kind == "turb" else
+                                                                  p.fractal_noise_curl(td, c.offsets))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("variant", list(S.PERLIN_CHANNELS))
+def test_perlin_sweep(wn, nm, variant):
+    """The grid has the bits of (float)(point entry) * out_scale, as test_grid_has_the_point_kernels_bits forms it."""
+    import torch
+    p = wn.perlin(12345)
+    forms = collections.Counter()
+    for c in S.perlin_cases(variant):
+        got = run_perlin(nm, p, c)
+        rec = perlin_points(p, c, plane_points(*lattice_axes(c)))
+        pk = _np(rec.to(torch.float32)) * np.float32(c.out_scale)
+        same = bits(got.T) == bits(pk)
+        assert same.all(), (S.describe(c), int((~same).sum()), np.argwhere(~same)[:5].tolist())
+        if c.kind == "turb" and c.depth == 0:
+            assert (got == 0.0).all()
+        forms[c.form] += 1
+    print(f"sweep perlin {variant}: {dict(forms)}")
+
+
+# ---- multiband2d -----------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def mb2d(wn):
+    import torch
+    import test_gpu_multiband2d as t2
+    coefs = {t: M.tile2d(int(t[1:])) for t in S.MB2D_TILES}
+    objs = {k: wn.WaveletNoise.from_coefficients(v, 2) for k, v in coefs.items()}
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    return t2, objs, cus
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("part", range(S.PARTS))
+def test_multiband2d_sweep(nm, mb2d, part):
+    t2, objs, cus = mb2d
+    step = S.MB2D_LDS_MIN_POINTS // 2 + 5                     # slices below kPointsLdsMinPoints: the global-gather point kernel
+    for c in S.mb2d_cases(cus)[part::S.PARTS]:
+        total, ch = c.nx * c.ny, 3 if c.grad else 1
+        g = nm.GridSpec(c.den, c.nx, c.ny, out_scale=c.out_scale)
+        out = Frame(ch * total, c.lead)
+        rc = t2.grid_abi(nm, c.grad, objs[c.tile]._handle(2), g, c.s, c.first, c.nbands, c.w, out.ptr)
+        assert rc == 0, (c.name, nm._lib.wn_last_error())
+        got = out.result(what=c.name).reshape(ch, total)
+        idx = S.mb2d_check_indices(c, cus)
+        px, py = (_ref64.lattice_coords(np.arange(k), c.den) for k in (c.nx, c.ny))
+        pts = np.stack([px[idx % c.nx], py[idx // c.nx]], axis=1).astype(np.float32)
+        pk = np.concatenate([t2.run_points(nm, c.grad, objs[c.tile], pts[a:a + step], np.float32(c.s), c.first, c.nbands, c.w, 0)
+                             for a in range(0, idx.size, step)])
+        same = bits(got[:, idx].T) == bits(pk * np.float32(c.out_scale))
+        assert same.all(), (S.describe(c), cus, int((~same).sum()), idx[np.argwhere(~same)[:5, 0]].tolist())
+        assert np.ptp(got[0]) > 0.0
+        print(f"sweep {c.name} {c.nx}x{c.ny} trips {S.mb2d_trips(c, cus)} bands {c.nbands} compared {idx.size}")
