@@ -21,7 +21,8 @@ _capi.load()  # fail loudly when the HIP library is missing
 from .noise import (  # noqa: E402
     WaveletNoise, perlin, PerlinNoise, noise_texture, wavelet_texture, wavelet_multiband_texture,
     noise_multiband_texture, GridSpec,
-    generate2DOctaveBandNoise, generate2DMultibandNoise, generate2DMultibandNoiseGradient, generate3DSlicedOctaveBandNoise,
+    generate2DOctaveBandNoise, generate2DMultibandNoise, generate2DMultibandNoiseGradient, generate2DMultibandNoiseCurl,
+    generate3DSlicedOctaveBandNoise,
     generate3DProjectedOctaveBandNoise, generatePerlinNoise2D, generatePerlinNoise3DSliced,
     wavelet_volume, wavelet_volume_launcher, multiband_volume, perlin_volume, turb_volume, device_info, HipTimer,
     wavelet_gradient_volume, multiband_gradient_volume, wavelet2d_gradient_image, projected_gradient_volume,
@@ -36,6 +37,7 @@ __all__ = [
     "WaveletNoise", "perlin", "PerlinNoise", "noise_texture", "wavelet_texture", "wavelet_multiband_texture",
     "noise_multiband_texture", "GridSpec",
     "generate2DOctaveBandNoise", "generate2DMultibandNoise", "generate2DMultibandNoiseGradient",
+    "generate2DMultibandNoiseCurl",
     "generate3DSlicedOctaveBandNoise",
     "generate3DProjectedOctaveBandNoise", "generatePerlinNoise2D", "generatePerlinNoise3DSliced",
     "wavelet_volume", "wavelet_volume_launcher", "multiband_volume", "perlin_volume", "turb_volume", "device_info",

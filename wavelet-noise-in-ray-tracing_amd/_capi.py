@@ -1,6 +1,6 @@
 """ctypes binding of libwnoise_hip.so (include/wnoise.h, include/wnoise_perlin_curl.h, include/wnoise_footprint.h,
 include/wnoise_perlin_footprint.h, include/wnoise_multiband2d.h, include/wnoise_advect.h,
-include/wnoise_perlin_advect.h).
+include/wnoise_perlin_advect.h, include/wnoise_curl2d.h).
 
 The library is the product: if it is missing or fails to load this module raises, it never
 substitutes a CPU implementation.
@@ -181,6 +181,21 @@ PERLIN_ADVECT_SIGNATURES = {
     "wn_perlin_advect_launch_steps": (_i, [_i, _i, _i]),
 }
 
+# name -> (restype, argtypes); every symbol include/wnoise_curl2d.h declares, and its wn_advect2d.
+class wn_advect2d(C.Structure):
+    _fields_ = [("method", C.c_int32), ("steps", C.c_int32), ("h", C.c_float), ("gain", C.c_float),
+                ("drift", C.c_float * 2), ("traj_every", C.c_int32)]
+
+
+_a2p = C.POINTER(wn_advect2d)
+CURL2D_SIGNATURES = {
+    "wn_multiband2d_curl_points": _points_mb2d,
+    "wn_multiband2d_curl_grid": _grid_mb2d,
+    # tile, xy_in, n, s, first_band, nbands, w, var, a, xy_out, traj, stream
+    "wn_multiband2d_curl_advect_points": (_i, [_vp, _vp, _sz, _f, _i, _i, _fp, _f, _a2p, _vp, _vp, _vp]),
+    "wn_advect2d_launch_steps": (_i, [_i, _i]),
+}
+
 _lib = None
 
 
@@ -196,7 +211,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (*SIGNATURES.items(), *PERLIN_CURL_SIGNATURES.items(), *FOOTPRINT_SIGNATURES.items(),
                               *PERLIN_FOOTPRINT_SIGNATURES.items(), *MULTIBAND2D_SIGNATURES.items(),
-                              *ADVECT_SIGNATURES.items(), *PERLIN_ADVECT_SIGNATURES.items()):
+                              *ADVECT_SIGNATURES.items(), *PERLIN_ADVECT_SIGNATURES.items(), *CURL2D_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

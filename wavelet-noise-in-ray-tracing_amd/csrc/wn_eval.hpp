@@ -467,6 +467,34 @@ WN_EVAL_FN float multiband2d_footprint_exact(const A &a, const float *coef, cons
     return v;
 }
 
+// The curl of the stream function psi = multiband2d_footprint_exact<GRAD = true> at the call-wide footprint s with fade 0
+// (include/wnoise_curl2d.h): v = (d psi/dy, -d psi/dx).  The band loop, the chain-rule factor and the division are that
+// function's (fade 0: wb = w[b] * 1.0f = w[b] exactly; a.fade is not read); the value sum is not formed.  v[0] has the bits of
+// its d/dy channel, v[1] those of its d/dx channel with the sign flipped.  No active band, or an empty tile: v = 0.
+// first_band = -1, nbands = 1, w = {1}, var_per_band = 1: q = 2 * p * 2^-1 = p exactly and out_div = 1, the curl of plain
+// evaluate2D(p).
+template <bool PADDED = false, typename A>
+WN_EVAL_FN void multiband2d_curl_exact(const A &a, const float *coef, const float p[2], float s, float v[2])
+{
+    float gx = 0.0f, gy = 0.0f;
+    for (int b = 0; b < a.nbands; ++b) {
+        const float t = footprint_t(a, s, b);
+        if (!(t < 0.0f)) break;
+        const float bs = a.band_scale[b];
+        float gb[2];
+        eval2d_exact<true, PADDED>(coef, a.n, a.nmask, 2.0f * p[0] * bs, 2.0f * p[1] * bs, gb);
+        const float f = a.band_w[b] * (2.0f * bs);
+        gx += f * gb[0];
+        gy += f * gb[1];
+    }
+    if (a.apply_div) {
+        gx /= a.out_div;
+        gy /= a.out_div;
+    }
+    v[0] = gy;
+    v[1] = -gx;
+}
+
 // ---- curl of a vector potential of three whole-cell shifts of one tile (absent from the reference) ---------------------
 // Psi = (psi0, psi1, psi2), psi_k = evaluate3D of the tile T_k[z][y][x] = C[Mod(z+oz_k)][Mod(y+oy_k)][Mod(x+ox_k)];
 // v = curl Psi = (d psi2/dy - d psi1/dz, d psi0/dz - d psi2/dx, d psi1/dx - d psi0/dy).  The shifts are whole cells, so the
@@ -586,8 +614,9 @@ WN_EVAL_FN void multiband_curl_exact(const A &a, const float p[3], float v[3])
 }
 
 // ---- one explicit time step of a particle through a velocity field (include/wnoise_advect.h; absent from the reference) --
-// METHOD: WN_ADVECT_EULER / _MIDPOINT / _RK4 (0, 1, 2).  T: float (the wavelet potentials, include/wnoise_advect.h) or double
-// (the Perlin potentials, include/wnoise_perlin_advect.h).  velocity(q, v) writes the field's v(q); the stage velocity is
+// METHOD: WN_ADVECT_EULER / _MIDPOINT / _RK4 (0, 1, 2).  D: the dimension, 3 (include/wnoise_advect.h,
+// include/wnoise_perlin_advect.h) or 2 (include/wnoise_curl2d.h).  T: float (the wavelet potentials) or double (the Perlin
+// potentials).  velocity(q, v) writes the field's v(q); the stage velocity is
 // k(q) = gain * v(q) + drift, one multiply, then one add per component.  h2 = T(0.5) * h and h6 = h / T(6) come from the
 // caller, formed once.  Every product and every sum below rounds on its own (in T, unfused), so p' has the bits of the same
 // operations written out with separately rounded arithmetic of that type around the field's own entry point:
@@ -596,39 +625,42 @@ WN_EVAL_FN void multiband_curl_exact(const A &a, const float p[3], float v[3])
 //     RK4       p' = p + h6 * (((k1 + 2 * k2) + 2 * k3) + k4),                k2 = k(p + h2 * k1), k3 = k(p + h2 * k2),
 //                                                                              k4 = k(p + h * k3)
 // RK4 keeps one running sum of the stage velocities beside p and the stage point.
-template <int METHOD, typename T, typename V>
-WN_EVAL_FN void advect_step(T p[3], T h, T h2, T h6, T gain, const T drift[3], const V &velocity)
+template <int METHOD, int D = 3, typename T, typename V>
+WN_EVAL_FN void advect_step(T p[D], T h, T h2, T h6, T gain, const T drift[D], const V &velocity)
 {
     static_assert(METHOD >= 0 && METHOD <= 2, "Euler, midpoint or RK4");
-    auto stage = [&](const T q[3], T k[3]) {
-        T v[3];
+    static_assert(D == 2 || D == 3, "a plane or a volume");
+    auto stage = [&](const T q[D], T k[D]) {
+        T v[D];
         velocity(q, v);
         WN_UNROLL
-        for (int c = 0; c < 3; ++c) k[c] = gain * v[c] + drift[c];
+        for (int c = 0; c < D; ++c) k[c] = gain * v[c] + drift[c];
     };
-    auto from_p = [&](T f, const T k[3], T q[3]) {
+    auto from_p = [&](T f, const T k[D], T q[D]) {
         WN_UNROLL
-        for (int c = 0; c < 3; ++c) q[c] = p[c] + f * k[c];
+        for (int c = 0; c < D; ++c) q[c] = p[c] + f * k[c];
     };
-    T k[3], q[3];
+    T k[D], q[D];
     stage(p, k);
     if constexpr (METHOD == 1) {
         from_p(h2, k, q);
         stage(q, k);
     } else if constexpr (METHOD == 2) {
-        T sum[3] = {k[0], k[1], k[2]};
+        T sum[D];
+        WN_UNROLL
+        for (int c = 0; c < D; ++c) sum[c] = k[c];
         from_p(h2, k, q);
         stage(q, k);
         WN_UNROLL
-        for (int c = 0; c < 3; ++c) sum[c] = sum[c] + T(2) * k[c];
+        for (int c = 0; c < D; ++c) sum[c] = sum[c] + T(2) * k[c];
         from_p(h2, k, q);
         stage(q, k);
         WN_UNROLL
-        for (int c = 0; c < 3; ++c) sum[c] = sum[c] + T(2) * k[c];
+        for (int c = 0; c < D; ++c) sum[c] = sum[c] + T(2) * k[c];
         from_p(h, k, q);
         stage(q, k);
         WN_UNROLL
-        for (int c = 0; c < 3; ++c) k[c] = sum[c] + k[c];
+        for (int c = 0; c < D; ++c) k[c] = sum[c] + k[c];
     }
     from_p(METHOD == 2 ? h6 : h, k, p);
 }

@@ -196,17 +196,19 @@ inline int curl_eval_args(const wn_tile *tile, const int32_t *offsets9_host, con
     return WN_OK;
 }
 
-// The checks of an advection call's wn_advect (wn_wavelet_advect.hip, wn_perlin_advect.hip).
-inline int check_advect(const wn_advect *a)
+// The checks of an advection call's wn_advect (wn_wavelet_advect.hip, wn_perlin_advect.hip) or wn_advect2d
+// (wn_wavelet_curl2d.hip): the same fields, a drift of three or two components.
+template <typename A>
+inline int check_advect(const A *a)
 {
     if (!a) return fail(WN_ERR_INVALID, "wn_advect is NULL");
     if (a->method < WN_ADVECT_EULER || a->method > WN_ADVECT_RK4)
         return fail(WN_ERR_INVALID, "wn_advect.method must be 0 (Euler), 1 (midpoint) or 2 (RK4) (got %d)", a->method);
     if (a->steps < 0) return fail(WN_ERR_INVALID, "wn_advect.steps must be >= 0 (got %d)", a->steps);
     if (a->traj_every < 0) return fail(WN_ERR_INVALID, "wn_advect.traj_every must be >= 0 (got %d)", a->traj_every);
-    if (!std::isfinite(a->h) || !std::isfinite(a->gain) || !std::isfinite(a->drift[0]) || !std::isfinite(a->drift[1]) ||
-        !std::isfinite(a->drift[2]))
-        return fail(WN_ERR_INVALID, "wn_advect.h, gain and drift must be finite");
+    bool finite = std::isfinite(a->h) && std::isfinite(a->gain);
+    for (const float d : a->drift) finite = finite && std::isfinite(d);
+    if (!finite) return fail(WN_ERR_INVALID, "wn_advect.h, gain and drift must be finite");
     return WN_OK;
 }
 

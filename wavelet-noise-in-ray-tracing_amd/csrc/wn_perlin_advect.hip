@@ -1,7 +1,7 @@
 // wn_perlin_advect.hip -- particles moved through the curl noise of Perlin noise potentials (include/wnoise_perlin_advect.h).
 //
 // The velocity is wn_perlin_curl.hip's point evaluator, wn::perlin_curl_exact / perlin_turb_curl / perlin_fractal_curl; the
-// time step is wn::advect_step<METHOD, double> (wn_eval.hpp), stated once for this kernel, for the wavelet kernel
+// time step is wn::advect_step<METHOD, 3, double> (wn_eval.hpp), stated once for this kernel, for the wavelet kernel
 // (wn_wavelet_advect.hip, in float) and for the host's wnhost_perlin_curl_advect.
 //
 //   perlin_curl_advect_kernel<KIND, METHOD>   one particle per lane in a grid-stride loop: the permutation table is staged
@@ -91,7 +91,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void p
         int until = a.until;
 #pragma unroll 1
         for (int t = 0; t < a.nsteps; ++t) {
-            wn::advect_step<METHOD, double>(p, a.h, a.h2, a.h6, a.gain, a.drift, velocity);
+            wn::advect_step<METHOD, 3, double>(p, a.h, a.h2, a.h6, a.gain, a.drift, velocity);
             if (a.every && --until == 0) {
                 store(snap);
                 snap += snap_stride;

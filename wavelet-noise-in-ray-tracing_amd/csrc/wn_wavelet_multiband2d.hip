@@ -19,6 +19,7 @@
 // profiles/multiband2d_timing.py, which builds the alternatives with the WN_MB2D_* macros below (the product defines none
 // of them); profiles/multiband2d_kernels.txt records what has been measured so far.
 #include "wn_internal.hpp"
+#include "wn_tile2d_lds.hpp"
 #include "wnoise_multiband2d.h"
 
 #include <cmath>
@@ -61,20 +62,11 @@ struct Mb2dArgs : wn::FootprintBands {
     GridArgs g;   // grids
 };
 
-// The whole tile from global memory to LDS in the padded layout, one row per wave and step; then the workgroup's barrier.
-__device__ __forceinline__ void stage_tile(float *lds, const float *coef, int n)
-{
-    const int stride = n + 2, lane = threadIdx.x & 63;
-    for (int y = threadIdx.x >> 6; y < n; y += kWorkgroup / 64)
-        for (int x = lane; x < stride; x += 64) lds[y * stride + x] = coef[y * n + (x >= n ? x - n : x)];
-    __syncthreads();
-}
-
 template <bool GRAD, bool LDS>
 __global__ __launch_bounds__(kWorkgroup, kWorkgroup / 128) void multiband2d_grid_kernel(const Mb2dArgs a)
 {
     extern __shared__ float tile_lds[];
-    if constexpr (LDS) stage_tile(tile_lds, a.coef, a.n);
+    if constexpr (LDS) wn::stage_tile<kWorkgroup>(tile_lds, a.coef, a.n);
     const float *coef = LDS ? tile_lds : a.coef;
     const GridArgs &g = a.g;
     const float den = (float)g.den;
@@ -121,7 +113,7 @@ template <bool GRAD, bool PER_POINT, bool LDS>
 __global__ __launch_bounds__(kWorkgroup, kWorkgroup / 128) void multiband2d_points_kernel(const Mb2dArgs a)
 {
     extern __shared__ float tile_lds[];
-    if constexpr (LDS) stage_tile(tile_lds, a.coef, a.n);
+    if constexpr (LDS) wn::stage_tile<kWorkgroup>(tile_lds, a.coef, a.n);
     const float *coef = LDS ? tile_lds : a.coef;
     for (size_t i = (size_t)blockIdx.x * kWorkgroup + threadIdx.x; i < a.count; i += (size_t)gridDim.x * kWorkgroup) {
         const float p[2] = {a.pts[2 * i], a.pts[2 * i + 1]};

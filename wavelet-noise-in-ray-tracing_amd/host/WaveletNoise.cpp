@@ -9,6 +9,7 @@
 #include "scalar_eval.h"
 #include "wn_host.hpp"
 #include "wnoise_advect.h"
+#include "wnoise_curl2d.h"
 #include "wnoise_footprint.h"
 #include "wnoise_multiband2d.h"
 
@@ -422,17 +423,18 @@ void WaveletNoise::WMultibandNoiseCurl(const float *xyz, size_t n, const int *of
 // one call of the C ABI, which checks `a`; the trajectory buffer exists only when a.traj_every asks for it
 namespace {
 
-template <typename Call>
-void advect_batch(const float *xyz, size_t n, const wn_advect &a, float *xyz_out, float *traj, Call call, const char *what)
+// D: floats per particle; Adv: wn_advect (D = 3) or wn_advect2d (D = 2)
+template <int D = 3, typename Adv, typename Call>
+void advect_batch(const float *pts, size_t n, const Adv &a, float *pts_out, float *traj, Call call, const char *what)
 {
     if (!n) return;
     const bool snaps = a.traj_every >= 1 && a.steps >= 0 && traj;
-    const size_t traj_bytes = snaps ? ((size_t)(a.steps / a.traj_every) + 1) * 3 * n * sizeof(float) : 0;
-    wnhost::DeviceBuffer pos(3 * n * sizeof(float)), path(traj_bytes ? traj_bytes : sizeof(float));
-    pos.upload(xyz);
+    const size_t traj_bytes = snaps ? ((size_t)(a.steps / a.traj_every) + 1) * D * n * sizeof(float) : 0;
+    wnhost::DeviceBuffer pos(D * n * sizeof(float)), path(traj_bytes ? traj_bytes : sizeof(float));
+    pos.upload(pts);
     check(call(pos.as<float>(), snaps ? path.as<float>() : nullptr), what); // in place on the device
     if (snaps) check(wn_copy_d2h(traj, path.get(), traj_bytes, nullptr), "wn_copy_d2h");
-    pos.download(xyz_out);
+    pos.download(pts_out);
 }
 
 } // namespace
@@ -475,6 +477,45 @@ void WaveletNoise::WMultibandNoiseAdvectCurl(const float *xyz, size_t n, const w
         return wn_multiband3d_curl_advect_points(tile(3), pos, n, offsets9 ? offsets9 : def, sarg, firstBand, nbands, w,
                                                  variance, &a, pos, path, nullptr);
     }, "wn_multiband3d_curl_advect_points");
+}
+
+// ---- curl noise on the 2-D tile and particles through it (include/wnoise_curl2d.h): the one-sample members on the host
+// (bit-identical to the kernels), the batched ones on the device; a 3-D tile goes to the C ABI, which reports it
+void WaveletNoise::WMultibandNoise2DCurl(const float p[2], float sarg, int firstBand, int nbands, const float *w, float v[2],
+                                         float variance) const
+{
+    if (tileDims == 3) return WMultibandNoise2DCurl(p, 1, sarg, firstBand, nbands, w, variance, v);
+    wnhost_multiband2d_curl(noiseCoefficients.empty() ? nullptr : noiseCoefficients.data(), tileSizeN, p, sarg, firstBand,
+                            nbands, w, variance, v);
+}
+
+void WaveletNoise::WMultibandNoise2DCurl(const float *xy, size_t n, float sarg, int firstBand, int nbands, const float *w,
+                                         float variance, float *out2) const
+{
+    if (!n) return;
+    wnhost::DeviceBuffer in(2 * n * sizeof(float)), res(2 * n * sizeof(float));
+    in.upload(xy);
+    check(wn_multiband2d_curl_points(tile(2), in.as<float>(), n, sarg, firstBand, nbands, w, variance, res.as<float>(),
+                                     nullptr), "wn_multiband2d_curl_points");
+    res.download(out2);
+}
+
+void WaveletNoise::WMultibandNoise2DAdvectCurl(const float p[2], const wn_advect2d &a, float sarg, int firstBand, int nbands,
+                                               const float *w, float p_out[2], float *traj, float variance) const
+{
+    if (tileDims == 3) return WMultibandNoise2DAdvectCurl(p, 1, a, sarg, firstBand, nbands, w, variance, p_out, traj);
+    if (wnhost_multiband2d_curl_advect(noiseCoefficients.empty() ? nullptr : noiseCoefficients.data(), tileSizeN, p, sarg,
+                                       firstBand, nbands, w, variance, &a, p_out, traj))
+        throw std::runtime_error("WMultibandNoise2DAdvectCurl: nbands outside 0..8, a method outside 0..2, negative steps or "
+                                 "traj_every, a non-finite h, gain or drift, or a trajectory without a buffer");
+}
+
+void WaveletNoise::WMultibandNoise2DAdvectCurl(const float *xy, size_t n, const wn_advect2d &a, float sarg, int firstBand,
+                                               int nbands, const float *w, float variance, float *xy_out, float *traj) const
+{
+    advect_batch<2>(xy, n, a, xy_out, traj, [&](float *pos, float *path) {
+        return wn_multiband2d_curl_advect_points(tile(2), pos, n, sarg, firstBand, nbands, w, variance, &a, pos, path, nullptr);
+    }, "wn_multiband2d_curl_advect_points");
 }
 
 // ---- batched members ----------------------------------------------------------------------------------

@@ -22,6 +22,7 @@
 
 struct wn_tile;   // include/wnoise.h
 struct wn_advect; // include/wnoise_advect.h
+struct wn_advect2d; // include/wnoise_curl2d.h
 
 // Statistical analysis structure (WaveletNoise.h:11-18)
 struct DataStats {
@@ -124,6 +125,22 @@ class WaveletNoise {
                            float variance, float *out) const;
     void WMultibandNoise2DGradient(const float *xy, size_t n, const float *s, bool fade, int firstBand, int nbands,
                                    const float *w, float variance, float *out3) const;
+    // Divergence-free curl noise on the 2-D tile and particles moved through it (include/wnoise_curl2d.h; absent from the
+    // reference): v = (d psi/dy, -d psi/dx) of the stream function psi = WMultibandNoise2D at ONE footprint s with the hard
+    // cut -- the d/dy channel of WMultibandNoise2DGradient, and its d/dx channel with the sign flipped.  The one-sample
+    // members are evaluated / traced on the host (wnhost_multiband2d_curl, wnhost_multiband2d_curl_advect), bit-identical to
+    // the kernels; the batched forms run on the device (wn_multiband2d_curl_points: n records {vx, vy} to out2;
+    // wn_multiband2d_curl_advect_points).  `a` carries method, steps, h, gain, drift and traj_every: the position after
+    // a.steps time steps through gain * v + drift goes to p_out / xy_out (which may be the input), and with a.traj_every =
+    // e >= 1 the positions after steps 0, e, 2e, ... to traj, a.steps / e + 1 snapshots of n points each ([snapshot][n][2]).
+    void WMultibandNoise2DCurl(const float p[2], float s, int firstBand, int nbands, const float *w, float v[2],
+                               float variance = 0.19686f) const;
+    void WMultibandNoise2DCurl(const float *xy, size_t n, float s, int firstBand, int nbands, const float *w, float variance,
+                               float *out2) const;
+    void WMultibandNoise2DAdvectCurl(const float p[2], const wn_advect2d &a, float s, int firstBand, int nbands,
+                                     const float *w, float p_out[2], float *traj = nullptr, float variance = 0.19686f) const;
+    void WMultibandNoise2DAdvectCurl(const float *xy, size_t n, const wn_advect2d &a, float s, int firstBand, int nbands,
+                                     const float *w, float variance, float *xy_out, float *traj = nullptr) const;
     // Divergence-free curl noise (absent from the reference; include/wnoise.h): the curl of the vector potential whose
     // components are evaluate3D (WMultibandNoiseCurl: WMultibandNoise, normal == NULL) of this tile shifted by the whole-cell
     // offsets offsets9 = (x, y, z) of psi0, psi1, psi2; nullptr: defaultCurlOffsets().  evaluate3DCurl(p, ., v) is

@@ -9,6 +9,7 @@
 
 #include "wn_eval.hpp"
 #include "wnoise_advect.h"
+#include "wnoise_curl2d.h"
 #include "wnoise_perlin_curl.h"
 
 namespace {
@@ -143,6 +144,41 @@ float wnhost_multiband2d_footprint(const float *coef, int n, const float p[2], f
                 : wn::multiband2d_footprint_exact<false>(a, a.coef, p, s, nullptr);
 }
 
+void wnhost_multiband2d_curl(const float *coef, int n, const float p[2], float s, int first_band, int nbands, const float *w,
+                             float var_per_band, float v[2])
+{
+    v[0] = v[1] = 0.0f;
+    Footprint a;
+    if (!footprint_setup(a, coef, n, first_band, nbands, w, var_per_band, 0)) return;
+    wn::multiband2d_curl_exact(a, a.coef, p, s, v);
+}
+
+int wnhost_multiband2d_curl_advect(const float *coef, int n, const float p_in[2], float s, int first_band, int nbands,
+                                   const float *w, float var_per_band, const wn_advect2d *a, float p_out[2], float *traj)
+{
+    if (!a || a->method < WN_ADVECT_EULER || a->method > WN_ADVECT_RK4 || a->steps < 0 || a->traj_every < 0) return 1;
+    if (!std::isfinite(a->h) || !std::isfinite(a->gain) || !std::isfinite(a->drift[0]) || !std::isfinite(a->drift[1]) ||
+        (a->traj_every && !traj))
+        return 1;
+    Footprint f;
+    if (!footprint_setup(f, coef, n, first_band, nbands, w, var_per_band, 0)) return 1;
+    const auto velocity = [&](const float q[2], float v[2]) { wn::multiband2d_curl_exact(f, f.coef, q, s, v); };
+    const float h = a->h, h2 = 0.5f * a->h, h6 = a->h / 6.0f;
+    float p[2] = {p_in[0], p_in[1]};
+    if (a->traj_every) traj[0] = p[0], traj[1] = p[1];
+    for (int t = 1; t <= a->steps; ++t) {
+        if (a->method == WN_ADVECT_EULER) wn::advect_step<WN_ADVECT_EULER, 2>(p, h, h2, h6, a->gain, a->drift, velocity);
+        else if (a->method == WN_ADVECT_MIDPOINT) wn::advect_step<WN_ADVECT_MIDPOINT, 2>(p, h, h2, h6, a->gain, a->drift, velocity);
+        else wn::advect_step<WN_ADVECT_RK4, 2>(p, h, h2, h6, a->gain, a->drift, velocity);
+        if (a->traj_every && t % a->traj_every == 0) {
+            float *snap = traj + 2 * (size_t)(t / a->traj_every);
+            snap[0] = p[0], snap[1] = p[1];
+        }
+    }
+    p_out[0] = p[0], p_out[1] = p[1];
+    return 0;
+}
+
 float wnhost_wavelet_multiband_texture_value(const float *coef, int n, double scale, int first_band, int nbands,
                                              const float *w, float var_per_band, int fade, const float xyz[3], float s)
 {
@@ -233,9 +269,9 @@ int wnhost_perlin_curl_advect(const int *perm, int kind, int depth, const double
     double p[3] = {p_in[0], p_in[1], p_in[2]};
     if (a->traj_every) traj[0] = p[0], traj[1] = p[1], traj[2] = p[2];
     for (int t = 1; t <= a->steps; ++t) {
-        if (a->method == WN_ADVECT_EULER) wn::advect_step<WN_ADVECT_EULER, double>(p, h, h2, h6, gain, drift, velocity);
-        else if (a->method == WN_ADVECT_MIDPOINT) wn::advect_step<WN_ADVECT_MIDPOINT, double>(p, h, h2, h6, gain, drift, velocity);
-        else wn::advect_step<WN_ADVECT_RK4, double>(p, h, h2, h6, gain, drift, velocity);
+        if (a->method == WN_ADVECT_EULER) wn::advect_step<WN_ADVECT_EULER, 3, double>(p, h, h2, h6, gain, drift, velocity);
+        else if (a->method == WN_ADVECT_MIDPOINT) wn::advect_step<WN_ADVECT_MIDPOINT, 3, double>(p, h, h2, h6, gain, drift, velocity);
+        else wn::advect_step<WN_ADVECT_RK4, 3, double>(p, h, h2, h6, gain, drift, velocity);
         if (a->traj_every && t % a->traj_every == 0) {
             double *snap = traj + 3 * (size_t)(t / a->traj_every);
             snap[0] = p[0], snap[1] = p[1], snap[2] = p[2];

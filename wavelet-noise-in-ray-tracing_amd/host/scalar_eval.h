@@ -75,6 +75,22 @@ WNHOST_API float wnhost_multiband3d_footprint(const float *coef, int n, const fl
 // every channel.
 WNHOST_API float wnhost_multiband2d_footprint(const float *coef, int n, const float p[2], float s, int fade, int first_band,
                                               int nbands, const float *w, float var_per_band, float *grad_or_null);
+// Curl noise on the 2-D tile (absent from the reference; include/wnoise_curl2d.h): v = (d psi/dy, -d psi/dx) of the stream
+// function psi = the function above at footprint s with fade == 0 -- v[0] has the bits of its d/dy channel, v[1] those of its
+// d/dx channel with the sign flipped: the bits of wn_multiband2d_curl_points.  n == 0, coef == NULL or nbands outside
+// 0..8 -> 0 in both.
+WNHOST_API void wnhost_multiband2d_curl(const float *coef, int n, const float p[2], float s, int first_band, int nbands,
+                                        const float *w, float var_per_band, float v[2]);
+// One particle traced through that field (include/wnoise_curl2d.h, whose wn_advect2d `a` is wn_advect with a drift of two
+// components): p_out receives the position after a->steps steps of wn::advect_step<., 2>, the step the device kernel runs,
+// around wnhost_multiband2d_curl -- the bits of wn_multiband2d_curl_advect_points.  traj (read only when a->traj_every >= 1;
+// may then not be NULL): a->steps / a->traj_every + 1 packed pairs, the positions after steps 0, e, 2e, ...  p_out may be
+// p_in.  n == 0 or coef == NULL: v = 0, pure drift.  Returns 0, or 1 and writes nothing when nbands or `a` is one that
+// entry point refuses.
+struct wn_advect2d;
+WNHOST_API int wnhost_multiband2d_curl_advect(const float *coef, int n, const float p_in[2], float s, int first_band,
+                                              int nbands, const float *w, float var_per_band, const struct wn_advect2d *a,
+                                              float p_out[2], float *traj);
 // grey level of wavelet_multiband_texture::value (texture.h; wn_wavelet_multiband_texture_points): the function above
 // (normal == NULL) at (float)((double)xyz * scale) and footprint s, through wavelet_texture's grey; coef == NULL: 0.5
 WNHOST_API float wnhost_wavelet_multiband_texture_value(const float *coef, int n, double scale, int first_band, int nbands,

@@ -394,6 +394,40 @@ class WaveletNoise:
         WMultibandNoise2D."""
         return self._multiband2d(p, s, firstBand, nbands, w, variance, fade, True)
 
+    # -- curl noise on the 2-D tile and particles moved through it (include/wnoise_curl2d.h; absent from the reference)
+    def WMultibandNoise2DCurl(self, p, s, firstBand, nbands, w, variance=0.19686):
+        """The divergence-free velocity (d psi/dy, -d psi/dx) of the stream function psi = WMultibandNoise2D at the scalar
+        footprint s, at one point or an (N, 2) batch (wn_multiband2d_curl_points): an (N, 2) CUDA tensor of {vx, vy}.  vx has
+        the bits of WMultibandNoise2DGradient's d/dy column, vy those of its d/dx column with the sign flipped.
+        firstBand=-1, nbands=1, w=[1], variance=1 is the curl of evaluate2D."""
+        pts = _dev(p, torch.float32).reshape(-1, 2)
+        out = torch.empty((pts.shape[0], 2), dtype=torch.float32, device="cuda")
+        wa = (C.c_float * max(1, nbands))(*[float(x) for x in list(w)[:nbands]])
+        check(_lib.wn_multiband2d_curl_points(self._handle(2), _ptr(pts), pts.shape[0], float(s), int(firstBand), int(nbands),
+                                              wa, float(variance), _ptr(out), _stream()))
+        return out
+
+    def WMultibandNoise2DAdvectCurl(self, pts, h, steps, s, firstBand, nbands, w, variance=0.19686, method="rk4", gain=1.0,
+                                    drift=None, trajectory_every=0):
+        """An (N, 2) batch of particles moved `steps` time steps of size h (negative: backwards) through the velocity
+        gain * WMultibandNoise2DCurl(., s, firstBand, nbands, w, variance) + drift, all steps inside the kernel
+        (wn_multiband2d_curl_advect_points).  method: "euler", "midpoint" or "rk4".  Returns the final (N, 2) positions; with
+        trajectory_every = e >= 1 also the (steps // e + 1, N, 2) positions after steps 0, e, 2e, ...  Float32 with every
+        operation rounded on its own: the bits of stepping with WMultibandNoise2DCurl and separately rounded float32 tensor
+        operations."""
+        if method not in self._ADVECT_METHODS:
+            raise ValueError(f"method: one of {sorted(self._ADVECT_METHODS)}")
+        pts = _dev(pts, torch.float32).reshape(-1, 2)
+        n, steps, every = pts.shape[0], int(steps), int(trajectory_every)
+        a = _capi.wn_advect2d(self._ADVECT_METHODS[method], steps, float(h), float(gain),
+                              (C.c_float * 2)(*([0.0] * 2 if drift is None else [float(x) for x in drift])), every)
+        wa = (C.c_float * max(1, nbands))(*[float(x) for x in list(w)[:nbands]])
+        out = torch.empty((n, 2), dtype=torch.float32, device="cuda")
+        traj = torch.empty((steps // every + 1, n, 2), dtype=torch.float32, device="cuda") if every >= 1 and steps >= 0 else None
+        check(_lib.wn_multiband2d_curl_advect_points(self._handle(2), _ptr(pts), n, float(s), int(firstBand), int(nbands), wa,
+                                                     float(variance), C.byref(a), _ptr(out), _ptr(traj), _stream()))
+        return out if traj is None else (out, traj)
+
     def evaluate3DProjectedGradient(self, p, normal):
         """evaluate3DProjected and its gradient with respect to p, the normal held fixed (wn_eval3d_projected_grad_points):
         (N, 4).  `normal`: one for all points, or one per point.  The value column has the bits of evaluate3DProjected;
@@ -827,6 +861,14 @@ def generate2DMultibandNoiseGradient(noise, image_size, s=-16.0, firstBand=0, nb
     """generate2DMultibandNoise with the gradient with respect to p (wn_multiband2d_grad_grid): [3, ny, nx] -- value, d/dx,
     d/dy; the value plane has the bits of generate2DMultibandNoise."""
     return _multiband2d_image(_lib.wn_multiband2d_grad_grid, 3, noise, image_size, s, firstBand, nbands, w, variance, den,
+                              out)
+
+
+def generate2DMultibandNoiseCurl(noise, image_size, s=-16.0, firstBand=0, nbands=5, w=None, variance=0.19686, den=None,
+                                 out=None):
+    """The curl of generate2DMultibandNoise's stream function on its lattice (wn_multiband2d_curl_grid): [2, ny, nx] -- vx =
+    d/dy and vy = -d/dx of generate2DMultibandNoiseGradient, the same bits but for vy's sign."""
+    return _multiband2d_image(_lib.wn_multiband2d_curl_grid, 2, noise, image_size, s, firstBand, nbands, w, variance, den,
                               out)
 
 
