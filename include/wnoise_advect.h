@@ -8,8 +8,8 @@
  * band, gives v = 0.  One call moves every particle `steps` explicit time steps of size h through the stage velocity
  *     k(q) = gain * v(q) + drift
  * inside ONE kernel launch per kAdvectLaunchSteps steps (csrc/wn_wavelet_advect.hip; launches are chained on `stream`):
- * the position and the stage sums stay in registers between steps.  The field does not depend on time and has no
- * boundaries; Perlin potentials are served by wnoise_perlin_advect.h.
+ * the position and the stage sums stay in registers between steps.  The field does not depend on time; solid
+ * boundaries (Bridson's distance ramp) are served by wnoise_bounded.h, Perlin potentials by wnoise_perlin_advect.h.
  *
  * Arithmetic, which is the contract.  Everything is float32; every product and every sum is rounded on its own (unfused).
  * Per component:

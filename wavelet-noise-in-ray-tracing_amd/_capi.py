@@ -1,5 +1,5 @@
 """ctypes binding of libwnoise_hip.so (include/wnoise.h, include/wnoise_perlin_curl.h, include/wnoise_footprint.h,
-include/wnoise_perlin_footprint.h, include/wnoise_multiband2d.h, include/wnoise_advect.h,
+include/wnoise_perlin_footprint.h, include/wnoise_multiband2d.h, include/wnoise_advect.h, include/wnoise_bounded.h,
 include/wnoise_perlin_advect.h, include/wnoise_curl2d.h).
 
 The library is the product: if it is missing or fails to load this module raises, it never
@@ -175,6 +175,26 @@ ADVECT_SIGNATURES = {
     "wn_advect_launch_steps": (_i, []),
 }
 
+# name -> (restype, argtypes); every symbol include/wnoise_bounded.h declares, and its wn_obstacle.
+WN_OBSTACLE_SPHERE, WN_OBSTACLE_CONTAINER, WN_OBSTACLE_HALFSPACE = range(3)
+WN_MAX_OBSTACLES = 16
+
+
+class wn_obstacle(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("c", C.c_float * 3), ("r", C.c_float), ("d0", C.c_float),
+                ("reserved", C.c_int32 * 2)]
+
+
+_op = C.POINTER(wn_obstacle)
+BOUNDED_SIGNATURES = {
+    # tile, xyz, n, offsets9, [s, first_band, nbands, w, var,] obstacles, nobs, out3, stream
+    "wn_eval3d_curl_bounded_points": (_i, [_vp, _vp, _sz, _i32p, _op, _i, _vp, _vp]),
+    "wn_multiband3d_curl_bounded_points": (_i, [_vp, _vp, _sz, _i32p, _f, _i, _i, _fp, _f, _op, _i, _vp, _vp]),
+    # tile, xyz_in, n, offsets9, [s, first_band, nbands, w, var,] obstacles, nobs, a, xyz_out, traj, stream
+    "wn_eval3d_curl_bounded_advect_points": (_i, [_vp, _vp, _sz, _i32p, _op, _i, _ap, _vp, _vp, _vp]),
+    "wn_multiband3d_curl_bounded_advect_points": (_i, [_vp, _vp, _sz, _i32p, _f, _i, _i, _fp, _f, _op, _i, _ap, _vp, _vp, _vp]),
+}
+
 # name -> (restype, argtypes); every symbol include/wnoise_perlin_advect.h declares.
 PERLIN_ADVECT_SIGNATURES = {
     "wn_perlin_curl_advect_points": (_i, [_vp, _vp, _sz, _i, _i, _i32p, _ap, _vp, _vp, _vp]),
@@ -211,7 +231,8 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (*SIGNATURES.items(), *PERLIN_CURL_SIGNATURES.items(), *FOOTPRINT_SIGNATURES.items(),
                               *PERLIN_FOOTPRINT_SIGNATURES.items(), *MULTIBAND2D_SIGNATURES.items(),
-                              *ADVECT_SIGNATURES.items(), *PERLIN_ADVECT_SIGNATURES.items(), *CURL2D_SIGNATURES.items()):
+                              *ADVECT_SIGNATURES.items(), *BOUNDED_SIGNATURES.items(), *PERLIN_ADVECT_SIGNATURES.items(),
+                              *CURL2D_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

@@ -613,6 +613,212 @@ WN_EVAL_FN void multiband_curl_exact(const A &a, const float p[3], float v[3])
     curl_of_sums(acc, v);
 }
 
+// ---- solid boundaries of that curl field (include/wnoise_bounded.h; absent from the reference) -----------------------------
+// Bridson, Houriham and Nordenstam 2007: the potential is faded to zero towards a solid by a smooth ramp A of the distance
+// to it, and the velocity is the curl of the faded potential, v = curl(A Psi) = A curl Psi + grad A x Psi: still
+// divergence-free, and on a solid A -> 0 and grad A is parallel to the normal, so the normal component of v vanishes.
+// O is wn_obstacle (kind, c[3], r, d0); this header does not include it.  Everything below is float32 and unfused.
+constexpr int kMaxObstacles = 16; // WN_MAX_OBSTACLES
+constexpr int kObstacleSphere = 0, kObstacleContainer = 1, kObstacleHalfspace = 2;
+
+// What is wrong with an obstacle list (the checks of include/wnoise_bounded.h), or nullptr.
+template <typename O>
+inline const char *obstacle_fault(const O *obs, int nobs)
+{
+    if (nobs < 0 || nobs > kMaxObstacles) return "nobs must be in 0..16";
+    if (nobs && !obs) return "obstacles_host is NULL";
+    for (int j = 0; j < nobs; ++j) {
+        const O &o = obs[j];
+        if (o.kind < kObstacleSphere || o.kind > kObstacleHalfspace) return "an obstacle's kind must be 0, 1 or 2";
+        if (!std::isfinite(o.c[0]) || !std::isfinite(o.c[1]) || !std::isfinite(o.c[2]) || !std::isfinite(o.r) ||
+            !std::isfinite(o.d0))
+            return "an obstacle's c, r and d0 must be finite";
+        if (!(o.d0 > 0.0f)) return "an obstacle's d0 must be > 0";
+        if (o.kind != kObstacleHalfspace && !(o.r > 0.0f)) return "a sphere's or container's r must be > 0";
+        if (o.kind == kObstacleHalfspace && o.c[0] == 0.0f && o.c[1] == 0.0f && o.c[2] == 0.0f)
+            return "a half-space's normal must not be zero";
+        if (o.reserved[0] != 0 || o.reserved[1] != 0) return "an obstacle's reserved fields must be 0";
+    }
+    return nullptr;
+}
+
+// The signed distance d of x to obstacle o (positive in the fluid) and its gradient nrm.
+//     sphere, container  dx = x - c, l = sqrtf((dx0*dx0 + dx1*dx1) + dx2*dx2), m = dx / l (0 when l == 0);
+//                        sphere: d = l - r, nrm = m; container: d = r - l, nrm = -m
+//     half-space         d = ((n0*x0 + n1*x1) + n2*x2) - o, nrm = n as given (not normalised: d is linear with gradient n)
+template <typename O>
+WN_EVAL_FN float obstacle_distance(const O &o, const float x[3], float nrm[3])
+{
+    if (o.kind == kObstacleHalfspace) {
+        WN_UNROLL
+        for (int c = 0; c < 3; ++c) nrm[c] = o.c[c];
+        return ((o.c[0] * x[0] + o.c[1] * x[1]) + o.c[2] * x[2]) - o.r;
+    }
+    const float dx[3] = {x[0] - o.c[0], x[1] - o.c[1], x[2] - o.c[2]};
+    const float l = sqrtf((dx[0] * dx[0] + dx[1] * dx[1]) + dx[2] * dx[2]);
+    const bool solid = o.kind == kObstacleSphere;
+    WN_UNROLL
+    for (int c = 0; c < 3; ++c) {
+        const float m = l == 0.0f ? 0.0f : dx[c] / l;
+        nrm[c] = solid ? m : -m;
+    }
+    return solid ? l - o.r : o.r - l;
+}
+
+// Where x lies, and for a near point the product A of the obstacles' ramps and its gradient G.
+//     inside  some obstacle has d <= 0: v = 0
+//     far     every obstacle has d >= d0: the unbounded field (A = 1, G = 0; the potential values are not needed)
+//     near    every other point.  Obstacles in list order, those with d >= d0 skipped; Bridson's quintic of r = d / d0,
+//             alpha = r * (1.875f + r2 * (-1.25f + r2 * 0.375f)), r2 = r * r, and its derivative
+//             dalpha = (1.875f * (q * q)) / d0, q = 1.0f - r2; per component G = G * alpha + (A * dalpha) * nrm, then
+//             A = A * alpha.  Overlapping ramps multiply: A stays C1 across every d = d0.
+constexpr int kBoundFar = 0, kBoundNear = 1, kBoundInside = 2;
+template <typename O>
+WN_EVAL_FN int obstacle_ramp(const O *obs, int nobs, const float x[3], float &A, float G[3])
+{
+    A = 1.0f;
+    G[0] = G[1] = G[2] = 0.0f;
+    int where = kBoundFar;
+    for (int j = 0; j < nobs; ++j) {
+        float nrm[3];
+        const float d = obstacle_distance(obs[j], x, nrm);
+        const float d0 = obs[j].d0;
+        if (d <= 0.0f) return kBoundInside;
+        if (d >= d0) continue;
+        where = kBoundNear;
+        const float r = d / d0;
+        const float r2 = r * r;
+        const float alpha = r * (1.875f + r2 * (-1.25f + r2 * 0.375f));
+        const float q = 1.0f - r2;
+        const float dalpha = (1.875f * (q * q)) / d0;
+        const float ad = A * dalpha;
+        WN_UNROLL
+        for (int c = 0; c < 3; ++c) G[c] = G[c] * alpha + ad * nrm[c];
+        A = A * alpha;
+    }
+    return where;
+}
+
+// The three potential values at one point: psi[K] is the value sum of eval3d_exact_impl -- tap weight (w_x*w_y)*w_z,
+// f2 -> f1 -> f0, unfused -- over the coefficients at potential K's offset indices: the bits of eval3d_exact on T_K.
+template <bool PADDED, bool POW2, int K>
+WN_EVAL_FN float curl_potential_value(const float *coef, int n, int nmask, const int *off, int mx, int my, int mz,
+                                      const float *wx, const float *wy, const float *wz)
+{
+    const int stride = PADDED ? n + 2 : n;
+    int cx[3], cy[3], cz[3];
+    WN_UNROLL
+    for (int f = 0; f < 3; ++f) {
+        cx[f] = POW2 ? ((mx + f - 1 + off[3 * K]) & nmask) : dmod(mx + f - 1 + off[3 * K], n, -1);
+        cy[f] = (POW2 ? ((my + f - 1 + off[3 * K + 1]) & nmask) : dmod(my + f - 1 + off[3 * K + 1], n, -1)) * stride;
+        cz[f] = (POW2 ? ((mz + f - 1 + off[3 * K + 2]) & nmask) : dmod(mz + f - 1 + off[3 * K + 2], n, -1)) * stride * n;
+    }
+    float result = 0.0f;
+    WN_UNROLL
+    for (int fz = 0; fz < 3; ++fz)
+        WN_UNROLL
+        for (int fy = 0; fy < 3; ++fy) {
+            float c[3];
+            if (PADDED) {
+                __builtin_memcpy(c, coef + cx[0] + cy[fy] + cz[fz], sizeof(c));
+            } else {
+                WN_UNROLL
+                for (int fx = 0; fx < 3; ++fx) c[fx] = coef[cx[fx] + cy[fy] + cz[fz]];
+            }
+            WN_UNROLL
+            for (int fx = 0; fx < 3; ++fx) {
+                const float weight = wx[fx] * wy[fy] * wz[fz];
+                result += weight * c[fx];
+            }
+        }
+    return result;
+}
+
+template <bool PADDED = false>
+WN_EVAL_FN void eval3d_potential_values(const float *coef, int n, int nmask, const int *off, float px, float py, float pz,
+                                        float psi[3])
+{
+    if (n == 0) {
+        psi[0] = psi[1] = psi[2] = 0.0f;
+        return;
+    }
+    int mx, my, mz;
+    float wx[3], wy[3], wz[3];
+    bspline(px, mx, wx[0], wx[1], wx[2]);
+    bspline(py, my, wy[0], wy[1], wy[2]);
+    bspline(pz, mz, wz[0], wz[1], wz[2]);
+    if (nmask >= 0) {
+        psi[0] = curl_potential_value<PADDED, true, 0>(coef, n, nmask, off, mx, my, mz, wx, wy, wz);
+        psi[1] = curl_potential_value<PADDED, true, 1>(coef, n, nmask, off, mx, my, mz, wx, wy, wz);
+        psi[2] = curl_potential_value<PADDED, true, 2>(coef, n, nmask, off, mx, my, mz, wx, wy, wz);
+    } else {
+        psi[0] = curl_potential_value<PADDED, false, 0>(coef, n, nmask, off, mx, my, mz, wx, wy, wz);
+        psi[1] = curl_potential_value<PADDED, false, 1>(coef, n, nmask, off, mx, my, mz, wx, wy, wz);
+        psi[2] = curl_potential_value<PADDED, false, 2>(coef, n, nmask, off, mx, my, mz, wx, wy, wz);
+    }
+}
+
+// The same of WMultibandNoise potentials: multiband_exact's value arm on T_K -- psi[K] += w[b] * (band b's value at
+// q_b = 2 * p * 2^(first_band+b)), divided by out_div when apply_div.  No active band: 0.
+template <bool PADDED, typename A>
+WN_EVAL_FN void multiband_potential_values(const A &a, const float p[3], float psi[3])
+{
+    float acc[3] = {0.0f, 0.0f, 0.0f};
+    for (int b = 0; b < a.nbands; ++b) {
+        const float s = a.band_scale[b];
+        float vb[3];
+        eval3d_potential_values<PADDED>(a.coef, a.n, a.nmask, a.off, 2.0f * p[0] * s, 2.0f * p[1] * s, 2.0f * p[2] * s, vb);
+        WN_UNROLL
+        for (int k = 0; k < 3; ++k) acc[k] += a.band_w[b] * vb[k];
+    }
+    WN_UNROLL
+    for (int k = 0; k < 3; ++k) psi[k] = a.apply_div ? acc[k] / a.out_div : acc[k];
+}
+
+// The bounded velocity at p from `where`, A, G of obstacle_ramp: curl(v) writes the unbounded curl c (its entry point's
+// bits), values(psi) the potential values.  inside: 0.  far: c, and values is not called.  near:
+// v = A * c + G x Psi, e.g. v0 = A * c0 + (G1 * psi2 - G2 * psi1), each operation rounded on its own.
+template <typename Curl, typename Values>
+WN_EVAL_FN void bounded_velocity(int where, float A, const float G[3], float v[3], const Curl &curl, const Values &values)
+{
+    if (where == kBoundInside) {
+        v[0] = v[1] = v[2] = 0.0f;
+        return;
+    }
+    curl(v);
+    if (where == kBoundFar) return;
+    float psi[3];
+    values(psi);
+    const float x0 = G[1] * psi[2] - G[2] * psi[1];
+    const float x1 = G[2] * psi[0] - G[0] * psi[2];
+    const float x2 = G[0] * psi[1] - G[1] * psi[0];
+    v[0] = A * v[0] + x0;
+    v[1] = A * v[1] + x1;
+    v[2] = A * v[2] + x2;
+}
+
+// eval3d_curl_exact / multiband_curl_exact with the obstacles obs[0 .. nobs): nobs == 0 and far points carry their bits.
+template <bool PADDED = false, typename O>
+WN_EVAL_FN void eval3d_curl_bounded_exact(const float *coef, int n, int nmask, const int *off, const O *obs, int nobs,
+                                          const float p[3], float v[3])
+{
+    float A, G[3];
+    const int where = obstacle_ramp(obs, nobs, p, A, G);
+    bounded_velocity(
+        where, A, G, v, [&](float *c) { eval3d_curl_exact<PADDED>(coef, n, nmask, off, p[0], p[1], p[2], c); },
+        [&](float *psi) { eval3d_potential_values<PADDED>(coef, n, nmask, off, p[0], p[1], p[2], psi); });
+}
+
+template <bool PADDED, typename E, typename O>
+WN_EVAL_FN void multiband_curl_bounded_exact(const E &a, const O *obs, int nobs, const float p[3], float v[3])
+{
+    float A, G[3];
+    const int where = obstacle_ramp(obs, nobs, p, A, G);
+    bounded_velocity(
+        where, A, G, v, [&](float *c) { multiband_curl_exact<PADDED>(a, p, c); },
+        [&](float *psi) { multiband_potential_values<PADDED>(a, p, psi); });
+}
+
 // ---- one explicit time step of a particle through a velocity field (include/wnoise_advect.h; absent from the reference) --
 // METHOD: WN_ADVECT_EULER / _MIDPOINT / _RK4 (0, 1, 2).  D: the dimension, 3 (include/wnoise_advect.h,
 // include/wnoise_perlin_advect.h) or 2 (include/wnoise_curl2d.h).  T: float (the wavelet potentials) or double (the Perlin

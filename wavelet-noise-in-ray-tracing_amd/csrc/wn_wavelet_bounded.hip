@@ -1,0 +1,267 @@
+// wn_wavelet_bounded.hip -- the curl noise of 3-D wavelet noise potentials with solid boundaries, on point lists and under
+// particle advection (include/wnoise_bounded.h).
+//
+// The velocity is wn::eval3d_curl_bounded_exact / multiband_curl_bounded_exact (wn_eval.hpp), stated once for these kernels
+// and for the host's wnhost_eval3d_curl_bounded; the time step is wn::advect_step, as in wn_wavelet_advect.hip.
+//
+//   curl3d_bounded_points_kernel<PADDED, MB>          one point per lane in a grid-stride loop, records {vx, vy, vz}.
+//   curl3d_bounded_advect_kernel<PADDED, MB, METHOD>  one particle per lane in a grid-stride loop; position, stage point and
+//                                                     RK4's running sum in registers, as curl3d_advect_kernel.
+//
+// The obstacle list travels by value in the launch arguments (16 x 32 bytes): it is the same for every lane, so the
+// obstacle loop reads it with scalar loads and branches on the kind as a wave.  A lane that is far from every obstacle
+// runs the unbounded evaluator and nothing else; a near lane then walks its 27 taps a second time for the three potential
+// values (the rows are in cache, the bits are those of one pass), so the far path keeps the unbounded kernel's live set;
+// an inside lane evaluates nothing.  No LDS, no private segment.
+//
+// Launch chaining is wn_wavelet_advect.hip's: a launch integrates at most wn_advect_launch_steps() steps, a longer trace is
+// a chain of launches on the stream, and a position crosses a launch boundary as the three floats it is.
+#include "wn_internal.hpp"
+#include "wnoise_bounded.h"
+
+#include <algorithm>
+#include <cmath>
+
+namespace {
+
+using wn::CurlEval;
+
+static_assert(WN_MAX_OBSTACLES == wn::kMaxObstacles && sizeof(wn_obstacle) == 32, "include/wnoise_bounded.h");
+static_assert(WN_OBSTACLE_SPHERE == wn::kObstacleSphere && WN_OBSTACLE_CONTAINER == wn::kObstacleContainer &&
+                  WN_OBSTACLE_HALFSPACE == wn::kObstacleHalfspace,
+              "include/wnoise_bounded.h");
+
+constexpr size_t kBoundedBlockCap = 256u * 8u; // of the curl point kernel's: the lanes hold 27 row loads each
+
+struct Obstacles {
+    wn_obstacle list[WN_MAX_OBSTACLES];
+    int nobs;
+};
+
+struct BoundedPointsArgs {
+    CurlEval e;
+    Obstacles o;
+    const float *pts; // xyz interleaved
+    float *out;       // {vx, vy, vz} per point
+    size_t count;
+};
+
+struct BoundedAdvectArgs { // AdvectArgs of wn_wavelet_advect.hip, and the obstacles
+    CurlEval e;
+    Obstacles o;
+    const float *in;
+    float *out;
+    float *snap;
+    size_t count;
+    int nsteps, every, until, snap_input;
+    float h, h2, h6, gain, drift[3];
+};
+
+template <bool PADDED, bool MB>
+__device__ __forceinline__ void bounded_velocity_at(const CurlEval &e, const Obstacles &o, const float q[3], float v[3])
+{
+    if (MB) wn::multiband_curl_bounded_exact<PADDED>(e, o.list, o.nobs, q, v);
+    else wn::eval3d_curl_bounded_exact<PADDED>(e.coef, e.n, e.nmask, e.off, o.list, o.nobs, q, v);
+}
+
+template <bool PADDED, bool MB>
+__global__ __launch_bounds__(256) void curl3d_bounded_points_kernel(const BoundedPointsArgs a)
+{
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.count; i += (size_t)gridDim.x * blockDim.x) {
+        const float p[3] = {a.pts[3 * i], a.pts[3 * i + 1], a.pts[3 * i + 2]};
+        float v[3];
+        bounded_velocity_at<PADDED, MB>(a.e, a.o, p, v);
+        a.out[3 * i] = v[0];
+        a.out[3 * i + 1] = v[1];
+        a.out[3 * i + 2] = v[2];
+    }
+}
+
+template <bool PADDED, bool MB, int METHOD>
+__global__ __launch_bounds__(256) void curl3d_bounded_advect_kernel(const BoundedAdvectArgs a)
+{
+    const auto velocity = [&](const float q[3], float v[3]) { bounded_velocity_at<PADDED, MB>(a.e, a.o, q, v); };
+    const size_t snap_stride = 3 * a.count;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.count; i += (size_t)gridDim.x * blockDim.x) {
+        float p[3] = {a.in[3 * i], a.in[3 * i + 1], a.in[3 * i + 2]};
+        float *snap = a.snap + 3 * i; // not dereferenced unless every != 0
+        auto store = [&](float *dst) {
+            dst[0] = p[0];
+            dst[1] = p[1];
+            dst[2] = p[2];
+        };
+        if (a.snap_input) {
+            store(snap);
+            snap += snap_stride;
+        }
+        int until = a.until;
+#pragma unroll 1
+        for (int t = 0; t < a.nsteps; ++t) {
+            wn::advect_step<METHOD>(p, a.h, a.h2, a.h6, a.gain, a.drift, velocity);
+            if (a.every && --until == 0) {
+                store(snap);
+                snap += snap_stride;
+                until = a.every;
+            }
+        }
+        store(a.out + 3 * i);
+    }
+}
+
+int obstacle_args(const wn_obstacle *obstacles_host, int nobs, const char *entry, Obstacles *o)
+{
+    if (const char *why = wn::obstacle_fault(obstacles_host, nobs)) return wn::fail(WN_ERR_INVALID, "%s: %s", entry, why);
+    *o = Obstacles{};
+    std::copy(obstacles_host, obstacles_host + nobs, o->list);
+    o->nobs = nobs;
+    return WN_OK;
+}
+
+int launch_bounded_points(const wn_tile *tile, const CurlEval &e, const Obstacles &o, const float *xyz_dev, size_t n,
+                          float *out3_dev, hipStream_t stream)
+{
+    if (!xyz_dev || !out3_dev) return wn::fail(WN_ERR_INVALID, "points/out pointer is NULL");
+    const BoundedPointsArgs a{e, o, xyz_dev, out3_dev, n};
+    const dim3 grid(wn::stride_blocks(n, kBoundedBlockCap)), block(256);
+    const bool padded = tile->dev_padded != nullptr;
+    if (e.mb) {
+        if (padded) hipLaunchKernelGGL((curl3d_bounded_points_kernel<true, true>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((curl3d_bounded_points_kernel<false, true>), grid, block, 0, stream, a);
+    } else {
+        if (padded) hipLaunchKernelGGL((curl3d_bounded_points_kernel<true, false>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((curl3d_bounded_points_kernel<false, false>), grid, block, 0, stream, a);
+    }
+    WN_LAUNCH_CHECK("curl3d_bounded_points_kernel");
+    return WN_OK;
+}
+
+template <bool PADDED, bool MB>
+void launch_method(int method, dim3 grid, hipStream_t stream, const BoundedAdvectArgs &a)
+{
+    const dim3 block(256);
+    if (method == WN_ADVECT_EULER)
+        hipLaunchKernelGGL((curl3d_bounded_advect_kernel<PADDED, MB, WN_ADVECT_EULER>), grid, block, 0, stream, a);
+    else if (method == WN_ADVECT_MIDPOINT)
+        hipLaunchKernelGGL((curl3d_bounded_advect_kernel<PADDED, MB, WN_ADVECT_MIDPOINT>), grid, block, 0, stream, a);
+    else hipLaunchKernelGGL((curl3d_bounded_advect_kernel<PADDED, MB, WN_ADVECT_RK4>), grid, block, 0, stream, a);
+}
+
+// The entry points after their tile, offset, band and obstacle checks: the checks of `a` and of the three buffers, then the
+// chain of launches, both as wn_wavelet_advect.hip's advect_points.
+int bounded_advect_points(const wn_tile *tile, const CurlEval &e, const Obstacles &o, const float *in_dev, size_t n,
+                          const wn_advect *adv, float *out_dev, float *traj_dev, hipStream_t stream)
+{
+    const int rc = wn::check_advect(adv);
+    if (rc || n == 0) return rc;
+    if (!in_dev || !out_dev) return wn::fail(WN_ERR_INVALID, "xyz_in_dev / xyz_out_dev is NULL");
+    const int every = adv->traj_every;
+    if (every && !traj_dev) return wn::fail(WN_ERR_INVALID, "traj_dev is NULL with traj_every = %d", every);
+    const uintptr_t in_b = reinterpret_cast<uintptr_t>(in_dev), out_b = reinterpret_cast<uintptr_t>(out_dev);
+    const size_t bytes = 3 * n * sizeof(float);
+    if (in_b != out_b && in_b < out_b + bytes && out_b < in_b + bytes)
+        return wn::fail(WN_ERR_INVALID, "xyz_out_dev overlaps xyz_in_dev without being equal to it");
+
+    BoundedAdvectArgs a{};
+    a.e = e;
+    a.o = o;
+    a.out = out_dev;
+    a.count = n;
+    a.every = every;
+    a.h = adv->h;
+    a.h2 = 0.5f * adv->h;
+    a.h6 = adv->h / 6.0f;
+    a.gain = adv->gain;
+    std::copy(adv->drift, adv->drift + 3, a.drift);
+    const dim3 grid(wn::stride_blocks(n, kBoundedBlockCap));
+    const bool padded = tile->dev_padded != nullptr;
+    const int launch_steps = wn_advect_launch_steps();
+    int done = 0;
+    do { // steps == 0: one launch, which copies the input
+        a.in = done ? out_dev : in_dev;
+        a.nsteps = std::min(launch_steps, adv->steps - done);
+        a.snap_input = every && done == 0;
+        a.until = every ? every - done % every : 0;
+        // snapshot done / every is written (the input, or by the launch before this one); the next one is this launch's
+        a.snap = every ? traj_dev + (size_t)(done / every + (done ? 1 : 0)) * 3 * n : nullptr;
+        if (e.mb) {
+            if (padded) launch_method<true, true>(adv->method, grid, stream, a);
+            else launch_method<false, true>(adv->method, grid, stream, a);
+        } else {
+            if (padded) launch_method<true, false>(adv->method, grid, stream, a);
+            else launch_method<false, false>(adv->method, grid, stream, a);
+        }
+        WN_LAUNCH_CHECK("curl3d_bounded_advect_kernel");
+        done += a.nsteps;
+    } while (done < adv->steps);
+    return WN_OK;
+}
+
+} // namespace
+
+using namespace wn;
+
+extern "C" {
+
+int wn_eval3d_curl_bounded_points(const wn_tile *tile, const float *xyz_dev, size_t n, const int32_t *offsets9_host,
+                                  const wn_obstacle *obstacles_host, int nobs, float *out3_dev, void *stream)
+{
+    WN_ENTRY();
+    CurlEval e;
+    Obstacles o;
+    int rc = curl_eval_args(tile, offsets9_host, "wn_eval3d_curl_bounded_points", &e);
+    if (rc) return rc;
+    rc = obstacle_args(obstacles_host, nobs, "wn_eval3d_curl_bounded_points", &o);
+    if (rc || n == 0) return rc;
+    return launch_bounded_points(tile, e, o, xyz_dev, n, out3_dev, as_stream(stream));
+}
+
+int wn_multiband3d_curl_bounded_points(const wn_tile *tile, const float *xyz_dev, size_t n, const int32_t *offsets9_host,
+                                       float s, int first_band, int nbands, const float *w_host, float var_per_band,
+                                       const wn_obstacle *obstacles_host, int nobs, float *out3_dev, void *stream)
+{
+    WN_ENTRY();
+    CurlEval e;
+    Obstacles o;
+    int rc = curl_eval_args(tile, offsets9_host, "wn_multiband3d_curl_bounded_points", &e);
+    if (rc) return rc;
+    rc = multiband_bands(s, first_band, nbands, w_host, var_per_band, &e);
+    if (rc) return rc;
+    rc = obstacle_args(obstacles_host, nobs, "wn_multiband3d_curl_bounded_points", &o);
+    if (rc || n == 0) return rc;
+    e.mb = 1;
+    return launch_bounded_points(tile, e, o, xyz_dev, n, out3_dev, as_stream(stream));
+}
+
+int wn_eval3d_curl_bounded_advect_points(const wn_tile *tile, const float *xyz_in_dev, size_t n, const int32_t *offsets9_host,
+                                         const wn_obstacle *obstacles_host, int nobs, const wn_advect *a, float *xyz_out_dev,
+                                         float *traj_dev, void *stream)
+{
+    WN_ENTRY();
+    CurlEval e;
+    Obstacles o;
+    int rc = curl_eval_args(tile, offsets9_host, "wn_eval3d_curl_bounded_advect_points", &e);
+    if (rc) return rc;
+    rc = obstacle_args(obstacles_host, nobs, "wn_eval3d_curl_bounded_advect_points", &o);
+    if (rc) return rc;
+    return bounded_advect_points(tile, e, o, xyz_in_dev, n, a, xyz_out_dev, traj_dev, as_stream(stream));
+}
+
+int wn_multiband3d_curl_bounded_advect_points(const wn_tile *tile, const float *xyz_in_dev, size_t n,
+                                              const int32_t *offsets9_host, float s, int first_band, int nbands,
+                                              const float *w_host, float var_per_band, const wn_obstacle *obstacles_host,
+                                              int nobs, const wn_advect *a, float *xyz_out_dev, float *traj_dev, void *stream)
+{
+    WN_ENTRY();
+    CurlEval e;
+    Obstacles o;
+    int rc = curl_eval_args(tile, offsets9_host, "wn_multiband3d_curl_bounded_advect_points", &e);
+    if (rc) return rc;
+    rc = multiband_bands(s, first_band, nbands, w_host, var_per_band, &e);
+    if (rc) return rc;
+    rc = obstacle_args(obstacles_host, nobs, "wn_multiband3d_curl_bounded_advect_points", &o);
+    if (rc) return rc;
+    e.mb = 1;
+    return bounded_advect_points(tile, e, o, xyz_in_dev, n, a, xyz_out_dev, traj_dev, as_stream(stream));
+}
+
+} // extern "C"

@@ -9,6 +9,7 @@
 #include "scalar_eval.h"
 #include "wn_host.hpp"
 #include "wnoise_advect.h"
+#include "wnoise_bounded.h"
 #include "wnoise_curl2d.h"
 #include "wnoise_footprint.h"
 #include "wnoise_multiband2d.h"
@@ -477,6 +478,96 @@ void WaveletNoise::WMultibandNoiseAdvectCurl(const float *xyz, size_t n, const w
         return wn_multiband3d_curl_advect_points(tile(3), pos, n, offsets9 ? offsets9 : def, sarg, firstBand, nbands, w,
                                                  variance, &a, pos, path, nullptr);
     }, "wn_multiband3d_curl_advect_points");
+}
+
+// ---- the curl field with solid boundaries (include/wnoise_bounded.h): as the eight members above, the obstacle list beside
+// the offsets
+void WaveletNoise::evaluate3DCurlBounded(const float p[3], const int *offsets9, const wn_obstacle *obs, int nobs,
+                                         float v[3]) const
+{
+    if (tileDims == 2) return evaluate3DCurlBounded(p, 1, offsets9, obs, nobs, v);
+    int def[9];
+    if (!offsets9) defaultCurlOffsets(def);
+    if (wnhost_eval3d_curl_bounded(noiseCoefficients.empty() ? nullptr : noiseCoefficients.data(), tileSizeN, p,
+                                   offsets9 ? offsets9 : def, obs, nobs, v))
+        throw std::runtime_error("evaluate3DCurlBounded: an obstacle list that wn_eval3d_curl_bounded_points refuses");
+}
+
+void WaveletNoise::evaluate3DCurlBounded(const float *xyz, size_t n, const int *offsets9, const wn_obstacle *obs, int nobs,
+                                         float *out3) const
+{
+    if (!n) return;
+    int def[9];
+    if (!offsets9) defaultCurlOffsets(def);
+    wnhost::DeviceBuffer in(3 * n * sizeof(float)), res(3 * n * sizeof(float));
+    in.upload(xyz);
+    check(wn_eval3d_curl_bounded_points(tile(3), in.as<float>(), n, offsets9 ? offsets9 : def, obs, nobs, res.as<float>(),
+                                        nullptr), "wn_eval3d_curl_bounded_points");
+    res.download(out3);
+}
+
+void WaveletNoise::WMultibandNoiseCurlBounded(const float p[3], const int *offsets9, const wn_obstacle *obs, int nobs,
+                                              float sarg, int firstBand, int nbands, const float *w, float v[3],
+                                              float variance) const
+{
+    WMultibandNoiseCurlBounded(p, 1, offsets9, obs, nobs, sarg, firstBand, nbands, w, variance, v);
+}
+
+void WaveletNoise::WMultibandNoiseCurlBounded(const float *xyz, size_t n, const int *offsets9, const wn_obstacle *obs, int nobs,
+                                              float sarg, int firstBand, int nbands, const float *w, float variance,
+                                              float *out3) const
+{
+    if (!n) return;
+    int def[9];
+    if (!offsets9) defaultCurlOffsets(def);
+    wnhost::DeviceBuffer in(3 * n * sizeof(float)), res(3 * n * sizeof(float));
+    in.upload(xyz);
+    check(wn_multiband3d_curl_bounded_points(tile(3), in.as<float>(), n, offsets9 ? offsets9 : def, sarg, firstBand, nbands, w,
+                                             variance, obs, nobs, res.as<float>(), nullptr),
+          "wn_multiband3d_curl_bounded_points");
+    res.download(out3);
+}
+
+void WaveletNoise::advectCurlBounded(const float p[3], const wn_advect &a, const int *offsets9, const wn_obstacle *obs,
+                                     int nobs, float p_out[3], float *traj) const
+{
+    if (tileDims == 2) return advectCurlBounded(p, 1, a, offsets9, obs, nobs, p_out, traj);
+    int def[9];
+    if (!offsets9) defaultCurlOffsets(def);
+    if (wnhost_eval3d_curl_bounded_advect(noiseCoefficients.empty() ? nullptr : noiseCoefficients.data(), tileSizeN, p,
+                                          offsets9 ? offsets9 : def, obs, nobs, &a, p_out, traj))
+        throw std::runtime_error("advectCurlBounded: an obstacle list or a wn_advect that "
+                                 "wn_eval3d_curl_bounded_advect_points refuses, or a trajectory without a buffer");
+}
+
+void WaveletNoise::advectCurlBounded(const float *xyz, size_t n, const wn_advect &a, const int *offsets9,
+                                     const wn_obstacle *obs, int nobs, float *xyz_out, float *traj) const
+{
+    int def[9];
+    if (!offsets9) defaultCurlOffsets(def);
+    advect_batch(xyz, n, a, xyz_out, traj, [&](float *pos, float *path) {
+        return wn_eval3d_curl_bounded_advect_points(tile(3), pos, n, offsets9 ? offsets9 : def, obs, nobs, &a, pos, path,
+                                                    nullptr);
+    }, "wn_eval3d_curl_bounded_advect_points");
+}
+
+void WaveletNoise::WMultibandNoiseAdvectCurlBounded(const float p[3], const wn_advect &a, const int *offsets9,
+                                                    const wn_obstacle *obs, int nobs, float sarg, int firstBand, int nbands,
+                                                    const float *w, float p_out[3], float *traj, float variance) const
+{
+    WMultibandNoiseAdvectCurlBounded(p, 1, a, offsets9, obs, nobs, sarg, firstBand, nbands, w, variance, p_out, traj);
+}
+
+void WaveletNoise::WMultibandNoiseAdvectCurlBounded(const float *xyz, size_t n, const wn_advect &a, const int *offsets9,
+                                                    const wn_obstacle *obs, int nobs, float sarg, int firstBand, int nbands,
+                                                    const float *w, float variance, float *xyz_out, float *traj) const
+{
+    int def[9];
+    if (!offsets9) defaultCurlOffsets(def);
+    advect_batch(xyz, n, a, xyz_out, traj, [&](float *pos, float *path) {
+        return wn_multiband3d_curl_bounded_advect_points(tile(3), pos, n, offsets9 ? offsets9 : def, sarg, firstBand, nbands,
+                                                         w, variance, obs, nobs, &a, pos, path, nullptr);
+    }, "wn_multiband3d_curl_bounded_advect_points");
 }
 
 // ---- curl noise on the 2-D tile and particles through it (include/wnoise_curl2d.h): the one-sample members on the host

@@ -23,6 +23,7 @@
 struct wn_tile;   // include/wnoise.h
 struct wn_advect; // include/wnoise_advect.h
 struct wn_advect2d; // include/wnoise_curl2d.h
+struct wn_obstacle; // include/wnoise_bounded.h
 
 // Statistical analysis structure (WaveletNoise.h:11-18)
 struct DataStats {
@@ -167,6 +168,28 @@ class WaveletNoise {
     void WMultibandNoiseAdvectCurl(const float *xyz, size_t n, const wn_advect &a, const int *offsets9, float s,
                                    int firstBand, int nbands, const float *w, float variance, float *xyz_out,
                                    float *traj = nullptr) const;
+    // The four members above with solid boundaries (absent from the reference; include/wnoise_bounded.h, whose wn_obstacle
+    // the list `obs` of nobs <= WN_MAX_OBSTACLES entries holds): v = A curl Psi + grad A x Psi, zero inside an obstacle and
+    // the unbounded bits far from all of them.  The one-point evaluate3DCurlBounded and advectCurlBounded run on the host
+    // (scalar_eval.h), bit-identical to wn_eval3d_curl_bounded_points / _advect_points, which the batched forms call; the
+    // multiband one-point forms are batches of one.  A list the C ABI refuses makes every member throw.
+    void evaluate3DCurlBounded(const float p[3], const int *offsets9, const wn_obstacle *obs, int nobs, float v[3]) const;
+    void evaluate3DCurlBounded(const float *xyz, size_t n, const int *offsets9, const wn_obstacle *obs, int nobs,
+                               float *out3) const;
+    void WMultibandNoiseCurlBounded(const float p[3], const int *offsets9, const wn_obstacle *obs, int nobs, float s,
+                                    int firstBand, int nbands, const float *w, float v[3], float variance = 0.18402f) const;
+    void WMultibandNoiseCurlBounded(const float *xyz, size_t n, const int *offsets9, const wn_obstacle *obs, int nobs, float s,
+                                    int firstBand, int nbands, const float *w, float variance, float *out3) const;
+    void advectCurlBounded(const float p[3], const wn_advect &a, const int *offsets9, const wn_obstacle *obs, int nobs,
+                           float p_out[3], float *traj = nullptr) const;
+    void advectCurlBounded(const float *xyz, size_t n, const wn_advect &a, const int *offsets9, const wn_obstacle *obs,
+                           int nobs, float *xyz_out, float *traj = nullptr) const;
+    void WMultibandNoiseAdvectCurlBounded(const float p[3], const wn_advect &a, const int *offsets9, const wn_obstacle *obs,
+                                          int nobs, float s, int firstBand, int nbands, const float *w, float p_out[3],
+                                          float *traj = nullptr, float variance = 0.18402f) const;
+    void WMultibandNoiseAdvectCurlBounded(const float *xyz, size_t n, const wn_advect &a, const int *offsets9,
+                                          const wn_obstacle *obs, int nobs, float s, int firstBand, int nbands,
+                                          const float *w, float variance, float *xyz_out, float *traj = nullptr) const;
     // (0,0,0), (n/3,)*3, (2n/3,)*3 with integer division: a default only, not a measured decorrelation.
     void defaultCurlOffsets(int offsets9[9]) const;
     // The device-resident tile (an empty tile before generate*); for the C-ABI grid entry points.

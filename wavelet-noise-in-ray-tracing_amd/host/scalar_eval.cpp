@@ -9,6 +9,7 @@
 
 #include "wn_eval.hpp"
 #include "wnoise_advect.h"
+#include "wnoise_bounded.h"
 #include "wnoise_curl2d.h"
 #include "wnoise_perlin_curl.h"
 
@@ -83,6 +84,25 @@ void wnhost_eval3d_curl(const float *coef, int n, const float p[3], const int of
 int wnhost_eval3d_curl_advect(const float *coef, int n, const float p_in[3], const int offsets9[9], const wn_advect *a,
                               float p_out[3], float *traj)
 {
+    return wnhost_eval3d_curl_bounded_advect(coef, n, p_in, offsets9, nullptr, 0, a, p_out, traj); // no obstacle: the same bits
+}
+
+int wnhost_eval3d_curl_bounded(const float *coef, int n, const float p[3], const int offsets9[9], const wn_obstacle *obstacles,
+                               int nobs, float v[3])
+{
+    if (wn::obstacle_fault(obstacles, nobs)) return 1;
+    if (!coef || n <= 0) n = 0;
+    const int nmask = wn::pow2_mask(n);
+    int off[9];
+    for (int i = 0; i < 9; ++i) off[i] = n ? wn::dmod(offsets9[i], n, nmask) : 0;
+    wn::eval3d_curl_bounded_exact(coef, n, nmask, off, obstacles, nobs, p, v);
+    return 0;
+}
+
+int wnhost_eval3d_curl_bounded_advect(const float *coef, int n, const float p_in[3], const int offsets9[9],
+                                      const wn_obstacle *obstacles, int nobs, const wn_advect *a, float p_out[3], float *traj)
+{
+    if (wn::obstacle_fault(obstacles, nobs)) return 1;
     if (!a || a->method < WN_ADVECT_EULER || a->method > WN_ADVECT_RK4 || a->steps < 0 || a->traj_every < 0) return 1;
     if (!std::isfinite(a->h) || !std::isfinite(a->gain) || !std::isfinite(a->drift[0]) || !std::isfinite(a->drift[1]) ||
         !std::isfinite(a->drift[2]) || (a->traj_every && !traj))
@@ -91,7 +111,9 @@ int wnhost_eval3d_curl_advect(const float *coef, int n, const float p_in[3], con
     const int nmask = wn::pow2_mask(n);
     int off[9];
     for (int i = 0; i < 9; ++i) off[i] = n ? wn::dmod(offsets9[i], n, nmask) : 0;
-    const auto velocity = [&](const float q[3], float v[3]) { wn::eval3d_curl_exact(coef, n, nmask, off, q[0], q[1], q[2], v); };
+    const auto velocity = [&](const float q[3], float v[3]) {
+        wn::eval3d_curl_bounded_exact(coef, n, nmask, off, obstacles, nobs, q, v);
+    };
     const float h = a->h, h2 = 0.5f * a->h, h6 = a->h / 6.0f;
     float p[3] = {p_in[0], p_in[1], p_in[2]};
     if (a->traj_every) traj[0] = p[0], traj[1] = p[1], traj[2] = p[2];

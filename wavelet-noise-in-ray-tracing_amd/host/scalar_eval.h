@@ -52,6 +52,18 @@ WNHOST_API void wnhost_eval3d_curl(const float *coef, int n, const float p[3], c
 struct wn_advect;
 WNHOST_API int wnhost_eval3d_curl_advect(const float *coef, int n, const float p_in[3], const int offsets9[9],
                                          const struct wn_advect *a, float p_out[3], float *traj);
+// That curl with solid boundaries (include/wnoise_bounded.h, whose wn_obstacle the list holds; absent from the reference):
+// v = A curl Psi + grad A x Psi with the ramp product A of the obstacles near p -- wn::eval3d_curl_bounded_exact, the
+// evaluator the device kernels run: the bits of wn_eval3d_curl_bounded_points.  nobs == 0 and a point far from every
+// obstacle: the bits of wnhost_eval3d_curl; a point inside one: 0.  n == 0 or coef == NULL: 0 in all three.  Returns 0, or 1
+// and writes nothing when the list is one that entry point refuses.  The advect form traces one particle through it as
+// wnhost_eval3d_curl_advect does through the unbounded field: the bits of wn_eval3d_curl_bounded_advect_points.
+struct wn_obstacle;
+WNHOST_API int wnhost_eval3d_curl_bounded(const float *coef, int n, const float p[3], const int offsets9[9],
+                                          const struct wn_obstacle *obstacles, int nobs, float v[3]);
+WNHOST_API int wnhost_eval3d_curl_bounded_advect(const float *coef, int n, const float p_in[3], const int offsets9[9],
+                                                 const struct wn_obstacle *obstacles, int nobs, const struct wn_advect *a,
+                                                 float p_out[3], float *traj);
 WNHOST_API float wnhost_eval3d_projected(const float *coef, int n, const float p[3], const float normal[3]); // WaveletNoise.cpp:218-265
 // evaluate3DProjected and its gradient with respect to p, the normal held fixed (absent from the reference): returns the
 // value (the bits of wnhost_eval3d_projected, its 1e-6 cut included), writes the gradient of the uncut sum over the same

@@ -352,6 +352,75 @@ class WaveletNoise:
             self._handle(3), p, n, off, float(s), int(firstBand), int(nbands), wa, var, a, out, traj, _stream()),
             pts, h, steps, method, gain, drift, trajectory_every)
 
+    # -- that curl field with solid boundaries (include/wnoise_bounded.h; absent from the reference)
+    _OBSTACLE_KINDS = {"sphere": _capi.WN_OBSTACLE_SPHERE, "container": _capi.WN_OBSTACLE_CONTAINER,
+                       "halfspace": _capi.WN_OBSTACLE_HALFSPACE}
+
+    @classmethod
+    def _obstacles(cls, obstacles):
+        """The wn_obstacle array of a list of ("sphere", c, r, d0), ("container", c, r, d0) and ("halfspace", n, o, d0)
+        entries, and its length; the library checks the values."""
+        obstacles = list(obstacles)
+        arr = (_capi.wn_obstacle * max(1, len(obstacles)))()
+        for dst, entry in zip(arr, obstacles):
+            kind, c, r, d0 = entry
+            if kind not in cls._OBSTACLE_KINDS:
+                raise ValueError(f"obstacle kind: one of {sorted(cls._OBSTACLE_KINDS)}")
+            c = [float(x) for x in c]
+            if len(c) != 3:
+                raise ValueError("an obstacle's centre or normal has three components")
+            dst.kind, dst.c, dst.r, dst.d0 = cls._OBSTACLE_KINDS[kind], (C.c_float * 3)(*c), float(r), float(d0)
+        return arr, len(obstacles)
+
+    def evaluate3DCurlBounded(self, p, obstacles, offsets=None):
+        """evaluate3DCurl with its potential faded to zero towards every solid of `obstacles`
+        (wn_eval3d_curl_bounded_points): v = A curl Psi + grad A x Psi, still divergence-free, with no normal component on
+        a solid's surface.  `obstacles`: a list of at most 16 ("sphere", c, r, d0), ("container", c, r, d0) or
+        ("halfspace", n, o, d0), in the coordinates of p; d0 is the width of the ramp.  A point inside a solid gets 0, a
+        point at distance >= d0 from all of them (and obstacles=[]) the bits of evaluate3DCurl."""
+        pts = _dev(p, torch.float32).reshape(-1, 3)
+        out = torch.empty((pts.shape[0], 3), dtype=torch.float32, device="cuda")
+        obs, nobs = self._obstacles(obstacles)
+        check(_lib.wn_eval3d_curl_bounded_points(self._handle(3), _ptr(pts), pts.shape[0], self._curl_offsets(offsets), obs,
+                                                 nobs, _ptr(out), _stream()))
+        return out
+
+    def WMultibandNoiseCurlBounded(self, p, obstacles, s, firstBand, nbands, w, variance=None, offsets=None):
+        """evaluate3DCurlBounded with WMultibandNoise (normal=None) potentials (wn_multiband3d_curl_bounded_points); the
+        obstacles live in the coordinates of p."""
+        pts = _dev(p, torch.float32).reshape(-1, 3)
+        out = torch.empty((pts.shape[0], 3), dtype=torch.float32, device="cuda")
+        wa = (C.c_float * max(1, nbands))(*[float(x) for x in list(w)[:nbands]])
+        obs, nobs = self._obstacles(obstacles)
+        check(_lib.wn_multiband3d_curl_bounded_points(self._handle(3), _ptr(pts), pts.shape[0], self._curl_offsets(offsets),
+                                                      float(s), int(firstBand), int(nbands), wa,
+                                                      float(0.18402 if variance is None else variance), obs, nobs,
+                                                      _ptr(out), _stream()))
+        return out
+
+    def advectCurlBounded(self, pts, h, steps, obstacles, method="rk4", offsets=None, gain=1.0, drift=None,
+                          trajectory_every=0):
+        """advectCurl through gain * evaluate3DCurlBounded(., obstacles, offsets) + drift, all steps inside the kernel
+        (wn_eval3d_curl_bounded_advect_points): particles flow around the solids.  A particle inside one moves by drift
+        alone."""
+        off = self._curl_offsets(offsets)
+        obs, nobs = self._obstacles(obstacles)
+        return self._advect(lambda p, n, a, out, traj: _lib.wn_eval3d_curl_bounded_advect_points(
+            self._handle(3), p, n, off, obs, nobs, a, out, traj, _stream()), pts, h, steps, method, gain, drift,
+            trajectory_every)
+
+    def WMultibandNoiseAdvectCurlBounded(self, pts, h, steps, obstacles, s, firstBand, nbands, w, variance=None, method="rk4",
+                                         offsets=None, gain=1.0, drift=None, trajectory_every=0):
+        """advectCurlBounded through gain * WMultibandNoiseCurlBounded(., obstacles, s, firstBand, nbands, w, variance,
+        offsets) + drift (wn_multiband3d_curl_bounded_advect_points)."""
+        off = self._curl_offsets(offsets)
+        obs, nobs = self._obstacles(obstacles)
+        wa = (C.c_float * max(1, nbands))(*[float(x) for x in list(w)[:nbands]])
+        var = float(0.18402 if variance is None else variance)
+        return self._advect(lambda p, n, a, out, traj: _lib.wn_multiband3d_curl_bounded_advect_points(
+            self._handle(3), p, n, off, float(s), int(firstBand), int(nbands), wa, var, obs, nobs, a, out, traj, _stream()),
+            pts, h, steps, method, gain, drift, trajectory_every)
+
     def evaluate2DGradient(self, p):
         """evaluate2D and its gradient at one point or an (N, 2) batch (wn_eval2d_grad_points): an (N, 3) CUDA tensor of
         {value, d/dx, d/dy}; the value column has the bits of evaluate2D."""
