@@ -40,7 +40,8 @@
  * A result has the bits of the host's wnhost_eval3d_curl_bounded / wnhost_eval3d_curl_bounded_advect.
  *
  * Not provided: Bridson's variant that keeps the normal component of Psi; obstacles other than these three kinds; moving
- * obstacles and potentials that change with time; dense grids; the Perlin and 2-D fields.
+ * obstacles and potentials that change with time; dense grids; the Perlin field (of the Perlin and 2-D fields, the 2-D one
+ * has its boundaries in wnoise_bounded2d.h).
  */
 #ifndef WNOISE_BOUNDED_H
 #define WNOISE_BOUNDED_H

@@ -22,6 +22,7 @@ from .noise import (  # noqa: E402
     WaveletNoise, perlin, PerlinNoise, noise_texture, wavelet_texture, wavelet_multiband_texture,
     noise_multiband_texture, GridSpec,
     generate2DOctaveBandNoise, generate2DMultibandNoise, generate2DMultibandNoiseGradient, generate2DMultibandNoiseCurl,
+    generate2DMultibandNoiseCurlBounded,
     generate3DSlicedOctaveBandNoise,
     generate3DProjectedOctaveBandNoise, generatePerlinNoise2D, generatePerlinNoise3DSliced,
     wavelet_volume, wavelet_volume_launcher, multiband_volume, perlin_volume, turb_volume, device_info, HipTimer,
@@ -38,6 +39,7 @@ __all__ = [
     "noise_multiband_texture", "GridSpec",
     "generate2DOctaveBandNoise", "generate2DMultibandNoise", "generate2DMultibandNoiseGradient",
     "generate2DMultibandNoiseCurl",
+    "generate2DMultibandNoiseCurlBounded",
     "generate3DSlicedOctaveBandNoise",
     "generate3DProjectedOctaveBandNoise", "generatePerlinNoise2D", "generatePerlinNoise3DSliced",
     "wavelet_volume", "wavelet_volume_launcher", "multiband_volume", "perlin_volume", "turb_volume", "device_info",

@@ -1,6 +1,6 @@
 """ctypes binding of libwnoise_hip.so (include/wnoise.h, include/wnoise_perlin_curl.h, include/wnoise_footprint.h,
 include/wnoise_perlin_footprint.h, include/wnoise_multiband2d.h, include/wnoise_advect.h, include/wnoise_bounded.h,
-include/wnoise_perlin_advect.h, include/wnoise_curl2d.h).
+include/wnoise_perlin_advect.h, include/wnoise_curl2d.h, include/wnoise_bounded2d.h).
 
 The library is the product: if it is missing or fails to load this module raises, it never
 substitutes a CPU implementation.
@@ -216,6 +216,22 @@ CURL2D_SIGNATURES = {
     "wn_advect2d_launch_steps": (_i, [_i, _i]),
 }
 
+# name -> (restype, argtypes); every symbol include/wnoise_bounded2d.h declares, and its wn_obstacle2d.
+class wn_obstacle2d(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("c", C.c_float * 2), ("r", C.c_float), ("d0", C.c_float),
+                ("reserved", C.c_int32 * 3)]
+
+
+_o2p = C.POINTER(wn_obstacle2d)
+BOUNDED2D_SIGNATURES = {
+    # tile, xy, n, s, first_band, nbands, w, var, obstacles, nobs, flow2, out2, stream
+    "wn_multiband2d_curl_bounded_points": (_i, [_vp, _vp, _sz, _f, _i, _i, _fp, _f, _o2p, _i, _fp, _vp, _vp]),
+    # tile, grid, s, first_band, nbands, w, var, obstacles, nobs, flow2, out, stream
+    "wn_multiband2d_curl_bounded_grid": (_i, [_vp, _gp, _f, _i, _i, _fp, _f, _o2p, _i, _fp, _vp, _vp]),
+    # tile, xy_in, n, s, first_band, nbands, w, var, obstacles, nobs, flow2, a, xy_out, traj, stream
+    "wn_multiband2d_curl_bounded_advect_points": (_i, [_vp, _vp, _sz, _f, _i, _i, _fp, _f, _o2p, _i, _fp, _a2p, _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -232,7 +248,7 @@ def load():
     for name, (res, args) in (*SIGNATURES.items(), *PERLIN_CURL_SIGNATURES.items(), *FOOTPRINT_SIGNATURES.items(),
                               *PERLIN_FOOTPRINT_SIGNATURES.items(), *MULTIBAND2D_SIGNATURES.items(),
                               *ADVECT_SIGNATURES.items(), *BOUNDED_SIGNATURES.items(), *PERLIN_ADVECT_SIGNATURES.items(),
-                              *CURL2D_SIGNATURES.items()):
+                              *CURL2D_SIGNATURES.items(), *BOUNDED2D_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

@@ -617,27 +617,33 @@ WN_EVAL_FN void multiband_curl_exact(const A &a, const float p[3], float v[3])
 // Bridson, Houriham and Nordenstam 2007: the potential is faded to zero towards a solid by a smooth ramp A of the distance
 // to it, and the velocity is the curl of the faded potential, v = curl(A Psi) = A curl Psi + grad A x Psi: still
 // divergence-free, and on a solid A -> 0 and grad A is parallel to the normal, so the normal component of v vanishes.
-// O is wn_obstacle (kind, c[3], r, d0); this header does not include it.  Everything below is float32 and unfused.
+// O is wn_obstacle (kind, c[3], r, d0), or wn_obstacle2d (c[2]) for the 2-D field further down; this header includes neither.
+// Everything below is float32 and unfused.
 constexpr int kMaxObstacles = 16; // WN_MAX_OBSTACLES
 constexpr int kObstacleSphere = 0, kObstacleContainer = 1, kObstacleHalfspace = 2;
 
-// What is wrong with an obstacle list (the checks of include/wnoise_bounded.h), or nullptr.
-template <typename O>
+// What is wrong with an obstacle list (the checks of include/wnoise_bounded.h and wnoise_bounded2d.h), or nullptr.  D: the
+// dimension, 3 (wn_obstacle) or 2 (wn_obstacle2d: c has two components, and a sphere is a disc, a half-space a half-plane).
+template <int D = 3, typename O>
 inline const char *obstacle_fault(const O *obs, int nobs)
 {
+    static_assert(D == 2 || D == 3, "a plane or a volume");
     if (nobs < 0 || nobs > kMaxObstacles) return "nobs must be in 0..16";
     if (nobs && !obs) return "obstacles_host is NULL";
     for (int j = 0; j < nobs; ++j) {
         const O &o = obs[j];
         if (o.kind < kObstacleSphere || o.kind > kObstacleHalfspace) return "an obstacle's kind must be 0, 1 or 2";
-        if (!std::isfinite(o.c[0]) || !std::isfinite(o.c[1]) || !std::isfinite(o.c[2]) || !std::isfinite(o.r) ||
-            !std::isfinite(o.d0))
-            return "an obstacle's c, r and d0 must be finite";
+        bool finite = std::isfinite(o.r) && std::isfinite(o.d0), zero = true;
+        for (int c = 0; c < D; ++c) {
+            finite = finite && std::isfinite(o.c[c]);
+            zero = zero && o.c[c] == 0.0f;
+        }
+        if (!finite) return "an obstacle's c, r and d0 must be finite";
         if (!(o.d0 > 0.0f)) return "an obstacle's d0 must be > 0";
         if (o.kind != kObstacleHalfspace && !(o.r > 0.0f)) return "a sphere's or container's r must be > 0";
-        if (o.kind == kObstacleHalfspace && o.c[0] == 0.0f && o.c[1] == 0.0f && o.c[2] == 0.0f)
-            return "a half-space's normal must not be zero";
-        if (o.reserved[0] != 0 || o.reserved[1] != 0) return "an obstacle's reserved fields must be 0";
+        if (o.kind == kObstacleHalfspace && zero) return "a half-space's normal must not be zero";
+        for (const int r : o.reserved)
+            if (r != 0) return "an obstacle's reserved fields must be 0";
     }
     return nullptr;
 }
@@ -646,19 +652,26 @@ inline const char *obstacle_fault(const O *obs, int nobs)
 //     sphere, container  dx = x - c, l = sqrtf((dx0*dx0 + dx1*dx1) + dx2*dx2), m = dx / l (0 when l == 0);
 //                        sphere: d = l - r, nrm = m; container: d = r - l, nrm = -m
 //     half-space         d = ((n0*x0 + n1*x1) + n2*x2) - o, nrm = n as given (not normalised: d is linear with gradient n)
-template <typename O>
-WN_EVAL_FN float obstacle_distance(const O &o, const float x[3], float nrm[3])
+// D == 2: the same with the third component dropped, l = sqrtf(dx0*dx0 + dx1*dx1) and d = (n0*x0 + n1*x1) - o.
+template <int D = 3, typename O>
+WN_EVAL_FN float obstacle_distance(const O &o, const float x[D], float nrm[D])
 {
     if (o.kind == kObstacleHalfspace) {
         WN_UNROLL
-        for (int c = 0; c < 3; ++c) nrm[c] = o.c[c];
-        return ((o.c[0] * x[0] + o.c[1] * x[1]) + o.c[2] * x[2]) - o.r;
+        for (int c = 0; c < D; ++c) nrm[c] = o.c[c];
+        float dot = o.c[0] * x[0] + o.c[1] * x[1];
+        if constexpr (D == 3) dot = dot + o.c[2] * x[2];
+        return dot - o.r;
     }
-    const float dx[3] = {x[0] - o.c[0], x[1] - o.c[1], x[2] - o.c[2]};
-    const float l = sqrtf((dx[0] * dx[0] + dx[1] * dx[1]) + dx[2] * dx[2]);
+    float dx[D];
+    WN_UNROLL
+    for (int c = 0; c < D; ++c) dx[c] = x[c] - o.c[c];
+    float l2 = dx[0] * dx[0] + dx[1] * dx[1];
+    if constexpr (D == 3) l2 = l2 + dx[2] * dx[2];
+    const float l = sqrtf(l2);
     const bool solid = o.kind == kObstacleSphere;
     WN_UNROLL
-    for (int c = 0; c < 3; ++c) {
+    for (int c = 0; c < D; ++c) {
         const float m = l == 0.0f ? 0.0f : dx[c] / l;
         nrm[c] = solid ? m : -m;
     }
@@ -673,15 +686,16 @@ WN_EVAL_FN float obstacle_distance(const O &o, const float x[3], float nrm[3])
 //             dalpha = (1.875f * (q * q)) / d0, q = 1.0f - r2; per component G = G * alpha + (A * dalpha) * nrm, then
 //             A = A * alpha.  Overlapping ramps multiply: A stays C1 across every d = d0.
 constexpr int kBoundFar = 0, kBoundNear = 1, kBoundInside = 2;
-template <typename O>
-WN_EVAL_FN int obstacle_ramp(const O *obs, int nobs, const float x[3], float &A, float G[3])
+template <int D = 3, typename O>
+WN_EVAL_FN int obstacle_ramp(const O *obs, int nobs, const float x[D], float &A, float G[D])
 {
     A = 1.0f;
-    G[0] = G[1] = G[2] = 0.0f;
+    WN_UNROLL
+    for (int c = 0; c < D; ++c) G[c] = 0.0f;
     int where = kBoundFar;
     for (int j = 0; j < nobs; ++j) {
-        float nrm[3];
-        const float d = obstacle_distance(obs[j], x, nrm);
+        float nrm[D];
+        const float d = obstacle_distance<D>(obs[j], x, nrm);
         const float d0 = obs[j].d0;
         if (d <= 0.0f) return kBoundInside;
         if (d >= d0) continue;
@@ -693,7 +707,7 @@ WN_EVAL_FN int obstacle_ramp(const O *obs, int nobs, const float x[3], float &A,
         const float dalpha = (1.875f * (q * q)) / d0;
         const float ad = A * dalpha;
         WN_UNROLL
-        for (int c = 0; c < 3; ++c) G[c] = G[c] * alpha + ad * nrm[c];
+        for (int c = 0; c < D; ++c) G[c] = G[c] * alpha + ad * nrm[c];
         A = A * alpha;
     }
     return where;
@@ -817,6 +831,64 @@ WN_EVAL_FN void multiband_curl_bounded_exact(const E &a, const O *obs, int nobs,
     bounded_velocity(
         where, A, G, v, [&](float *c) { multiband_curl_exact<PADDED>(a, p, c); },
         [&](float *psi) { multiband_potential_values<PADDED>(a, p, psi); });
+}
+
+// ---- solid boundaries and a background stream for the 2-D curl field (include/wnoise_bounded2d.h; absent from the reference) --
+// In two dimensions the faded potential is a scalar: v = (d(A psi_t)/dy, -d(A psi_t)/dx) with psi_t the stream function of
+// multiband2d_curl_exact plus, when flow != nullptr, the uniform stream psi_bg = ux * py - uy * px (Bridson's remedy: inside
+// the potential the ramp bends the stream around a solid with the noise).  `where`, A, G: obstacle_ramp<2> at p.
+//     psi, gx, gy   the three channels of multiband2d_footprint_exact<GRAD = true> at s with fade 0
+//     flow          psi_t = psi + (ux * py - uy * px),  gx_t = gx - uy,  gy_t = gy + ux   (flow == nullptr: skipped)
+//     inside        v = (0, 0), nothing is evaluated
+//     far           v = (gy_t, -gx_t)
+//     near          v0 = A * gy_t + G1 * psi_t,  v1 = -(A * gx_t + G0 * psi_t)
+// `wide` picks the evaluator walk: true forms the value sum beside the two derivative sums, false is multiband2d_curl_exact
+// alone, whose channels have the same bits as the derivative sums of the former (fade 0: the weight is w[b] * 1.0f).  A caller
+// passes wide = true wherever psi is read (near, or flow != nullptr); it may pass true elsewhere too, and the kernels do so
+// for a whole wave when any of its lanes needs it: no wave walks the nine taps twice.  The bits do not depend on `wide`.
+template <bool PADDED = false, typename A>
+WN_EVAL_FN void multiband2d_curl_bounded_at(const A &a, const float *coef, int where, float ramp, const float G[2],
+                                            const float *flow, bool wide, const float p[2], float s, float v[2])
+{
+    if (where == kBoundInside) {
+        v[0] = v[1] = 0.0f;
+        return;
+    }
+    if (!wide) { // far, no stream: the unbounded field
+        multiband2d_curl_exact<PADDED>(a, coef, p, s, v);
+        return;
+    }
+    float g[2];
+    float psi = multiband2d_footprint_exact<true, PADDED>(a, coef, p, s, g);
+    if (flow) {
+        const float a0 = flow[0] * p[1];
+        const float a1 = flow[1] * p[0];
+        psi = psi + (a0 - a1);
+        g[0] = g[0] - flow[1];
+        g[1] = g[1] + flow[0];
+    }
+    if (where == kBoundFar) {
+        v[0] = g[1];
+        v[1] = -g[0];
+        return;
+    }
+    const float t0 = ramp * g[1];
+    const float u0 = G[1] * psi;
+    const float t1 = ramp * g[0];
+    const float u1 = G[0] * psi;
+    v[0] = t0 + u0;
+    v[1] = -(t1 + u1);
+}
+
+// multiband2d_curl_exact with the obstacles obs[0 .. nobs) and the stream `flow` ({ux, uy}, or nullptr): nobs == 0 with
+// flow == nullptr, and far points with flow == nullptr, carry its bits.  `a` must have fade == 0.
+template <bool PADDED = false, typename A, typename O>
+WN_EVAL_FN void multiband2d_curl_bounded_exact(const A &a, const float *coef, const O *obs, int nobs, const float *flow,
+                                               const float p[2], float s, float v[2])
+{
+    float ramp, G[2];
+    const int where = obstacle_ramp<2>(obs, nobs, p, ramp, G);
+    multiband2d_curl_bounded_at<PADDED>(a, coef, where, ramp, G, flow, where == kBoundNear || flow != nullptr, p, s, v);
 }
 
 // ---- one explicit time step of a particle through a velocity field (include/wnoise_advect.h; absent from the reference) --

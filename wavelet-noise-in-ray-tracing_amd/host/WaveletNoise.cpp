@@ -10,6 +10,7 @@
 #include "wn_host.hpp"
 #include "wnoise_advect.h"
 #include "wnoise_bounded.h"
+#include "wnoise_bounded2d.h"
 #include "wnoise_curl2d.h"
 #include "wnoise_footprint.h"
 #include "wnoise_multiband2d.h"
@@ -607,6 +608,53 @@ void WaveletNoise::WMultibandNoise2DAdvectCurl(const float *xy, size_t n, const 
     advect_batch<2>(xy, n, a, xy_out, traj, [&](float *pos, float *path) {
         return wn_multiband2d_curl_advect_points(tile(2), pos, n, sarg, firstBand, nbands, w, variance, &a, pos, path, nullptr);
     }, "wn_multiband2d_curl_advect_points");
+}
+
+// ---- that field with solid boundaries and a background stream (include/wnoise_bounded2d.h): as the four members above, the
+// obstacle list and the stream beside the bands
+void WaveletNoise::WMultibandNoise2DCurlBounded(const float p[2], const wn_obstacle2d *obs, int nobs, const float *flow,
+                                                float sarg, int firstBand, int nbands, const float *w, float v[2],
+                                                float variance) const
+{
+    if (tileDims == 3) return WMultibandNoise2DCurlBounded(p, 1, obs, nobs, flow, sarg, firstBand, nbands, w, variance, v);
+    if (wnhost_multiband2d_curl_bounded(noiseCoefficients.empty() ? nullptr : noiseCoefficients.data(), tileSizeN, p, sarg,
+                                        firstBand, nbands, w, variance, obs, nobs, flow, v))
+        throw std::runtime_error("WMultibandNoise2DCurlBounded: nbands outside 0..8, or an obstacle list or a stream that "
+                                 "wn_multiband2d_curl_bounded_points refuses");
+}
+
+void WaveletNoise::WMultibandNoise2DCurlBounded(const float *xy, size_t n, const wn_obstacle2d *obs, int nobs,
+                                                const float *flow, float sarg, int firstBand, int nbands, const float *w,
+                                                float variance, float *out2) const
+{
+    if (!n) return;
+    wnhost::DeviceBuffer in(2 * n * sizeof(float)), res(2 * n * sizeof(float));
+    in.upload(xy);
+    check(wn_multiband2d_curl_bounded_points(tile(2), in.as<float>(), n, sarg, firstBand, nbands, w, variance, obs, nobs, flow,
+                                             res.as<float>(), nullptr), "wn_multiband2d_curl_bounded_points");
+    res.download(out2);
+}
+
+void WaveletNoise::WMultibandNoise2DAdvectCurlBounded(const float p[2], const wn_advect2d &a, const wn_obstacle2d *obs,
+                                                      int nobs, const float *flow, float sarg, int firstBand, int nbands,
+                                                      const float *w, float p_out[2], float *traj, float variance) const
+{
+    if (tileDims == 3)
+        return WMultibandNoise2DAdvectCurlBounded(p, 1, a, obs, nobs, flow, sarg, firstBand, nbands, w, variance, p_out, traj);
+    if (wnhost_multiband2d_curl_bounded_advect(noiseCoefficients.empty() ? nullptr : noiseCoefficients.data(), tileSizeN, p,
+                                               sarg, firstBand, nbands, w, variance, obs, nobs, flow, &a, p_out, traj))
+        throw std::runtime_error("WMultibandNoise2DAdvectCurlBounded: nbands outside 0..8, or an obstacle list, a stream or a "
+                                 "wn_advect2d that wn_multiband2d_curl_bounded_advect_points refuses");
+}
+
+void WaveletNoise::WMultibandNoise2DAdvectCurlBounded(const float *xy, size_t n, const wn_advect2d &a, const wn_obstacle2d *obs,
+                                                      int nobs, const float *flow, float sarg, int firstBand, int nbands,
+                                                      const float *w, float variance, float *xy_out, float *traj) const
+{
+    advect_batch<2>(xy, n, a, xy_out, traj, [&](float *pos, float *path) {
+        return wn_multiband2d_curl_bounded_advect_points(tile(2), pos, n, sarg, firstBand, nbands, w, variance, obs, nobs, flow,
+                                                         &a, pos, path, nullptr);
+    }, "wn_multiband2d_curl_bounded_advect_points");
 }
 
 // ---- batched members ----------------------------------------------------------------------------------

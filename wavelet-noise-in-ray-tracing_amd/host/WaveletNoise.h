@@ -24,6 +24,7 @@ struct wn_tile;   // include/wnoise.h
 struct wn_advect; // include/wnoise_advect.h
 struct wn_advect2d; // include/wnoise_curl2d.h
 struct wn_obstacle; // include/wnoise_bounded.h
+struct wn_obstacle2d; // include/wnoise_bounded2d.h
 
 // Statistical analysis structure (WaveletNoise.h:11-18)
 struct DataStats {
@@ -142,6 +143,23 @@ class WaveletNoise {
                                      const float *w, float p_out[2], float *traj = nullptr, float variance = 0.19686f) const;
     void WMultibandNoise2DAdvectCurl(const float *xy, size_t n, const wn_advect2d &a, float s, int firstBand, int nbands,
                                      const float *w, float variance, float *xy_out, float *traj = nullptr) const;
+    // The two members above with solid boundaries and a background stream (absent from the reference;
+    // include/wnoise_bounded2d.h, whose wn_obstacle2d the list `obs` of nobs <= WN_MAX_OBSTACLES discs, hollow discs and
+    // half-planes holds): the stream function, plus ux * py - uy * px when flow = {ux, uy} is not nullptr, fades to zero
+    // towards every obstacle; v is zero inside one and, without a stream, has the unbounded bits far from all of them.  The
+    // one-point members run on the host (wnhost_multiband2d_curl_bounded, wnhost_multiband2d_curl_bounded_advect),
+    // bit-identical to wn_multiband2d_curl_bounded_points / _advect_points, which the batched forms call.  A list or a stream
+    // the C ABI refuses makes every member throw.
+    void WMultibandNoise2DCurlBounded(const float p[2], const wn_obstacle2d *obs, int nobs, const float *flow, float s,
+                                      int firstBand, int nbands, const float *w, float v[2], float variance = 0.19686f) const;
+    void WMultibandNoise2DCurlBounded(const float *xy, size_t n, const wn_obstacle2d *obs, int nobs, const float *flow, float s,
+                                      int firstBand, int nbands, const float *w, float variance, float *out2) const;
+    void WMultibandNoise2DAdvectCurlBounded(const float p[2], const wn_advect2d &a, const wn_obstacle2d *obs, int nobs,
+                                            const float *flow, float s, int firstBand, int nbands, const float *w,
+                                            float p_out[2], float *traj = nullptr, float variance = 0.19686f) const;
+    void WMultibandNoise2DAdvectCurlBounded(const float *xy, size_t n, const wn_advect2d &a, const wn_obstacle2d *obs, int nobs,
+                                            const float *flow, float s, int firstBand, int nbands, const float *w,
+                                            float variance, float *xy_out, float *traj = nullptr) const;
     // Divergence-free curl noise (absent from the reference; include/wnoise.h): the curl of the vector potential whose
     // components are evaluate3D (WMultibandNoiseCurl: WMultibandNoise, normal == NULL) of this tile shifted by the whole-cell
     // offsets offsets9 = (x, y, z) of psi0, psi1, psi2; nullptr: defaultCurlOffsets().  evaluate3DCurl(p, ., v) is

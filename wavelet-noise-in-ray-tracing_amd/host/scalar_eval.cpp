@@ -10,6 +10,7 @@
 #include "wn_eval.hpp"
 #include "wnoise_advect.h"
 #include "wnoise_bounded.h"
+#include "wnoise_bounded2d.h"
 #include "wnoise_curl2d.h"
 #include "wnoise_perlin_curl.h"
 
@@ -178,13 +179,38 @@ void wnhost_multiband2d_curl(const float *coef, int n, const float p[2], float s
 int wnhost_multiband2d_curl_advect(const float *coef, int n, const float p_in[2], float s, int first_band, int nbands,
                                    const float *w, float var_per_band, const wn_advect2d *a, float p_out[2], float *traj)
 {
+    // no obstacle and no stream: the same bits
+    return wnhost_multiband2d_curl_bounded_advect(coef, n, p_in, s, first_band, nbands, w, var_per_band, nullptr, 0, nullptr, a,
+                                                  p_out, traj);
+}
+
+int wnhost_multiband2d_curl_bounded(const float *coef, int n, const float p[2], float s, int first_band, int nbands,
+                                    const float *w, float var_per_band, const wn_obstacle2d *obstacles, int nobs,
+                                    const float *flow2, float v[2])
+{
+    if (wn::obstacle_fault<2>(obstacles, nobs)) return 1;
+    if (flow2 && !(std::isfinite(flow2[0]) && std::isfinite(flow2[1]))) return 1;
+    Footprint f;
+    if (!footprint_setup(f, coef, n, first_band, nbands, w, var_per_band, 0)) return 1;
+    wn::multiband2d_curl_bounded_exact(f, f.coef, obstacles, nobs, flow2, p, s, v);
+    return 0;
+}
+
+int wnhost_multiband2d_curl_bounded_advect(const float *coef, int n, const float p_in[2], float s, int first_band, int nbands,
+                                           const float *w, float var_per_band, const wn_obstacle2d *obstacles, int nobs,
+                                           const float *flow2, const wn_advect2d *a, float p_out[2], float *traj)
+{
     if (!a || a->method < WN_ADVECT_EULER || a->method > WN_ADVECT_RK4 || a->steps < 0 || a->traj_every < 0) return 1;
     if (!std::isfinite(a->h) || !std::isfinite(a->gain) || !std::isfinite(a->drift[0]) || !std::isfinite(a->drift[1]) ||
         (a->traj_every && !traj))
         return 1;
+    if (wn::obstacle_fault<2>(obstacles, nobs)) return 1;
+    if (flow2 && !(std::isfinite(flow2[0]) && std::isfinite(flow2[1]))) return 1;
     Footprint f;
     if (!footprint_setup(f, coef, n, first_band, nbands, w, var_per_band, 0)) return 1;
-    const auto velocity = [&](const float q[2], float v[2]) { wn::multiband2d_curl_exact(f, f.coef, q, s, v); };
+    const auto velocity = [&](const float q[2], float v[2]) {
+        wn::multiband2d_curl_bounded_exact(f, f.coef, obstacles, nobs, flow2, q, s, v);
+    };
     const float h = a->h, h2 = 0.5f * a->h, h6 = a->h / 6.0f;
     float p[2] = {p_in[0], p_in[1]};
     if (a->traj_every) traj[0] = p[0], traj[1] = p[1];

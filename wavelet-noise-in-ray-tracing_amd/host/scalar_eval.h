@@ -103,6 +103,21 @@ struct wn_advect2d;
 WNHOST_API int wnhost_multiband2d_curl_advect(const float *coef, int n, const float p_in[2], float s, int first_band,
                                               int nbands, const float *w, float var_per_band, const struct wn_advect2d *a,
                                               float p_out[2], float *traj);
+// That field with solid boundaries and a background stream (absent from the reference; include/wnoise_bounded2d.h, whose
+// wn_obstacle2d the list holds): the ramp of the obstacles fades the stream function psi_t = psi + (ux * py - uy * px)
+// (flow = {ux, uy}; NULL: psi alone), v = (d(A psi_t)/dy, -d(A psi_t)/dx) -- zero inside a solid, and without a stream the
+// bits of wnhost_multiband2d_curl far from all of them and with nobs == 0: the bits of wn_multiband2d_curl_bounded_points.
+// wnhost_multiband2d_curl_bounded_advect traces one particle through it as wnhost_multiband2d_curl_advect does through the
+// unbounded field: the bits of wn_multiband2d_curl_bounded_advect_points.  Both return 0, or 1 and write nothing for an
+// obstacle list, a stream, nbands or `a` that the entry point refuses.
+struct wn_obstacle2d;
+WNHOST_API int wnhost_multiband2d_curl_bounded(const float *coef, int n, const float p[2], float s, int first_band, int nbands,
+                                               const float *w, float var_per_band, const struct wn_obstacle2d *obstacles,
+                                               int nobs, const float *flow2, float v[2]);
+WNHOST_API int wnhost_multiband2d_curl_bounded_advect(const float *coef, int n, const float p_in[2], float s, int first_band,
+                                                      int nbands, const float *w, float var_per_band,
+                                                      const struct wn_obstacle2d *obstacles, int nobs, const float *flow2,
+                                                      const struct wn_advect2d *a, float p_out[2], float *traj);
 // grey level of wavelet_multiband_texture::value (texture.h; wn_wavelet_multiband_texture_points): the function above
 // (normal == NULL) at (float)((double)xyz * scale) and footprint s, through wavelet_texture's grey; coef == NULL: 0.5
 WNHOST_API float wnhost_wavelet_multiband_texture_value(const float *coef, int n, double scale, int first_band, int nbands,

@@ -497,6 +497,66 @@ class WaveletNoise:
                                                      float(variance), C.byref(a), _ptr(out), _ptr(traj), _stream()))
         return out if traj is None else (out, traj)
 
+    # -- that field with solid boundaries and a background stream (include/wnoise_bounded2d.h; absent from the reference)
+    _OBSTACLE2D_KINDS = {"disc": _capi.WN_OBSTACLE_SPHERE, "container": _capi.WN_OBSTACLE_CONTAINER,
+                         "halfplane": _capi.WN_OBSTACLE_HALFSPACE}
+
+    @classmethod
+    def _bounds2d(cls, obstacles, flow):
+        """The wn_obstacle2d array of a list of ("disc", c, r, d0), ("container", c, r, d0) and ("halfplane", n, o, d0)
+        entries, its length, and the float pair of flow=(ux, uy) or None; the library checks the values."""
+        obstacles = list(obstacles)
+        arr = (_capi.wn_obstacle2d * max(1, len(obstacles)))()
+        for dst, entry in zip(arr, obstacles):
+            kind, c, r, d0 = entry
+            if kind not in cls._OBSTACLE2D_KINDS:
+                raise ValueError(f"obstacle kind: one of {sorted(cls._OBSTACLE2D_KINDS)}")
+            c = [float(x) for x in c]
+            if len(c) != 2:
+                raise ValueError("an obstacle's centre or normal has two components")
+            dst.kind, dst.c, dst.r, dst.d0 = cls._OBSTACLE2D_KINDS[kind], (C.c_float * 2)(*c), float(r), float(d0)
+        if flow is not None:
+            flow = [float(x) for x in flow]
+            if len(flow) != 2:
+                raise ValueError("flow: None or (ux, uy)")
+            flow = (C.c_float * 2)(*flow)
+        return arr, len(obstacles), flow
+
+    def WMultibandNoise2DCurlBounded(self, p, obstacles, s, firstBand, nbands, w, variance=0.19686, flow=None):
+        """WMultibandNoise2DCurl with its stream function faded to zero towards every solid of `obstacles`
+        (wn_multiband2d_curl_bounded_points): still divergence-free, with no normal component on a solid's surface.
+        `obstacles`: a list of at most 16 ("disc", c, r, d0), ("container", c, r, d0) or ("halfplane", n, o, d0), in the
+        coordinates of p; d0 is the width of the ramp.  flow=(ux, uy) adds the uniform stream ux * y - uy * x to the stream
+        function, so that it is bent around the solids with the noise (a drift is not).  A point inside a solid gets 0; with
+        flow=None a point at distance >= d0 from every solid (and obstacles=[]) has the bits of WMultibandNoise2DCurl."""
+        pts = _dev(p, torch.float32).reshape(-1, 2)
+        out = torch.empty((pts.shape[0], 2), dtype=torch.float32, device="cuda")
+        wa = (C.c_float * max(1, nbands))(*[float(x) for x in list(w)[:nbands]])
+        obs, nobs, fl = self._bounds2d(obstacles, flow)
+        check(_lib.wn_multiband2d_curl_bounded_points(self._handle(2), _ptr(pts), pts.shape[0], float(s), int(firstBand),
+                                                      int(nbands), wa, float(variance), obs, nobs, fl, _ptr(out), _stream()))
+        return out
+
+    def WMultibandNoise2DAdvectCurlBounded(self, pts, h, steps, obstacles, s, firstBand, nbands, w, variance=0.19686,
+                                           method="rk4", gain=1.0, drift=None, trajectory_every=0, flow=None):
+        """WMultibandNoise2DAdvectCurl through gain * WMultibandNoise2DCurlBounded(., obstacles, s, firstBand, nbands, w,
+        variance, flow) + drift, all steps inside the kernel (wn_multiband2d_curl_bounded_advect_points): particles flow
+        around the solids.  A particle inside one moves by drift alone."""
+        if method not in self._ADVECT_METHODS:
+            raise ValueError(f"method: one of {sorted(self._ADVECT_METHODS)}")
+        pts = _dev(pts, torch.float32).reshape(-1, 2)
+        n, steps, every = pts.shape[0], int(steps), int(trajectory_every)
+        a = _capi.wn_advect2d(self._ADVECT_METHODS[method], steps, float(h), float(gain),
+                              (C.c_float * 2)(*([0.0] * 2 if drift is None else [float(x) for x in drift])), every)
+        wa = (C.c_float * max(1, nbands))(*[float(x) for x in list(w)[:nbands]])
+        obs, nobs, fl = self._bounds2d(obstacles, flow)
+        out = torch.empty((n, 2), dtype=torch.float32, device="cuda")
+        traj = torch.empty((steps // every + 1, n, 2), dtype=torch.float32, device="cuda") if every >= 1 and steps >= 0 else None
+        check(_lib.wn_multiband2d_curl_bounded_advect_points(self._handle(2), _ptr(pts), n, float(s), int(firstBand),
+                                                             int(nbands), wa, float(variance), obs, nobs, fl, C.byref(a),
+                                                             _ptr(out), _ptr(traj), _stream()))
+        return out if traj is None else (out, traj)
+
     def evaluate3DProjectedGradient(self, p, normal):
         """evaluate3DProjected and its gradient with respect to p, the normal held fixed (wn_eval3d_projected_grad_points):
         (N, 4).  `normal`: one for all points, or one per point.  The value column has the bits of evaluate3DProjected;
@@ -939,6 +999,16 @@ def generate2DMultibandNoiseCurl(noise, image_size, s=-16.0, firstBand=0, nbands
     d/dy and vy = -d/dx of generate2DMultibandNoiseGradient, the same bits but for vy's sign."""
     return _multiband2d_image(_lib.wn_multiband2d_curl_grid, 2, noise, image_size, s, firstBand, nbands, w, variance, den,
                               out)
+
+
+def generate2DMultibandNoiseCurlBounded(noise, image_size, obstacles, s=-16.0, firstBand=0, nbands=5, w=None, variance=0.19686,
+                                        den=None, out=None, flow=None):
+    """generate2DMultibandNoiseCurl with solid boundaries and a background stream (wn_multiband2d_curl_bounded_grid):
+    [2, ny, nx].  `obstacles` and `flow` as WaveletNoise.WMultibandNoise2DCurlBounded, in the lattice's coordinate
+    p = (i/den)*4."""
+    obs, nobs, fl = WaveletNoise._bounds2d(obstacles, flow)
+    return _multiband2d_image(lambda tile, g, s_, first, nb, wa, var, o, st: _lib.wn_multiband2d_curl_bounded_grid(
+        tile, g, s_, first, nb, wa, var, obs, nobs, fl, o, st), 2, noise, image_size, s, firstBand, nbands, w, variance, den, out)
 
 
 def generate3DSlicedOctaveBandNoise(imageSize, octave, outputFile, noise, flags=WN_GRID_EXACT, out=None):
