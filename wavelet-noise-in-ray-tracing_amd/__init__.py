@@ -28,6 +28,7 @@ from .noise import (  # noqa: E402
     wavelet_volume, wavelet_volume_launcher, multiband_volume, perlin_volume, turb_volume, device_info, HipTimer,
     wavelet_gradient_volume, multiband_gradient_volume, wavelet2d_gradient_image, projected_gradient_volume,
     perlin_gradient_volume, turb_gradient_volume, curl_volume, multiband_curl_volume, perlin_curl_volume,
+    wavelet_bricks, multiband_bricks,
 )
 from .shard import slab_bounds, gather_volume, NativeComm  # noqa: E402
 from . import formats  # noqa: E402
@@ -45,5 +46,5 @@ __all__ = [
     "wavelet_volume", "wavelet_volume_launcher", "multiband_volume", "perlin_volume", "turb_volume", "device_info",
     "HipTimer", "wavelet_gradient_volume", "multiband_gradient_volume", "wavelet2d_gradient_image",
     "projected_gradient_volume", "perlin_gradient_volume", "turb_gradient_volume", "curl_volume",
-    "multiband_curl_volume", "perlin_curl_volume", "slab_bounds", "gather_volume", "NativeComm", "formats",
+    "multiband_curl_volume", "perlin_curl_volume", "wavelet_bricks", "multiband_bricks", "slab_bounds", "gather_volume", "NativeComm", "formats",
 ]

@@ -1,6 +1,6 @@
 """ctypes binding of libwnoise_hip.so (include/wnoise.h, include/wnoise_perlin_curl.h, include/wnoise_footprint.h,
 include/wnoise_perlin_footprint.h, include/wnoise_multiband2d.h, include/wnoise_advect.h, include/wnoise_bounded.h,
-include/wnoise_perlin_advect.h, include/wnoise_curl2d.h, include/wnoise_bounded2d.h).
+include/wnoise_perlin_advect.h, include/wnoise_curl2d.h, include/wnoise_bounded2d.h, include/wnoise_bricks.h).
 
 The library is the product: if it is missing or fails to load this module raises, it never
 substitutes a CPU implementation.
@@ -232,6 +232,14 @@ BOUNDED2D_SIGNATURES = {
     "wn_multiband2d_curl_bounded_advect_points": (_i, [_vp, _vp, _sz, _f, _i, _i, _fp, _f, _o2p, _i, _fp, _a2p, _vp, _vp, _vp]),
 }
 
+# name -> (restype, argtypes); every symbol include/wnoise_bricks.h declares.
+WN_BRICK = 8
+BRICKS_SIGNATURES = {
+    # tile, grid, bricks, n, [s, first_band, nbands, w, var,] out, stream
+    "wn_eval3d_bricks": (_i, [_vp, _gp, _vp, _sz, _vp, _vp]),
+    "wn_multiband3d_bricks": (_i, [_vp, _gp, _vp, _sz, _f, _i, _i, _fp, _f, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -248,7 +256,7 @@ def load():
     for name, (res, args) in (*SIGNATURES.items(), *PERLIN_CURL_SIGNATURES.items(), *FOOTPRINT_SIGNATURES.items(),
                               *PERLIN_FOOTPRINT_SIGNATURES.items(), *MULTIBAND2D_SIGNATURES.items(),
                               *ADVECT_SIGNATURES.items(), *BOUNDED_SIGNATURES.items(), *PERLIN_ADVECT_SIGNATURES.items(),
-                              *CURL2D_SIGNATURES.items(), *BOUNDED2D_SIGNATURES.items()):
+                              *CURL2D_SIGNATURES.items(), *BOUNDED2D_SIGNATURES.items(), *BRICKS_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

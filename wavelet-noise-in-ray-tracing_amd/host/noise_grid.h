@@ -13,6 +13,7 @@
 #include "PerlinNoise.hpp"
 #include "WaveletNoise.h"
 #include "wn_host.hpp"
+#include "wnoise_bricks.h"
 #include "wnoise_multiband2d.h"
 
 namespace wnhost {
@@ -123,4 +124,46 @@ inline void generatePerlinNoise3DSliced(int imageSize, int octave, const std::st
         wnhost::check(wn_perlin_grid(perlin.perm(), &g, out, nullptr), "wn_perlin_grid");
     });
     std::cout << "Generated Perlin 3D Sliced Octave " << octave << " noise: " << outputFile << std::endl;
+}
+
+// ---- sparse brick lists (include/wnoise_bricks.h; absent from the reference) -------------------------------------------
+// The lattices of the volume generators on a device list of n 8 x 8 x 8 bricks (bx, by, bz): brick i fills
+// out_dev[512 i + lx + 8 (ly + 8 lz)].  bounds = {nx, ny, z0, z1} (nullptr: den on each axis) says which bricks are in
+// range; the others are left untouched.  Both only enqueue on `stream`: the list and the output stay on the device, where
+// a sparse-volume holder keeps them.
+namespace wnhost {
+inline wn_grid brick_lattice(int den, const int *bounds, float octave_scale, float post_scale, float out_scale, int flags)
+{
+    wn_grid g{};
+    g.den = den;
+    g.nx = bounds ? bounds[0] : den;
+    g.ny = bounds ? bounds[1] : den;
+    g.z0 = bounds ? bounds[2] : 0;
+    g.z1 = bounds ? bounds[3] : den;
+    g.base_range = 4.0f;
+    g.octave_scale = octave_scale;
+    g.post_scale = post_scale;
+    g.z_mode = WN_Z_LATTICE;
+    g.out_scale = out_scale;
+    g.flags = flags;
+    return g;
+}
+} // namespace wnhost
+
+// q = ((i / den) * 4) * 2^octave * 2 on all three axes, evaluate3D(q) / sqrt(0.18402): config 2's lattice.
+inline void waveletBricks(WaveletNoise &noise, int den, const int32_t *bricks_dev, size_t n, int octave, float *out_dev,
+                          const int *bounds = nullptr, int flags = WN_GRID_DEFAULT, void *stream = nullptr)
+{
+    const wn_grid g = wnhost::brick_lattice(den, bounds, std::pow(2.0f, octave), 2.0f, 1.0f / std::sqrt(0.18402f), flags);
+    wnhost::check(wn_eval3d_bricks(noise.tile(3), &g, bricks_dev, n, out_dev, stream), "wn_eval3d_bricks");
+}
+
+// WMultibandNoise(p = (i / den) * 4, s, NULL, firstBand, nbands, w): config 3's lattice.
+inline void multibandBricks(WaveletNoise &noise, int den, const int32_t *bricks_dev, size_t n, float s, int firstBand,
+                            int nbands, const float *w, float *out_dev, float variance = 0.18402f,
+                            const int *bounds = nullptr, int flags = WN_GRID_DEFAULT, void *stream = nullptr)
+{
+    const wn_grid g = wnhost::brick_lattice(den, bounds, 1.0f, 1.0f, 1.0f, flags);
+    wnhost::check(wn_multiband3d_bricks(noise.tile(3), &g, bricks_dev, n, s, firstBand, nbands, w, variance, out_dev, stream),
+                  "wn_multiband3d_bricks");
 }

@@ -1101,6 +1101,48 @@ def multiband_volume(noise, den, nx, ny, z0, z1, s=-16.0, firstBand=0, nbands=5,
     return out[: g.nz * ny * nx].view(g.nz, ny, nx)
 
 
+# ---- sparse brick lists (include/wnoise_bricks.h) ---------------------------------------------------
+def _bricks_args(den, bricks, bounds, out):
+    """The (n, 3) int32 device list, (nx, ny, z0, z1) -- `den` on each axis by default, as the generators do -- and the
+    (n, 8, 8, 8) output, indexed [brick][z][y][x]."""
+    if not (isinstance(bricks, torch.Tensor) and bricks.is_cuda and bricks.dtype == torch.int32 and bricks.dim() == 2
+            and bricks.shape[1] == 3 and bricks.is_contiguous()):
+        raise ValueError("bricks must be a contiguous (n, 3) int32 CUDA tensor of (bx, by, bz)")
+    nx, ny, z0, z1 = (den, den, 0, den) if bounds is None else (int(v) for v in bounds)
+    n = bricks.shape[0]
+    edge = _capi.WN_BRICK
+    if out is None:
+        out = torch.empty((n, edge, edge, edge), dtype=torch.float32, device="cuda")
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == n * edge ** 3):
+        raise ValueError("out must be a contiguous float32 CUDA tensor of n * 512 elements")
+    return n, (nx, ny, z0, z1), out
+
+
+def wavelet_bricks(noise, den, bricks, octave, bounds=None, exact=False, out=None):
+    """wavelet_volume on the listed 8^3 bricks of the lattice only: brick (bx, by, bz) holds the samples
+    [8bz, 8bz+8) x [8by, 8by+8) x [8bx, 8bx+8) of wavelet_volume(noise, den, ...), as out[i][z][y][x].  Bricks outside
+    `bounds` are left untouched (with out=None their contents are undefined)."""
+    n, (nx, ny, z0, z1), out = _bricks_args(den, bricks, bounds, out)
+    g = GridSpec(den, nx, ny, z0, z1, octave_scale=_octave_scale(octave), post_scale=2.0,
+                 out_scale=_inv_stddev(0.18402), flags=WN_GRID_EXACT if exact else WN_GRID_DEFAULT)
+    gc = g.c()
+    check(_lib.wn_eval3d_bricks(noise._handle(3), C.byref(gc), _ptr(bricks), n, _ptr(out), _stream()))
+    return out.view(n, _capi.WN_BRICK, _capi.WN_BRICK, _capi.WN_BRICK)
+
+
+def multiband_bricks(noise, den, bricks, s=-16.0, firstBand=0, nbands=5, w=None, variance=0.18402, bounds=None,
+                     exact=False, out=None):
+    """multiband_volume on the listed 8^3 bricks of the lattice only, laid out as wavelet_bricks."""
+    w = [1.0] * nbands if w is None else list(w)
+    n, (nx, ny, z0, z1), out = _bricks_args(den, bricks, bounds, out)
+    g = GridSpec(den, nx, ny, z0, z1, flags=WN_GRID_EXACT if exact else WN_GRID_DEFAULT)
+    gc = g.c()
+    wa = (C.c_float * max(1, nbands))(*[float(x) for x in w[:nbands]])
+    check(_lib.wn_multiband3d_bricks(noise._handle(3), C.byref(gc), _ptr(bricks), n, float(s), int(firstBand),
+                                     int(nbands), wa, float(variance), _ptr(out), _stream()))
+    return out.view(n, _capi.WN_BRICK, _capi.WN_BRICK, _capi.WN_BRICK)
+
+
 def _grad_out(g, out):
     n = 4 * g.nz * g.ny * g.nx
     if out is None:
