@@ -6,6 +6,7 @@
   plan_sep / plan_sep_bz       csrc/wn_wavelet_grid.hip        grid3d_sep_kernel<NB, XW>
   exact_lds_try                csrc/wn_wavelet_exact.hip       grid3d_exact_lds_kernel
   brick_plan                   csrc/wn_brick.hpp               grad3d_ / curl3d_grid_sep_kernel<NB>
+  bricks_call + sep_try        csrc/wn_wavelet_bricks.hip      bricks_sep_kernel<NB> (brick lists: bricks_route)
 
 Every *_try returns None when its kernel takes the lattice, else the NAME of the first check that declines it: "static"
 for the checks that do not involve a coordinate bound (row width, tile, alignment, z0 < 0, WN_Z_CONST ...), and "gate",
@@ -16,6 +17,8 @@ SLACK_PER_CELL and GATE are lattice_step's two constants; the mutation checks of
 here to see which rows of the far table move.  A plain helper module (not a conftest): the tests import it by name.
 """
 import math
+import os
+import re
 
 import numpy as np
 
@@ -303,3 +306,74 @@ def deriv_route(g, tile_n, exact, family, bands=None):
         if why["brick"] is None:
             return sep.format(nb), why
     return direct, why
+
+
+# ---- brick lists: bricks_sep_kernel<NB>, else bricks_exact_kernel --------------------------------------------------------------
+BRICKS_REGIME_ON_WHOLE_BRICKS = True   # bricks_call checks the regime on gr; the mutation checks set it to False (on g)
+
+
+def brick_constants():
+    """(WN_BRICK, kBoxCap, kSepBlockCap) as include/wnoise_bricks.h and csrc/wn_wavelet_bricks.hip state them."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with open(os.path.join(root, "include", "wnoise_bricks.h")) as f:
+        (edge,) = re.findall(r"^#define WN_BRICK (\d+)\b", f.read(), re.M)
+    with open(os.path.join(root, "wavelet-noise-in-ray-tracing_amd", "csrc", "wn_wavelet_bricks.hip")) as f:
+        src = f.read()
+    caps = []
+    for decl in (r"constexpr int kBoxCap = ([^;]+);", r"constexpr size_t kSepBlockCap = ([^;]+);"):
+        (expr,) = re.findall(decl, src)
+        caps.append(math.prod(int(v.strip().rstrip("u")) for v in expr.split("*")))
+    assert "constexpr int kEdge = WN_BRICK" in src
+    return int(edge), caps[0], caps[1]
+
+
+def brick_range(g, edge=8):
+    """(nbx, nby, bz0, bz1) of bricks_call: ceil(nx / 8), ceil(ny / 8), floor(z0 / 8), ceil(z1 / 8)."""
+    return -(-g.nx // edge), -(-g.ny // edge), g.z0 // edge, -(-(g.z0 + g.nz) // edge)
+
+
+def bricks_rounded(g, edge=8):
+    """gr: the lattice rounded up to whole bricks, on which sep_try checks the regime."""
+    nbx, nby, bz0, bz1 = brick_range(g, edge)
+    return Grid(g.den, nbx * edge, nby * edge, bz0 * edge, (bz1 - bz0) * edge, g.base_range, g.octave_scale, g.post_scale)
+
+
+def bricks_band_scales(g, bands):
+    """The oscale sep_try passes to lattice_step per active band: (float)(octave_scale * qmul_b), qmul 1 or 2 * 2^(first+b)."""
+    if bands is None:
+        return [g.octave_scale]
+    return [float(f32(g.octave_scale) * f32(2.0 * 2.0 ** (bands[1] + b))) for b in range(active_bands(*bands))]
+
+
+def bricks_route(g, tile_n, exact, bands=None):
+    """bricks_call + sep_try of wn_eval3d_bricks (bands None) / wn_multiband3d_bricks (bands = (s, first, nbands)):
+    ("sep<NB>", None), or ("exact", check) with the first check that declines the separable kernel: "flag", "roundable",
+    "no active band", "empty tile", "negative step", "gate", "two_mids", "box"; ("nothing", "empty volume") where no brick
+    is in range."""
+    edge, box_cap, _ = brick_constants()
+    if g.nx == 0 or g.ny == 0 or g.nz == 0:
+        return "nothing", "empty volume"
+    if exact:
+        return "exact", "flag"
+    nbx, nby, bz0, bz1 = brick_range(g, edge)
+    imax, imin = 2 ** 31 - 1, -2 ** 31
+    if not (nbx * edge <= imax and nby * edge <= imax and bz0 * edge >= imin and bz1 * edge <= imax):
+        return "exact", "roundable"
+    oscales = bricks_band_scales(g, bands)
+    if not oscales:
+        return "exact", "no active band"
+    if tile_n == 0:
+        return "exact", "empty tile"
+    gr = bricks_rounded(g, edge) if BRICKS_REGIME_ON_WHOLE_BRICKS else g
+    for os_ in oscales:
+        step = gr.base_range * float(f32(os_)) * gr.post_scale / gr.den
+        if not (step >= 0.0) or not math.isfinite(step):
+            return "exact", "negative step"
+        ls = lattice_step(gr, os_, False, False, 0.0)
+        if ls is None:
+            return "exact", "gate"
+        if not ls.two_mids():
+            return "exact", "two_mids"
+        if (ls.extent(edge) + 1) * ls.extent(edge) ** 2 > box_cap:
+            return "exact", "box"
+    return f"sep<{len(oscales)}>", None

@@ -456,3 +456,186 @@ def mb2d_check_indices(c, cus, seed=MB2D_SEED):
     parts.append(np.arange(total - 2048, total))
     parts.append(np.random.default_rng([seed, total]).integers(0, total, 8192))
     return np.unique(np.concatenate(parts))
+
+
+# ---- brick lists ---------------------------------------------------------------------------------------------------------------
+BRICKS_SEEDS = (20255, 20256)
+BRICKS_PER_SEED = 30
+BRICKS_MAX_LIST = 40
+BRICKS_DECLINES = ("flag", "two_mids", "gate", "negative step", "no active band", "empty tile")
+_ND = (1.1547005, 0.8862269, 1.0954451, 0.9189385, 1.2533141, 0.8408964)   # full-mantissa factors next to 1
+
+
+def bricks_grid(c):
+    return fp.Grid(c.den, c.nx, c.ny, c.z0, c.z1 - c.z0, c.base_range, c.octave_scale, c.post_scale)
+
+
+def bricks_route(c):
+    return fp.bricks_route(bricks_grid(c), TILE_N[c.tile], c.exact, None if c.bands is None else c.bands[:3])
+
+
+def bricks_top_step(c):
+    """The signed step of the finest active band (None where no band is active)."""
+    os_ = fp.bricks_band_scales(bricks_grid(c), None if c.bands is None else c.bands[:3])
+    return c.base_range * float(f32(os_[-1])) * c.post_scale / c.den if os_ else None
+
+
+def bricks_near_third(c):
+    st = bricks_top_step(c)
+    if st is None:
+        return None
+    r = 3.0 * st
+    return "below" if 0.98 <= r < 1.0 else ("at_above" if 1.0 <= r <= 1.02 else None)
+
+
+def bricks_in_range(c):
+    nbx, nby, bz0, bz1 = fp.brick_range(bricks_grid(c))
+    b = np.asarray(c.bricks, np.int64)
+    return (b[:, 0] >= 0) & (b[:, 0] < nbx) & (b[:, 1] >= 0) & (b[:, 1] < nby) & (b[:, 2] >= bz0) & (b[:, 2] < bz1)
+
+
+def bricks_classes(c):
+    k = {f"tile_{c.tile}", f"lead{c.lead}"}
+    if bricks_near_third(c):
+        k.add("third_" + bricks_near_third(c))
+    if not _pow2(c.den):
+        k.add("den_np2")
+    if any(math.frexp(v)[0] not in (0.5, -0.5) for v in (c.base_range, c.octave_scale, c.post_scale)):
+        k.add("non_dyadic")
+    if c.z0 < 0:
+        k.add("z0<0")
+    if c.z0 % 8 and c.z1 % 8:
+        k.add("ragged_z")
+    if c.nx % 8 and c.ny % 8:
+        k.add("ragged_xy")
+    if c.out_scale < 0:
+        k.add("neg_out")
+    if c.bands is not None:
+        s, first, nbands, w = c.bands
+        if 0 < fp.active_bands(s, first, nbands) < nbands:
+            k.add("s_cut")
+        k.add("first_neg" if first < 0 else ("first_pos" if first > 0 else "first_0"))
+        if any(x == 0.0 for x in w):
+            k.add("zero_w")
+    n = len(c.bricks)
+    k.add("len1" if n == 1 else ("len_odd" if n % 2 else "len_even"))
+    live = bricks_in_range(c)
+    if n % 2 == 0 and live[-2:].sum() == 1:
+        k.add("half_dead_tail")
+    nbx, nby, bz0, bz1 = fp.brick_range(bricks_grid(c))
+    b = np.asarray(c.bricks, np.int64)
+    for name, hit in (("out_x_lo", b[:, 0] < 0), ("out_x_hi", b[:, 0] >= nbx), ("out_y_lo", b[:, 1] < 0), ("out_y_hi", b[:, 1] >= nby),
+                      ("out_z_lo", b[:, 2] < bz0), ("out_z_hi", b[:, 2] >= bz1)):
+        if hit.any():
+            k.add(name)
+    if len({tuple(r) for r in b.tolist()}) < n:
+        k.add("duplicate")
+    return k
+
+
+_BRICKS_SIDES = ("out_x_lo", "out_x_hi", "out_y_lo", "out_y_hi", "out_z_lo", "out_z_hi")
+
+
+def _bricks_slots(seed):
+    """(target, near) of a seed's 30 cases: every sep<NB> twice, each declining check once and three of them twice (the two
+    seeds take different halves), and five more sep cases; near: the top band's step next to 1/3."""
+    slots = [[("sep", nb), None] for nb in range(1, 9)] * 2
+    slots = [list(s) for s in slots]
+    slots[seed % 8][1] = "below"
+    slots[8 + (seed + 3) % 8][1] = "below"
+    extra = BRICKS_DECLINES[:3] if seed % 2 else BRICKS_DECLINES[3:]
+    slots += [[d, "at_above" if d == "two_mids" else None] for d in BRICKS_DECLINES + extra]
+    slots += [[("sep", 1 + (seed + 3 * i) % 8), None] for i in range(5)]
+    assert len(slots) == BRICKS_PER_SEED
+    return slots
+
+
+def _draw_bricks(rng, idx, target, near):
+    sep = isinstance(target, tuple)
+    c = SimpleNamespace(lead=(idx // 4 + idx) % 4, exact=target == "flag")
+    c.tile = "empty" if target == "empty tile" else BRICK_TILES[idx % 4]
+    nb = target[1] if sep else int(rng.integers(1, 9))
+    multi = nb > 1 or target == "no active band" or bool(rng.integers(0, 2))
+    nd = idx % 3 == 0
+    if multi:
+        nbands = nb if idx % 5 else min(8, nb + int(rng.integers(1, 4)))      # s cuts the band count
+        first = int(rng.integers(-3, 3))
+        s = -16.0 if nbands == nb else -(first + nb) + 0.5
+        if target == "no active band":
+            s = float(-first) + 0.25
+        w = [float(f32(x)) for x in rng.uniform(0.25, 2.0, nbands)]
+        if idx % 4 == 1 and nbands >= 2:
+            w[int(rng.integers(0, nbands))] = 0.0
+        c.bands = (float(s), first, nbands, w)
+        c.base_range, c.octave_scale, c.post_scale = 4.0, 1.0, 1.0
+        top = 2.0 * 2.0 ** (first + (nb if target != "no active band" else 1) - 1)
+    else:
+        c.bands = None
+        c.base_range, c.octave_scale, c.post_scale = 4.0, float(2.0 ** int(rng.integers(2, 6))), 2.0
+        top = 1.0
+    if nd:
+        f = rng.permutation(len(_ND))[:3]
+        c.base_range, c.octave_scale, c.post_scale = (float(f32(v) * f32(_ND[j])) for v, j in
+                                                      zip((c.base_range, c.octave_scale, c.post_scale), f))
+    num = c.base_range * float(f32(f32(c.octave_scale) * f32(top))) * c.post_scale     # the top band's step is num / den
+    if near == "below":
+        step = float(rng.uniform(0.981, 0.9995)) / 3.0
+    elif near == "at_above":
+        step = float(rng.uniform(1.0005, 1.019)) / 3.0
+    elif target == "two_mids":
+        step = float(rng.uniform(0.4, 2.0))
+    elif target == "gate":
+        step = float(rng.uniform(0.1, 0.17))
+    else:
+        step = float(rng.uniform(0.04, 0.3))
+    c.den = max(1, int(round(num / step)))
+    if idx % 4 == 2 and near is None:
+        c.den = 1 << max(0, int(round(math.log2(num / step))))
+    step = num / c.den
+    # the volume: each axis near or far, ragged or whole bricks, z0 of either sign
+    reach = 1.2e6 / step if target == "gate" else min(3.0e5, 0.5 * (1.0 - min(3.0 * step, 0.99)) / fp.SLACK_PER_CELL) / max(step, 1e-3)
+    ext = [int(min(reach, float(np.exp(rng.uniform(np.log(9.0), np.log(4.0e6)))))) for _ in range(3)]
+    if target == "gate":
+        ext[int(rng.integers(0, 3))] = int(reach)
+    ragged = idx % 2 == 0
+    c.nx, c.ny, c.z1 = (max(9, e // 8 * 8 + (int(rng.integers(1, 8)) if ragged else 0)) for e in ext)
+    zsign = idx % 3
+    c.z0 = 0 if zsign == 0 else (-int(rng.choice([1003, 8 * 125, 20, 8 * 40000])) if zsign == 1 else int(rng.choice([3, 8, 21])))
+    if ragged and c.z0 % 8 == 0:
+        c.z0 -= 3
+    if target == "negative step":
+        c.base_range = -c.base_range
+    c.out_scale = float(f32(rng.choice([INV, 1.0, 0.75, -1.5, -INV])))
+    # the list
+    nbx, nby, bz0, bz1 = fp.brick_range(bricks_grid(c))
+    n = 1 if idx % 3 == 0 else (2 * int(rng.integers(1, 20)) + 1 if idx % 3 == 1 else 2 * int(rng.integers(1, 21)))
+    b = np.stack([rng.integers(0, nbx, n), rng.integers(0, nby, n), rng.integers(bz0, bz1, n)], -1)
+    b[0] = (nbx - 1, nby - 1, bz1 - 1)                                       # the far corner
+    if n >= 3:
+        b[n // 2] = (0, 0, min(max(bz0, 0), bz1 - 1))                        # next to the origin
+        b[1] = b[int(rng.integers(2, n))]                                   # a duplicate
+        side = _BRICKS_SIDES[(idx // 3) % 6]
+        out = {"out_x_lo": (-1, 0, bz0), "out_x_hi": (nbx, 0, bz0), "out_y_lo": (0, -1, bz0), "out_y_hi": (0, nby, bz0),
+               "out_z_lo": (0, 0, bz0 - 1), "out_z_hi": (0, 0, bz1)}[side]
+        b[n - 1 - (idx // 2) % 2 if n % 2 == 0 else 2] = out                  # even lists: in the last pair
+    c.bricks = np.ascontiguousarray(b, np.int32)
+    return c
+
+
+def bricks_cases(seed):
+    """A seed's cases, each with .name, .route (bricks_route's label and declining check)."""
+    rng = np.random.default_rng([seed, 7])
+    cases = []
+    for idx, (target, near) in enumerate(_bricks_slots(seed)):
+        for _attempt in range(400):
+            c = _draw_bricks(rng, idx, target, near)
+            label, why = bricks_route(c)
+            hit = (why is None and label == f"sep<{target[1]}>") if isinstance(target, tuple) else why == target
+            if hit and (near is None or bricks_near_third(c) == near) and (why is not None or bricks_in_range(c).any()):
+                break
+        else:
+            raise AssertionError(f"the generator cannot place bricks seed {seed} case {idx}: {target} {near}")
+        c.route, c.name = (label, why), f"bricks-{seed}-{idx:02d}"
+        assert 1 <= len(c.bricks) <= BRICKS_MAX_LIST
+        cases.append(c)
+    return cases

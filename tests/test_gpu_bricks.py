@@ -285,7 +285,8 @@ def sep_block_cap():
 def test_a_second_grid_stride_trip(env, mb, exact):
     """A list a few workgroups longer than one pass of the launch cap: the separable kernel takes kSepBlockCap pairs of
     bricks per pass, the exact kernel kStrideBlockCap * 256 samples (512 per brick).  The head is random bricks of the
-    512^3 volume; the tail -- LIST, whose bricks the second trip serves -- is checked against the exact dense grid."""
+    512^3 volume, 64 of them checked against the point entry (exact tier: bits) or the float64 reference (default tier:
+    1e-5); the tail -- LIST, whose bricks the second trip serves -- is checked against the exact dense grid."""
     per_pass = sp.STRIDE_BLOCK_CAP * sp.LANES // 512 if exact else 2 * sep_block_cap()
     assert per_pass == (8192 if exact else 4096)
     octave = 4 if mb is None else None
@@ -304,6 +305,16 @@ def test_a_second_grid_stride_trip(env, mb, exact):
         assert np.abs(tail[inside].astype(np.float64) - want).max() <= TOL
         same_bits(tail[inside], env.run("t128", 512, LIST, 2, octave=octave, mb=mb)[inside], "the second trip against a short list")
     assert np.isfinite(got[:per_pass]).all() and np.abs(got[:per_pass]).max() > 0.1
+    # 64 of the head's bricks: the point entry's bits in the exact tier, the float64 reference in the default tier
+    import test_gpu_bricks_far as bf
+    pick = np.sort(np.random.default_rng(11).choice(per_pass, 64, replace=False))
+    if exact:
+        same_bits(got[pick], env.points("t128", 512, head[pick], octave, mb), "the first trip's bricks against the point entry")
+    else:
+        c = bf.case("second_trip", "t128", 512, bf.DY if mb is None else bf.DYM, bounds, mb, None if mb is None else weights(mb[2]),
+                    bf.INV if mb is None else 1.0, bricks=head[pick])
+        ref = bf.ref64(env.coefs["t128"], c, bf.sample_points(c, c.bricks)).reshape(64, 512)
+        assert np.abs(got[pick].astype(np.float64) - ref).max() <= TOL
 
 
 @pytest.mark.gpu

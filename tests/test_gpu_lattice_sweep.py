@@ -14,7 +14,9 @@ GPU, every call writing into a guarded Frame (tests/_frame.py: every sample writ
  * Perlin value, gradient and curl grids: the bits of (float)(point entry) * out_scale, run form and generic kernel;
  * multiband2d grids: the bits of the point entry sent in slices below kPointsLdsMinPoints (the global-gather point
    kernel, whose bits tests/test_gpu_multiband2d.py holds to the host evaluator), in full up to 300 k samples, else around
-   every trip boundary, at the end and at 8,192 random samples.
+   every trip boundary, at the end and at 8,192 random samples;
+ * brick lists (wn_eval3d_bricks / wn_multiband3d_bricks), per (seed, part): the checks of tests/test_gpu_bricks_far.py on
+   lists of at most 40 bricks, classified with _far_plan.bricks_route.
 The sweep traces no kernel: its routes come from the CPU model, which tests/test_gpu_gradient.py, test_gpu_curl.py,
 test_gpu_point_dispatch.py and test_gpu_far_lattice.py pin against traced kernels.
 """
@@ -143,6 +145,52 @@ def test_multiband2d_sweep_reaches_every_row_length_and_trip_class(cus):
     for tile in S.MB2D_TILES:
         assert {c.grad for c in cases if c.tile == tile} == {False, True}, tile
         assert {c.cls for c in cases if c.tile == tile} >= {"one", "multi"}, tile
+
+
+def test_bricks_sweep_reaches_every_route_and_class():
+    cases = [c for seed in S.BRICKS_SEEDS for c in S.bricks_cases(seed)]
+    assert len(cases) == 60 and len({c.name for c in cases}) == 60
+    routes = collections.Counter(c.route for c in cases)
+    for nb in range(1, 9):
+        assert routes[(f"sep<{nb}>", None)] >= 3, routes
+    for check in S.BRICKS_DECLINES:
+        assert routes[("exact", check)] >= 3, routes
+    assert set(routes) == {(f"sep<{nb}>", None) for nb in range(1, 9)} | {("exact", d) for d in S.BRICKS_DECLINES}
+    classes = collections.Counter(k for c in cases for k in S.bricks_classes(c))
+    want = ["third_below", "third_at_above", "tile_t128", "tile_t32", "tile_t8", "tile_t6", "den_np2", "non_dyadic", "z0<0", "ragged_z",
+            "ragged_xy", "neg_out", "s_cut", "first_neg", "first_pos", "zero_w", "len1", "len_odd", "len_even", "half_dead_tail",
+            "out_x_lo", "out_x_hi", "out_y_lo", "out_y_hi", "out_z_lo", "out_z_hi", "duplicate", "lead0", "lead1", "lead2", "lead3"]
+    short = {k: classes[k] for k in want if classes[k] < 3}
+    assert not short, short
+    for c in cases:
+        assert 1 <= len(c.bricks) <= S.BRICKS_MAX_LIST and c.bricks.dtype == np.int32
+        assert S.bricks_route(c) == c.route
+        near = S.bricks_near_third(c)
+        assert near != "below" or c.route[1] is None or c.route[1] in ("flag", "empty tile")
+        assert near != "at_above" or c.route[1] is not None
+    # every part of a seed holds separable cases (each part asserts a non-zero default-versus-exact difference of its own)
+    for seed in S.BRICKS_SEEDS:
+        for part in range(S.PARTS):
+            assert sum(c.route[1] is None for c in S.bricks_cases(seed)[part::S.PARTS]) >= 5
+    a, b = S.bricks_cases(S.BRICKS_SEEDS[0]), S.bricks_cases(S.BRICKS_SEEDS[0])
+    assert all((x.bricks == y.bricks).all() and x.den == y.den and x.bands == y.bands for x, y in zip(a, b))
+
+
+def test_bricks_sweep_host_evaluator_within_the_bound(ora, gold):
+    """The CPU precondition of tests/test_gpu_bricks_far.py on the drawn cases: libwnoise_host.so's exact evaluator stays
+    well inside 1e-5 of the float64 reference at every in-range sample, so a GPU failure is a finding about a kernel."""
+    import test_gpu_bricks_far as bf
+    import test_gpu_dispatch as td
+    coefs = {"t128": ora.tile3d(128, 12345), "t32": ora.tile3d(32, td.SEED32), "t8": gold["tile3d_8_7"], "t6": gold["tile3d_5odd_11"],
+             "empty": np.empty(0, np.float32)}
+    host = bf.tf.Host()
+    worst = 0.0
+    for seed in S.BRICKS_SEEDS:
+        for c in S.bricks_cases(seed):
+            pts = bf.sample_points(c, c.bricks[bf.in_range(c.bricks, c)])
+            worst = max(worst, float(np.abs(bf.host_exact(host, coefs[c.tile], c, pts) - bf.ref64(coefs[c.tile], c, pts)).max()))
+    print(f"bricks sweep: largest |host exact - ref64| {worst:.3e}")
+    assert worst <= bf.TOL / 4
 
 
 def test_the_mirrored_constants_are_those_of_the_sources():
@@ -429,3 +477,22 @@ def test_multiband2d_sweep(nm, mb2d, part):
         assert same.all(), (S.describe(c), cus, int((~same).sum()), idx[np.argwhere(~same)[:5, 0]].tolist())
         assert np.ptp(got[0]) > 0.0
         print(f"sweep {c.name} {c.nx}x{c.ny} trips {S.mb2d_trips(c, cus)} bands {c.nbands} compared {idx.size}")
+
+
+# ---- brick lists ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("part", range(S.PARTS))
+@pytest.mark.parametrize("seed", S.BRICKS_SEEDS)
+def test_bricks_sweep(wn, tiles, seed, part):
+    """The checks of tests/test_gpu_bricks_far.py (check_case) on the drawn lists: the frame, the exact tier's bits against the
+    point entry, the default tier within 1e-5 of the float64 reference and of the exact tier, the route by bits, and the
+    first in-range brick alone."""
+    import test_gpu_bricks_far as bf
+    env = bf.Env(wn, tiles)
+    worst = 0.0
+    for c in S.bricks_cases(seed)[part::S.PARTS]:
+        e_fr, e_er, e_fe = bf.check_case(env, c, c.route)
+        if c.route[1] is None:
+            worst = max(worst, e_fe)
+    print(f"bricks sweep seed {seed} part {part}: largest |default - exact| {worst:.3e}")
+    assert 0.0 < worst <= bf.TOL
