@@ -11,7 +11,8 @@
 #include <cstdint>
 #include <cstdio>
 
-#include "wn_eval.hpp" // dmod, pow2_mask, bspline and the exact evaluators, shared with host/scalar_eval.cpp
+#include "wn_advect.hpp" // a particle's trace and its chain of launches, shared with host/scalar_eval.cpp
+#include "wn_eval.hpp"   // dmod, pow2_mask, bspline and the exact evaluators, shared with host/scalar_eval.cpp
 #include "wnoise.h"
 #include "wnoise_advect.h"
 
@@ -196,8 +197,21 @@ inline int curl_eval_args(const wn_tile *tile, const int32_t *offsets9_host, con
     return WN_OK;
 }
 
-// The checks of an advection call's wn_advect (wn_wavelet_advect.hip, wn_perlin_advect.hip) or wn_advect2d
-// (wn_wavelet_curl2d.hip): the same fields, a drift of three or two components.
+// f(PADDED, MB) as std::bool_constant for the four forms of a kernel that evaluates a CurlEval: the tile's padded copy or
+// its linear one, WMultibandNoise potentials or evaluate3D's.
+template <typename F>
+inline void with_curl_form(const wn_tile *tile, const CurlEval &e, const F &f)
+{
+    if (e.mb) {
+        if (tile->dev_padded) f(std::true_type{}, std::true_type{});
+        else f(std::false_type{}, std::true_type{});
+    } else {
+        if (tile->dev_padded) f(std::true_type{}, std::false_type{});
+        else f(std::false_type{}, std::false_type{});
+    }
+}
+
+// The checks of an advection call's wn_advect or wn_advect2d: the same fields, a drift of three or two components.
 template <typename A>
 inline int check_advect(const A *a)
 {
@@ -209,6 +223,21 @@ inline int check_advect(const A *a)
     bool finite = std::isfinite(a->h) && std::isfinite(a->gain);
     for (const float d : a->drift) finite = finite && std::isfinite(d);
     if (!finite) return fail(WN_ERR_INVALID, "wn_advect.h, gain and drift must be finite");
+    return WN_OK;
+}
+
+// The checks of an advection call's three buffers of n particles of D components of T, after check_advect; in_name and
+// out_name are the entry point's parameter names.  out may be in itself, and may not overlap it otherwise.
+template <typename T, int D>
+inline int check_advect_buffers(const T *in_dev, const T *out_dev, const T *traj_dev, size_t n, int traj_every,
+                                const char *in_name, const char *out_name)
+{
+    if (!in_dev || !out_dev) return fail(WN_ERR_INVALID, "%s / %s is NULL", in_name, out_name);
+    if (traj_every && !traj_dev) return fail(WN_ERR_INVALID, "traj_dev is NULL with traj_every = %d", traj_every);
+    const uintptr_t in_b = reinterpret_cast<uintptr_t>(in_dev), out_b = reinterpret_cast<uintptr_t>(out_dev);
+    const size_t bytes = D * n * sizeof(T);
+    if (in_b != out_b && in_b < out_b + bytes && out_b < in_b + bytes)
+        return fail(WN_ERR_INVALID, "%s overlaps %s without being equal to it", out_name, in_name);
     return WN_OK;
 }
 

@@ -1,8 +1,8 @@
 // wn_perlin_advect.hip -- particles moved through the curl noise of Perlin noise potentials (include/wnoise_perlin_advect.h).
 //
 // The velocity is wn_perlin_curl.hip's point evaluator, wn::perlin_curl_exact / perlin_turb_curl / perlin_fractal_curl; the
-// time step is wn::advect_step<METHOD, 3, double> (wn_eval.hpp), stated once for this kernel, for the wavelet kernel
-// (wn_wavelet_advect.hip, in float) and for the host's wnhost_perlin_curl_advect.
+// trace of a particle through a launch (wn::advect_trace, in double) and the chain of launches of a call (wn::advect_chain)
+// are wn_advect.hpp's, stated once for every advection kernel and for the host's wnhost_perlin_curl_advect.
 //
 //   perlin_curl_advect_kernel<KIND, METHOD>   one particle per lane in a grid-stride loop: the permutation table is staged
 //                                             in LDS (512 bytes), the position is loaded once, the steps of the launch run
@@ -12,9 +12,7 @@
 //                                             evaluator, as wn_perlin_curl_points_vec3 is given it.  No LDS beyond the
 //                                             table, no private segment.
 //
-// A launch integrates at most launch_steps() steps; a longer trace is a chain of launches on the stream, each reading the
-// positions the one before wrote to xyz_out_dev.  A position crosses a launch boundary as the three doubles it is, so the
-// bits do not depend on where the boundaries fall.
+// A launch integrates at most launch_steps() steps; a longer trace is a chain of launches on the stream.
 #include "wn_perlin_frame.hpp"
 #include "wnoise_perlin_advect.h"
 
@@ -38,27 +36,17 @@ static_assert(WN_PERLIN_CURL_NOISE == kNoise && WN_PERLIN_CURL_TURB == kTurb && 
 // launch's does.  A launch boundary costs one 48-byte position round trip per particle, about 0.1 ms on that list.
 constexpr int kPerlinAdvectOctaveBudget = 112;
 
-int stages_of(int method) { return method == WN_ADVECT_EULER ? 1 : (method == WN_ADVECT_MIDPOINT ? 2 : 4); }
-
 int launch_steps(int kind, int depth, int method)
 {
     const long long octaves = kind == kNoise ? 1 : (kind == kTurb ? std::max(depth, 1) : wn::kFractalOctaves);
-    return (int)std::max(1LL, kPerlinAdvectOctaveBudget / (stages_of(method) * octaves));
+    return (int)std::max(1LL, kPerlinAdvectOctaveBudget / (wn::advect_stages(method) * octaves));
 }
 
 struct PerlinAdvectArgs {
     const uint8_t *perm;
-    const double *in; // xyz interleaved
-    double *out;      // the positions after this launch's steps
-    double *snap;     // every != 0: the first snapshot this launch writes
-    size_t count;
-    int off[9];       // (x, y, z) of psi0, psi1, psi2, each in 0..255
-    int depth;        // TURB
-    int nsteps;       // of this launch
-    int every;        // 0: no trajectory
-    int until;        // steps until the next snapshot, in 1..every
-    int snap_input;   // the launch stores its input as a snapshot first (the call's snapshot 0)
-    double h, h2, h6, gain, drift[3];
+    int off[9]; // (x, y, z) of psi0, psi1, psi2, each in 0..255
+    int depth;  // TURB
+    wn::AdvectTrace<double, 3> t; // xyz interleaved
 };
 
 // amdgpu_waves_per_eu(4): at least the 4 waves per SIMD perlin_curl_points_kernel runs at (121 VGPRs).  Left alone,
@@ -75,41 +63,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void p
         else if (KIND == kTurb) wn::perlin_turb_curl(perm, (float)q[0], (float)q[1], (float)q[2], a.depth, a.off, v);
         else wn::perlin_fractal_curl(perm, (float)q[0], (float)q[1], (float)q[2], a.off, v);
     };
-    const size_t snap_stride = 3 * a.count;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.count; i += (size_t)gridDim.x * blockDim.x) {
-        double p[3] = {a.in[3 * i], a.in[3 * i + 1], a.in[3 * i + 2]};
-        double *snap = a.snap + 3 * i; // not dereferenced unless every != 0
-        auto store = [&](double *dst) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.t.count; i += (size_t)gridDim.x * blockDim.x) {
+        double p[3] = {a.t.in[3 * i], a.t.in[3 * i + 1], a.t.in[3 * i + 2]};
+        wn::advect_trace<METHOD>(a.t, p, 3 * i, velocity, [&](double *dst) {
             dst[0] = p[0];
             dst[1] = p[1];
             dst[2] = p[2];
-        };
-        if (a.snap_input) {
-            store(snap);
-            snap += snap_stride;
-        }
-        int until = a.until;
-#pragma unroll 1
-        for (int t = 0; t < a.nsteps; ++t) {
-            wn::advect_step<METHOD, 3, double>(p, a.h, a.h2, a.h6, a.gain, a.drift, velocity);
-            if (a.every && --until == 0) {
-                store(snap);
-                snap += snap_stride;
-                until = a.every;
-            }
-        }
-        store(a.out + 3 * i);
+        });
     }
-}
-
-template <int KIND>
-void launch_method(int method, dim3 grid, hipStream_t stream, const PerlinAdvectArgs &a)
-{
-    const dim3 block(256);
-    if (method == WN_ADVECT_EULER) hipLaunchKernelGGL((perlin_curl_advect_kernel<KIND, WN_ADVECT_EULER>), grid, block, 0, stream, a);
-    else if (method == WN_ADVECT_MIDPOINT)
-        hipLaunchKernelGGL((perlin_curl_advect_kernel<KIND, WN_ADVECT_MIDPOINT>), grid, block, 0, stream, a);
-    else hipLaunchKernelGGL((perlin_curl_advect_kernel<KIND, WN_ADVECT_RK4>), grid, block, 0, stream, a);
 }
 
 int advect_points(const wn_perm *perm, const double *in_dev, size_t n, int kind, int depth, const int32_t *offsets9_host,
@@ -122,43 +83,28 @@ int advect_points(const wn_perm *perm, const double *in_dev, size_t n, int kind,
     if (rc) return rc;
     rc = wn::check_advect(adv);
     if (rc || n == 0) return rc;
-    if (!in_dev || !out_dev) return wn::fail(WN_ERR_INVALID, "xyz_in_dev / xyz_out_dev is NULL");
     if (!offsets9_host) return wn::fail(WN_ERR_INVALID, "offsets9_host is NULL");
-    const int every = adv->traj_every;
-    if (every && !traj_dev) return wn::fail(WN_ERR_INVALID, "traj_dev is NULL with traj_every = %d", every);
-    const uintptr_t in_b = reinterpret_cast<uintptr_t>(in_dev), out_b = reinterpret_cast<uintptr_t>(out_dev);
-    const size_t bytes = 3 * n * sizeof(double);
-    if (in_b != out_b && in_b < out_b + bytes && out_b < in_b + bytes)
-        return wn::fail(WN_ERR_INVALID, "xyz_out_dev overlaps xyz_in_dev without being equal to it");
+    rc = wn::check_advect_buffers<double, 3>(in_dev, out_dev, traj_dev, n, adv->traj_every, "xyz_in_dev", "xyz_out_dev");
+    if (rc) return rc;
 
     PerlinAdvectArgs a{};
     a.perm = perm->dev;
-    a.out = out_dev;
-    a.count = n;
     for (int i = 0; i < 9; ++i) a.off[i] = offsets9_host[i] & 255;
     a.depth = depth;
-    a.every = every;
-    a.h = (double)adv->h;
-    a.h2 = 0.5 * (double)adv->h;
-    a.h6 = (double)adv->h / 6.0;
-    a.gain = (double)adv->gain;
-    for (int c = 0; c < 3; ++c) a.drift[c] = (double)adv->drift[c];
-    const int per_launch = launch_steps(kind, depth, adv->method);
-    int done = 0;
-    do { // steps == 0: one launch, which copies the input
-        a.in = done ? out_dev : in_dev;
-        a.nsteps = std::min(per_launch, adv->steps - done);
-        a.snap_input = every && done == 0;
-        a.until = every ? every - done % every : 0;
-        // snapshot done / every is written (the input, or by the launch before this one); the next one is this launch's
-        a.snap = every ? traj_dev + (size_t)(done / every + (done ? 1 : 0)) * 3 * n : nullptr;
-        if (kind == kNoise) launch_method<kNoise>(adv->method, dim3(wn::stride_blocks(n)), stream, a);
-        else if (kind == kTurb) launch_method<kTurb>(adv->method, dim3(wn::stride_blocks(n)), stream, a);
-        else launch_method<kFractal>(adv->method, dim3(wn::stride_blocks(n)), stream, a);
+    const dim3 grid = dim3(wn::stride_blocks(n)), block(256);
+    const auto launch_one = [&](const wn::AdvectTrace<double, 3> &t) -> int {
+        a.t = t;
+        wn::with_advect_method(adv->method, [&](auto method) {
+            constexpr int kMethod = decltype(method)::value;
+            if (kind == kNoise) hipLaunchKernelGGL((perlin_curl_advect_kernel<kNoise, kMethod>), grid, block, 0, stream, a);
+            else if (kind == kTurb) hipLaunchKernelGGL((perlin_curl_advect_kernel<kTurb, kMethod>), grid, block, 0, stream, a);
+            else hipLaunchKernelGGL((perlin_curl_advect_kernel<kFractal, kMethod>), grid, block, 0, stream, a);
+        });
         WN_LAUNCH_CHECK("perlin_curl_advect_kernel");
-        done += a.nsteps;
-    } while (done < adv->steps);
-    return WN_OK;
+        return WN_OK;
+    };
+    return wn::advect_chain(wn::advect_trace_fill<double, 3>(*adv, n), in_dev, out_dev, traj_dev, adv->steps,
+                            launch_steps(kind, depth, adv->method), launch_one);
 }
 
 } // namespace

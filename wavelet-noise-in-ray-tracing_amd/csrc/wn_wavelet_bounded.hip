@@ -2,11 +2,12 @@
 // particle advection (include/wnoise_bounded.h).
 //
 // The velocity is wn::eval3d_curl_bounded_exact / multiband_curl_bounded_exact (wn_eval.hpp), stated once for these kernels
-// and for the host's wnhost_eval3d_curl_bounded; the time step is wn::advect_step, as in wn_wavelet_advect.hip.
+// and for the host's wnhost_eval3d_curl_bounded; a particle's trace through a launch and the chain of launches are
+// wn_advect.hpp's (wn::advect_trace, wn::advect_chain).
 //
 //   curl3d_bounded_points_kernel<PADDED, MB>          one point per lane in a grid-stride loop, records {vx, vy, vz}.
 //   curl3d_bounded_advect_kernel<PADDED, MB, METHOD>  one particle per lane in a grid-stride loop; position, stage point and
-//                                                     RK4's running sum in registers, as curl3d_advect_kernel.
+//                                                     RK4's running sum in registers.
 //
 // The obstacle list travels by value in the launch arguments (16 x 32 bytes): it is the same for every lane, so the
 // obstacle loop reads it with scalar loads and branches on the kind as a wave.  A lane that is far from every obstacle
@@ -14,8 +15,8 @@
 // values (the rows are in cache, the bits are those of one pass), so the far path keeps the unbounded kernel's live set;
 // an inside lane evaluates nothing.  No LDS, no private segment.
 //
-// Launch chaining is wn_wavelet_advect.hip's: a launch integrates at most wn_advect_launch_steps() steps, a longer trace is
-// a chain of launches on the stream, and a position crosses a launch boundary as the three floats it is.
+// A launch integrates at most wn_advect_launch_steps() steps, the cap wn_wavelet_advect.hip measured; a longer trace is a
+// chain of launches on the stream.
 #include "wn_internal.hpp"
 #include "wnoise_bounded.h"
 
@@ -46,15 +47,10 @@ struct BoundedPointsArgs {
     size_t count;
 };
 
-struct BoundedAdvectArgs { // AdvectArgs of wn_wavelet_advect.hip, and the obstacles
+struct BoundedAdvectArgs {
     CurlEval e;
     Obstacles o;
-    const float *in;
-    float *out;
-    float *snap;
-    size_t count;
-    int nsteps, every, until, snap_input;
-    float h, h2, h6, gain, drift[3];
+    wn::AdvectTrace<float, 3> t; // xyz interleaved
 };
 
 template <bool PADDED, bool MB>
@@ -81,30 +77,13 @@ template <bool PADDED, bool MB, int METHOD>
 __global__ __launch_bounds__(256) void curl3d_bounded_advect_kernel(const BoundedAdvectArgs a)
 {
     const auto velocity = [&](const float q[3], float v[3]) { bounded_velocity_at<PADDED, MB>(a.e, a.o, q, v); };
-    const size_t snap_stride = 3 * a.count;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.count; i += (size_t)gridDim.x * blockDim.x) {
-        float p[3] = {a.in[3 * i], a.in[3 * i + 1], a.in[3 * i + 2]};
-        float *snap = a.snap + 3 * i; // not dereferenced unless every != 0
-        auto store = [&](float *dst) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.t.count; i += (size_t)gridDim.x * blockDim.x) {
+        float p[3] = {a.t.in[3 * i], a.t.in[3 * i + 1], a.t.in[3 * i + 2]};
+        wn::advect_trace<METHOD>(a.t, p, 3 * i, velocity, [&](float *dst) {
             dst[0] = p[0];
             dst[1] = p[1];
             dst[2] = p[2];
-        };
-        if (a.snap_input) {
-            store(snap);
-            snap += snap_stride;
-        }
-        int until = a.until;
-#pragma unroll 1
-        for (int t = 0; t < a.nsteps; ++t) {
-            wn::advect_step<METHOD>(p, a.h, a.h2, a.h6, a.gain, a.drift, velocity);
-            if (a.every && --until == 0) {
-                store(snap);
-                snap += snap_stride;
-                until = a.every;
-            }
-        }
-        store(a.out + 3 * i);
+        });
     }
 }
 
@@ -123,77 +102,38 @@ int launch_bounded_points(const wn_tile *tile, const CurlEval &e, const Obstacle
     if (!xyz_dev || !out3_dev) return wn::fail(WN_ERR_INVALID, "points/out pointer is NULL");
     const BoundedPointsArgs a{e, o, xyz_dev, out3_dev, n};
     const dim3 grid(wn::stride_blocks(n, kBoundedBlockCap)), block(256);
-    const bool padded = tile->dev_padded != nullptr;
-    if (e.mb) {
-        if (padded) hipLaunchKernelGGL((curl3d_bounded_points_kernel<true, true>), grid, block, 0, stream, a);
-        else hipLaunchKernelGGL((curl3d_bounded_points_kernel<false, true>), grid, block, 0, stream, a);
-    } else {
-        if (padded) hipLaunchKernelGGL((curl3d_bounded_points_kernel<true, false>), grid, block, 0, stream, a);
-        else hipLaunchKernelGGL((curl3d_bounded_points_kernel<false, false>), grid, block, 0, stream, a);
-    }
+    wn::with_curl_form(tile, e, [&](auto padded, auto mb) {
+        hipLaunchKernelGGL((curl3d_bounded_points_kernel<decltype(padded)::value, decltype(mb)::value>), grid, block, 0, stream,
+                           a);
+    });
     WN_LAUNCH_CHECK("curl3d_bounded_points_kernel");
     return WN_OK;
 }
 
-template <bool PADDED, bool MB>
-void launch_method(int method, dim3 grid, hipStream_t stream, const BoundedAdvectArgs &a)
-{
-    const dim3 block(256);
-    if (method == WN_ADVECT_EULER)
-        hipLaunchKernelGGL((curl3d_bounded_advect_kernel<PADDED, MB, WN_ADVECT_EULER>), grid, block, 0, stream, a);
-    else if (method == WN_ADVECT_MIDPOINT)
-        hipLaunchKernelGGL((curl3d_bounded_advect_kernel<PADDED, MB, WN_ADVECT_MIDPOINT>), grid, block, 0, stream, a);
-    else hipLaunchKernelGGL((curl3d_bounded_advect_kernel<PADDED, MB, WN_ADVECT_RK4>), grid, block, 0, stream, a);
-}
-
-// The entry points after their tile, offset, band and obstacle checks: the checks of `a` and of the three buffers, then the
-// chain of launches, both as wn_wavelet_advect.hip's advect_points.
+// The entry points after their tile, offset, band and obstacle checks: the checks of `adv` and of the three buffers, then
+// the chain of launches, each of at most wn_advect_launch_steps() steps.
 int bounded_advect_points(const wn_tile *tile, const CurlEval &e, const Obstacles &o, const float *in_dev, size_t n,
                           const wn_advect *adv, float *out_dev, float *traj_dev, hipStream_t stream)
 {
-    const int rc = wn::check_advect(adv);
+    int rc = wn::check_advect(adv);
     if (rc || n == 0) return rc;
-    if (!in_dev || !out_dev) return wn::fail(WN_ERR_INVALID, "xyz_in_dev / xyz_out_dev is NULL");
-    const int every = adv->traj_every;
-    if (every && !traj_dev) return wn::fail(WN_ERR_INVALID, "traj_dev is NULL with traj_every = %d", every);
-    const uintptr_t in_b = reinterpret_cast<uintptr_t>(in_dev), out_b = reinterpret_cast<uintptr_t>(out_dev);
-    const size_t bytes = 3 * n * sizeof(float);
-    if (in_b != out_b && in_b < out_b + bytes && out_b < in_b + bytes)
-        return wn::fail(WN_ERR_INVALID, "xyz_out_dev overlaps xyz_in_dev without being equal to it");
-
-    BoundedAdvectArgs a{};
-    a.e = e;
-    a.o = o;
-    a.out = out_dev;
-    a.count = n;
-    a.every = every;
-    a.h = adv->h;
-    a.h2 = 0.5f * adv->h;
-    a.h6 = adv->h / 6.0f;
-    a.gain = adv->gain;
-    std::copy(adv->drift, adv->drift + 3, a.drift);
-    const dim3 grid(wn::stride_blocks(n, kBoundedBlockCap));
-    const bool padded = tile->dev_padded != nullptr;
-    const int launch_steps = wn_advect_launch_steps();
-    int done = 0;
-    do { // steps == 0: one launch, which copies the input
-        a.in = done ? out_dev : in_dev;
-        a.nsteps = std::min(launch_steps, adv->steps - done);
-        a.snap_input = every && done == 0;
-        a.until = every ? every - done % every : 0;
-        // snapshot done / every is written (the input, or by the launch before this one); the next one is this launch's
-        a.snap = every ? traj_dev + (size_t)(done / every + (done ? 1 : 0)) * 3 * n : nullptr;
-        if (e.mb) {
-            if (padded) launch_method<true, true>(adv->method, grid, stream, a);
-            else launch_method<false, true>(adv->method, grid, stream, a);
-        } else {
-            if (padded) launch_method<true, false>(adv->method, grid, stream, a);
-            else launch_method<false, false>(adv->method, grid, stream, a);
-        }
+    rc = wn::check_advect_buffers<float, 3>(in_dev, out_dev, traj_dev, n, adv->traj_every, "xyz_in_dev", "xyz_out_dev");
+    if (rc) return rc;
+    const dim3 grid(wn::stride_blocks(n, kBoundedBlockCap)), block(256);
+    const auto launch_one = [&](const wn::AdvectTrace<float, 3> &t) -> int {
+        const BoundedAdvectArgs a{e, o, t};
+        wn::with_curl_form(tile, e, [&](auto padded, auto mb) {
+            wn::with_advect_method(adv->method, [&](auto method) {
+                constexpr bool kPadded = decltype(padded)::value, kMb = decltype(mb)::value;
+                hipLaunchKernelGGL((curl3d_bounded_advect_kernel<kPadded, kMb, decltype(method)::value>), grid, block, 0, stream,
+                                   a);
+            });
+        });
         WN_LAUNCH_CHECK("curl3d_bounded_advect_kernel");
-        done += a.nsteps;
-    } while (done < adv->steps);
-    return WN_OK;
+        return WN_OK;
+    };
+    return wn::advect_chain(wn::advect_trace_fill<float, 3>(*adv, n), in_dev, out_dev, traj_dev, adv->steps,
+                            wn_advect_launch_steps(), launch_one);
 }
 
 } // namespace

@@ -2,8 +2,8 @@
 // lattices and under particle advection (include/wnoise_bounded2d.h).
 //
 // The velocity is wn::obstacle_ramp<2> followed by wn::multiband2d_curl_bounded_at (wn_eval.hpp), stated once for these
-// kernels and for the host's wnhost_multiband2d_curl_bounded; the time step is wn::advect_step<METHOD, 2>, as in
-// wn_wavelet_curl2d.hip, whose kernels these mirror:
+// kernels and for the host's wnhost_multiband2d_curl_bounded; a particle's trace through a launch and the chain of launches
+// are wn_advect.hpp's (wn::advect_trace, wn::advect_chain).  The kernels mirror wn_wavelet_curl2d.hip's:
 //
 //   curl2d_bounded_grid_kernel<LDS>            one sample per lane, the lattice walk of curl2d_grid_kernel; two planes.
 //   curl2d_bounded_points_kernel<LDS>          one point per lane, grid-stride; records {vx, vy}.
@@ -83,16 +83,12 @@ struct Bounded2dArgs : wn::FootprintBands { // Curl2dArgs of wn_wavelet_curl2d.h
     Bounds2d b;
 };
 
-struct BoundedAdvect2dArgs : wn::FootprintBands { // Advect2dArgs of wn_wavelet_curl2d.hip, and the bounds
+struct BoundedAdvect2dArgs : wn::FootprintBands {
     const float *coef;
     int n, nmask;
     float s;
-    const float *in;
-    float *out;
-    float *snap;
-    size_t count;
-    int nsteps, every, until, snap_input;
-    float h, h2, h6, gain, drift[2];
+    size_t count;                // of t: what launch() sizes the grid by
+    wn::AdvectTrace<float, 2> t; // xy interleaved
     Bounds2d b;
 };
 
@@ -172,34 +168,17 @@ __global__ __launch_bounds__(kWorkgroup, kWavesPerSimd) void curl2d_bounded_adve
     if constexpr (LDS) wn::stage_tile<kWorkgroup>(tile_lds, a.coef, a.n);
     const float *coef = LDS ? tile_lds : a.coef;
     const auto velocity = [&](const float q[2], float v[2]) { bounded_velocity_at<LDS>(a, coef, q, v); };
-    const size_t snap_stride = 2 * a.count;
     // The span's base and the snapshot's plane are the same for every lane (scalar registers); a lane keeps its position
     // alone across the steps and forms its addresses where it stores.
-    for (size_t base = (size_t)blockIdx.x * kWorkgroup; base < a.count; base += (size_t)gridDim.x * kWorkgroup) {
-        if (base + threadIdx.x >= a.count) continue;
-        float p[2] = {a.in[2 * (base + threadIdx.x)], a.in[2 * (base + threadIdx.x) + 1]};
-        float *plane = a.snap + 2 * base; // not dereferenced unless every != 0
-        auto store = [&](float *dst) {
+    for (size_t base = (size_t)blockIdx.x * kWorkgroup; base < a.t.count; base += (size_t)gridDim.x * kWorkgroup) {
+        if (base + threadIdx.x >= a.t.count) continue;
+        float p[2] = {a.t.in[2 * (base + threadIdx.x)], a.t.in[2 * (base + threadIdx.x) + 1]};
+        wn::advect_trace<METHOD>(a.t, p, 2 * base, velocity, [&](float *dst) {
             unsigned lane = threadIdx.x;
             asm volatile("" : "+v"(lane)); // the lane's address is formed here, not kept in registers across the steps
             dst[2 * lane] = p[0];
             dst[2 * lane + 1] = p[1];
-        };
-        if (a.snap_input) {
-            store(plane);
-            plane += snap_stride;
-        }
-        int until = a.until;
-#pragma unroll 1
-        for (int t = 0; t < a.nsteps; ++t) {
-            wn::advect_step<METHOD, 2>(p, a.h, a.h2, a.h6, a.gain, a.drift, velocity);
-            if (a.every && --until == 0) {
-                store(plane);
-                plane += snap_stride;
-                until = a.every;
-            }
-        }
-        store(a.out + 2 * base);
+        });
     }
 }
 
@@ -260,13 +239,6 @@ int bounds_args(const char *entry, const wn_obstacle2d *obstacles_host, int nobs
 
 bool unbounded(const Bounds2d &b) { return b.nobs == 0 && !b.has_flow; }
 
-template <int METHOD>
-int launch_advect(size_t lds, const BoundedAdvect2dArgs &a, hipStream_t stream)
-{
-    return launch(curl2d_bounded_advect_kernel<METHOD, true>, curl2d_bounded_advect_kernel<METHOD, false>, lds, a,
-                  "curl2d_bounded_advect_kernel", stream);
-}
-
 } // namespace
 
 extern "C" {
@@ -323,50 +295,28 @@ int wn_multiband2d_curl_bounded_advect_points(const wn_tile *tile, const float *
     BoundedAdvect2dArgs a{};
     int rc = common_args(entry, tile, first_band, nbands, w_host, var_per_band, s, &a);
     if (rc) return rc;
-    // `a`, the three buffers and the chain of launches as wn_multiband2d_curl_advect_points
     rc = wn::check_advect(adv);
     if (rc) return rc;
-    const int every = adv->traj_every;
-    if (n) {
-        if (!xy_in_dev || !xy_out_dev) return wn::fail(WN_ERR_INVALID, "xy_in_dev / xy_out_dev is NULL");
-        if (every && !traj_dev) return wn::fail(WN_ERR_INVALID, "traj_dev is NULL with traj_every = %d", every);
-        const uintptr_t in_b = reinterpret_cast<uintptr_t>(xy_in_dev), out_b = reinterpret_cast<uintptr_t>(xy_out_dev);
-        const size_t bytes = 2 * n * sizeof(float);
-        if (in_b != out_b && in_b < out_b + bytes && out_b < in_b + bytes)
-            return wn::fail(WN_ERR_INVALID, "xy_out_dev overlaps xy_in_dev without being equal to it");
-    }
+    if (n) rc = wn::check_advect_buffers<float, 2>(xy_in_dev, xy_out_dev, traj_dev, n, adv->traj_every, "xy_in_dev", "xy_out_dev");
+    if (rc) return rc;
     rc = bounds_args(entry, obstacles_host, nobs, flow2_host, &a.b);
     if (rc || n == 0) return rc;
     if (unbounded(a.b))
         return wn_multiband2d_curl_advect_points(tile, xy_in_dev, n, s, first_band, nbands, w_host, var_per_band, adv,
                                                  xy_out_dev, traj_dev, stream);
 
-    a.out = xy_out_dev;
     a.count = n;
-    a.every = every;
-    a.h = adv->h;
-    a.h2 = 0.5f * adv->h;
-    a.h6 = adv->h / 6.0f;
-    a.gain = adv->gain;
-    std::copy(adv->drift, adv->drift + 2, a.drift);
     const size_t lds = n >= kAdvectLdsMinPoints ? lds_tile_bytes(a.n) : 0;
-    const int per_launch = wn_advect2d_launch_steps(adv->method, nbands);
-    const hipStream_t st = wn::as_stream(stream);
-    int done = 0;
-    do { // steps == 0: one launch, which copies the input
-        a.in = done ? xy_out_dev : xy_in_dev;
-        a.nsteps = std::min(per_launch, adv->steps - done);
-        a.snap_input = every && done == 0;
-        a.until = every ? every - done % every : 0;
-        // snapshot done / every is written (the input, or by the launch before this one); the next one is this launch's
-        a.snap = every ? traj_dev + (size_t)(done / every + (done ? 1 : 0)) * 2 * n : nullptr;
-        rc = adv->method == WN_ADVECT_EULER      ? launch_advect<WN_ADVECT_EULER>(lds, a, st)
-             : adv->method == WN_ADVECT_MIDPOINT ? launch_advect<WN_ADVECT_MIDPOINT>(lds, a, st)
-                                                 : launch_advect<WN_ADVECT_RK4>(lds, a, st);
-        if (rc) return rc;
-        done += a.nsteps;
-    } while (done < adv->steps);
-    return WN_OK;
+    const auto launch_one = [&](const wn::AdvectTrace<float, 2> &t) {
+        a.t = t;
+        return wn::with_advect_method(adv->method, [&](auto method) {
+            constexpr int kMethod = decltype(method)::value;
+            return launch(curl2d_bounded_advect_kernel<kMethod, true>, curl2d_bounded_advect_kernel<kMethod, false>, lds, a,
+                          "curl2d_bounded_advect_kernel", wn::as_stream(stream));
+        });
+    };
+    return wn::advect_chain(wn::advect_trace_fill<float, 2>(*adv, n), xy_in_dev, xy_out_dev, traj_dev, adv->steps,
+                            wn_advect2d_launch_steps(adv->method, nbands), launch_one);
 }
 
 } // extern "C"

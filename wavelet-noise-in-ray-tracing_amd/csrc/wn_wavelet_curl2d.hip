@@ -1,8 +1,8 @@
 // wn_wavelet_curl2d.hip -- divergence-free curl noise on a 2-D tile and particles moved through it
 // (include/wnoise_curl2d.h).  The velocity at a point is one call of wn::multiband2d_curl_exact (wn_eval.hpp): the gradient
-// channels of wn_wavelet_multiband2d.hip's evaluator at the call's footprint, rotated; the time step is wn::advect_step
-// <METHOD, 2>, the step of wn_wavelet_advect.hip in two dimensions.  The host's wnhost_multiband2d_curl and
-// wnhost_multiband2d_curl_advect compile both too: the same bits.
+// channels of wn_wavelet_multiband2d.hip's evaluator at the call's footprint, rotated; the trace of a particle through a
+// launch and the chain of launches of a call are wn_advect.hpp's (wn::advect_trace, wn::advect_chain), in two dimensions.
+// The host's wnhost_multiband2d_curl and wnhost_multiband2d_curl_advect compile both too: the same bits.
 //
 //   curl2d_grid_kernel<LDS>            one sample per lane; a workgroup walks spans of kWorkgroup samples (the lattice
 //                                      walk of multiband2d_grid_kernel); two planes, vx and vy.
@@ -97,15 +97,8 @@ struct Advect2dArgs : wn::FootprintBands {
     const float *coef;
     int n, nmask;
     float s;
-    const float *in; // xy interleaved
-    float *out;      // the positions after this launch's steps
-    float *snap;     // every != 0: the first snapshot this launch writes
-    size_t count;
-    int nsteps;      // of this launch
-    int every;       // 0: no trajectory
-    int until;       // steps until the next snapshot, in 1..every
-    int snap_input;  // the launch stores its input as a snapshot first (the call's snapshot 0)
-    float h, h2, h6, gain, drift[2];
+    size_t count;                // of t: what launch() sizes the grid by
+    wn::AdvectTrace<float, 2> t; // xy interleaved
 };
 
 template <bool LDS>
@@ -174,29 +167,12 @@ __global__ __launch_bounds__(kWorkgroup, kWavesPerSimd) void curl2d_advect_kerne
     if constexpr (LDS) wn::stage_tile<kWorkgroup>(tile_lds, a.coef, a.n);
     const float *coef = LDS ? tile_lds : a.coef;
     const auto velocity = [&](const float q[2], float v[2]) { wn::multiband2d_curl_exact<LDS>(a, coef, q, a.s, v); };
-    const size_t snap_stride = 2 * a.count;
-    for (size_t i = (size_t)blockIdx.x * kWorkgroup + threadIdx.x; i < a.count; i += (size_t)gridDim.x * kWorkgroup) {
-        float p[2] = {a.in[2 * i], a.in[2 * i + 1]};
-        float *snap = a.snap + 2 * i; // not dereferenced unless every != 0
-        auto store = [&](float *dst) {
+    for (size_t i = (size_t)blockIdx.x * kWorkgroup + threadIdx.x; i < a.t.count; i += (size_t)gridDim.x * kWorkgroup) {
+        float p[2] = {a.t.in[2 * i], a.t.in[2 * i + 1]};
+        wn::advect_trace<METHOD>(a.t, p, 2 * i, velocity, [&](float *dst) {
             dst[0] = p[0];
             dst[1] = p[1];
-        };
-        if (a.snap_input) {
-            store(snap);
-            snap += snap_stride;
-        }
-        int until = a.until;
-#pragma unroll 1
-        for (int t = 0; t < a.nsteps; ++t) {
-            wn::advect_step<METHOD, 2>(p, a.h, a.h2, a.h6, a.gain, a.drift, velocity);
-            if (a.every && --until == 0) {
-                store(snap);
-                snap += snap_stride;
-                until = a.every;
-            }
-        }
-        store(a.out + 2 * i);
+        });
     }
 }
 
@@ -241,19 +217,10 @@ int common_args(const char *entry, const wn_tile *tile, int first_band, int nban
     return WN_OK;
 }
 
-int stages_of(int method) { return method == WN_ADVECT_EULER ? 1 : (method == WN_ADVECT_MIDPOINT ? 2 : 4); }
-
 int launch_steps(int method, int nbands)
 {
     const int bands = std::min(std::max(nbands, 1), wn::kFootprintMaxBands);
-    return std::max(1, kAdvect2dLaunchEvals / (stages_of(method) * bands));
-}
-
-template <int METHOD>
-int launch_advect(size_t lds, const Advect2dArgs &a, hipStream_t stream)
-{
-    return launch(curl2d_advect_kernel<METHOD, true>, curl2d_advect_kernel<METHOD, false>, lds, a, "curl2d_advect_kernel",
-                  stream);
+    return std::max(1, kAdvect2dLaunchEvals / (wn::advect_stages(method) * bands));
 }
 
 } // namespace
@@ -300,43 +267,23 @@ int wn_multiband2d_curl_advect_points(const wn_tile *tile, const float *xy_in_de
     Advect2dArgs a{};
     int rc = common_args("wn_multiband2d_curl_advect_points", tile, first_band, nbands, w_host, var_per_band, s, &a);
     if (rc) return rc;
-    // `a`, the three buffers and the chain of launches as wn_eval3d_curl_advect_points
     rc = wn::check_advect(adv);
     if (rc || n == 0) return rc;
-    if (!xy_in_dev || !xy_out_dev) return wn::fail(WN_ERR_INVALID, "xy_in_dev / xy_out_dev is NULL");
-    const int every = adv->traj_every;
-    if (every && !traj_dev) return wn::fail(WN_ERR_INVALID, "traj_dev is NULL with traj_every = %d", every);
-    const uintptr_t in_b = reinterpret_cast<uintptr_t>(xy_in_dev), out_b = reinterpret_cast<uintptr_t>(xy_out_dev);
-    const size_t bytes = 2 * n * sizeof(float);
-    if (in_b != out_b && in_b < out_b + bytes && out_b < in_b + bytes)
-        return wn::fail(WN_ERR_INVALID, "xy_out_dev overlaps xy_in_dev without being equal to it");
+    rc = wn::check_advect_buffers<float, 2>(xy_in_dev, xy_out_dev, traj_dev, n, adv->traj_every, "xy_in_dev", "xy_out_dev");
+    if (rc) return rc;
 
-    a.out = xy_out_dev;
     a.count = n;
-    a.every = every;
-    a.h = adv->h;
-    a.h2 = 0.5f * adv->h;
-    a.h6 = adv->h / 6.0f;
-    a.gain = adv->gain;
-    std::copy(adv->drift, adv->drift + 2, a.drift);
     const size_t lds = n >= kAdvect2dLdsMinPoints ? lds_tile_bytes(a.n) : 0;
-    const int per_launch = launch_steps(adv->method, nbands);
-    const hipStream_t st = wn::as_stream(stream);
-    int done = 0;
-    do { // steps == 0: one launch, which copies the input
-        a.in = done ? xy_out_dev : xy_in_dev;
-        a.nsteps = std::min(per_launch, adv->steps - done);
-        a.snap_input = every && done == 0;
-        a.until = every ? every - done % every : 0;
-        // snapshot done / every is written (the input, or by the launch before this one); the next one is this launch's
-        a.snap = every ? traj_dev + (size_t)(done / every + (done ? 1 : 0)) * 2 * n : nullptr;
-        rc = adv->method == WN_ADVECT_EULER      ? launch_advect<WN_ADVECT_EULER>(lds, a, st)
-             : adv->method == WN_ADVECT_MIDPOINT ? launch_advect<WN_ADVECT_MIDPOINT>(lds, a, st)
-                                                 : launch_advect<WN_ADVECT_RK4>(lds, a, st);
-        if (rc) return rc;
-        done += a.nsteps;
-    } while (done < adv->steps);
-    return WN_OK;
+    const auto launch_one = [&](const wn::AdvectTrace<float, 2> &t) {
+        a.t = t;
+        return wn::with_advect_method(adv->method, [&](auto method) {
+            constexpr int kMethod = decltype(method)::value;
+            return launch(curl2d_advect_kernel<kMethod, true>, curl2d_advect_kernel<kMethod, false>, lds, a,
+                          "curl2d_advect_kernel", wn::as_stream(stream));
+        });
+    };
+    return wn::advect_chain(wn::advect_trace_fill<float, 2>(*adv, n), xy_in_dev, xy_out_dev, traj_dev, adv->steps,
+                            launch_steps(adv->method, nbands), launch_one);
 }
 
 int wn_advect2d_launch_steps(int method, int nbands) { return launch_steps(method, nbands); }

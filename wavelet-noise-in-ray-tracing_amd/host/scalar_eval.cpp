@@ -7,6 +7,7 @@
 #include <cmath>
 #include <cstdlib>
 
+#include "wn_advect.hpp"
 #include "wn_eval.hpp"
 #include "wnoise_advect.h"
 #include "wnoise_bounded.h"
@@ -40,6 +41,32 @@ bool footprint_setup(Footprint &a, const float *coef, int n, int first_band, int
     a.nmask = wn::pow2_mask(a.n);
     a.scale = 1.0;
     return true;
+}
+
+// false: a wn_advect / wn_advect2d that no trace can follow, or one that asks for a trajectory without a buffer for it
+template <typename A>
+bool advect_ok(const A *a, const void *traj)
+{
+    if (!a || a->method < WN_ADVECT_EULER || a->method > WN_ADVECT_RK4 || a->steps < 0 || a->traj_every < 0) return false;
+    bool finite = std::isfinite(a->h) && std::isfinite(a->gain);
+    for (const float d : a->drift) finite = finite && std::isfinite(d);
+    return finite && (!a->traj_every || traj);
+}
+
+// One particle's whole trace: the chain of wn_advect.hpp with a single launch of all the steps, on a list of one.
+template <typename T, int D, typename A, typename V>
+void advect_one(const A &a, const T *p_in, T *p_out, T *traj, const V &velocity)
+{
+    wn::advect_chain(wn::advect_trace_fill<T, D>(a, 1), p_in, p_out, traj, a.steps, a.steps, [&](const wn::AdvectTrace<T, D> &t) {
+        T p[D];
+        for (int c = 0; c < D; ++c) p[c] = t.in[c];
+        wn::with_advect_method(a.method, [&](auto method) {
+            wn::advect_trace<decltype(method)::value>(t, p, 0, velocity, [&](T *dst) {
+                for (int c = 0; c < D; ++c) dst[c] = p[c];
+            });
+        });
+        return 0;
+    });
 }
 
 } // namespace
@@ -104,10 +131,7 @@ int wnhost_eval3d_curl_bounded_advect(const float *coef, int n, const float p_in
                                       const wn_obstacle *obstacles, int nobs, const wn_advect *a, float p_out[3], float *traj)
 {
     if (wn::obstacle_fault(obstacles, nobs)) return 1;
-    if (!a || a->method < WN_ADVECT_EULER || a->method > WN_ADVECT_RK4 || a->steps < 0 || a->traj_every < 0) return 1;
-    if (!std::isfinite(a->h) || !std::isfinite(a->gain) || !std::isfinite(a->drift[0]) || !std::isfinite(a->drift[1]) ||
-        !std::isfinite(a->drift[2]) || (a->traj_every && !traj))
-        return 1;
+    if (!advect_ok(a, traj)) return 1;
     if (!coef || n <= 0) n = 0;
     const int nmask = wn::pow2_mask(n);
     int off[9];
@@ -115,19 +139,7 @@ int wnhost_eval3d_curl_bounded_advect(const float *coef, int n, const float p_in
     const auto velocity = [&](const float q[3], float v[3]) {
         wn::eval3d_curl_bounded_exact(coef, n, nmask, off, obstacles, nobs, q, v);
     };
-    const float h = a->h, h2 = 0.5f * a->h, h6 = a->h / 6.0f;
-    float p[3] = {p_in[0], p_in[1], p_in[2]};
-    if (a->traj_every) traj[0] = p[0], traj[1] = p[1], traj[2] = p[2];
-    for (int t = 1; t <= a->steps; ++t) {
-        if (a->method == WN_ADVECT_EULER) wn::advect_step<WN_ADVECT_EULER>(p, h, h2, h6, a->gain, a->drift, velocity);
-        else if (a->method == WN_ADVECT_MIDPOINT) wn::advect_step<WN_ADVECT_MIDPOINT>(p, h, h2, h6, a->gain, a->drift, velocity);
-        else wn::advect_step<WN_ADVECT_RK4>(p, h, h2, h6, a->gain, a->drift, velocity);
-        if (a->traj_every && t % a->traj_every == 0) {
-            float *snap = traj + 3 * (size_t)(t / a->traj_every);
-            snap[0] = p[0], snap[1] = p[1], snap[2] = p[2];
-        }
-    }
-    p_out[0] = p[0], p_out[1] = p[1], p_out[2] = p[2];
+    advect_one<float, 3>(*a, p_in, p_out, traj, velocity);
     return 0;
 }
 
@@ -200,10 +212,7 @@ int wnhost_multiband2d_curl_bounded_advect(const float *coef, int n, const float
                                            const float *w, float var_per_band, const wn_obstacle2d *obstacles, int nobs,
                                            const float *flow2, const wn_advect2d *a, float p_out[2], float *traj)
 {
-    if (!a || a->method < WN_ADVECT_EULER || a->method > WN_ADVECT_RK4 || a->steps < 0 || a->traj_every < 0) return 1;
-    if (!std::isfinite(a->h) || !std::isfinite(a->gain) || !std::isfinite(a->drift[0]) || !std::isfinite(a->drift[1]) ||
-        (a->traj_every && !traj))
-        return 1;
+    if (!advect_ok(a, traj)) return 1;
     if (wn::obstacle_fault<2>(obstacles, nobs)) return 1;
     if (flow2 && !(std::isfinite(flow2[0]) && std::isfinite(flow2[1]))) return 1;
     Footprint f;
@@ -211,19 +220,7 @@ int wnhost_multiband2d_curl_bounded_advect(const float *coef, int n, const float
     const auto velocity = [&](const float q[2], float v[2]) {
         wn::multiband2d_curl_bounded_exact(f, f.coef, obstacles, nobs, flow2, q, s, v);
     };
-    const float h = a->h, h2 = 0.5f * a->h, h6 = a->h / 6.0f;
-    float p[2] = {p_in[0], p_in[1]};
-    if (a->traj_every) traj[0] = p[0], traj[1] = p[1];
-    for (int t = 1; t <= a->steps; ++t) {
-        if (a->method == WN_ADVECT_EULER) wn::advect_step<WN_ADVECT_EULER, 2>(p, h, h2, h6, a->gain, a->drift, velocity);
-        else if (a->method == WN_ADVECT_MIDPOINT) wn::advect_step<WN_ADVECT_MIDPOINT, 2>(p, h, h2, h6, a->gain, a->drift, velocity);
-        else wn::advect_step<WN_ADVECT_RK4, 2>(p, h, h2, h6, a->gain, a->drift, velocity);
-        if (a->traj_every && t % a->traj_every == 0) {
-            float *snap = traj + 2 * (size_t)(t / a->traj_every);
-            snap[0] = p[0], snap[1] = p[1];
-        }
-    }
-    p_out[0] = p[0], p_out[1] = p[1];
+    advect_one<float, 2>(*a, p_in, p_out, traj, velocity);
     return 0;
 }
 
@@ -303,29 +300,13 @@ int wnhost_perlin_curl_advect(const int *perm, int kind, int depth, const double
                               const wn_advect *a, double p_out[3], double *traj)
 {
     if (kind < WN_PERLIN_CURL_NOISE || kind > WN_PERLIN_CURL_FRACTAL || (kind == WN_PERLIN_CURL_TURB && depth < 0)) return 1;
-    if (!a || a->method < WN_ADVECT_EULER || a->method > WN_ADVECT_RK4 || a->steps < 0 || a->traj_every < 0) return 1;
-    if (!std::isfinite(a->h) || !std::isfinite(a->gain) || !std::isfinite(a->drift[0]) || !std::isfinite(a->drift[1]) ||
-        !std::isfinite(a->drift[2]) || (a->traj_every && !traj))
-        return 1;
+    if (!advect_ok(a, traj)) return 1;
     const auto velocity = [&](const double q[3], double v[3]) {
         if (kind == WN_PERLIN_CURL_NOISE) wn::perlin_curl_exact(perm, q[0], q[1], q[2], offsets9, v);
         else if (kind == WN_PERLIN_CURL_TURB) wn::perlin_turb_curl(perm, (float)q[0], (float)q[1], (float)q[2], depth, offsets9, v);
         else wn::perlin_fractal_curl(perm, (float)q[0], (float)q[1], (float)q[2], offsets9, v);
     };
-    const double h = (double)a->h, h2 = 0.5 * (double)a->h, h6 = (double)a->h / 6.0, gain = (double)a->gain;
-    const double drift[3] = {(double)a->drift[0], (double)a->drift[1], (double)a->drift[2]};
-    double p[3] = {p_in[0], p_in[1], p_in[2]};
-    if (a->traj_every) traj[0] = p[0], traj[1] = p[1], traj[2] = p[2];
-    for (int t = 1; t <= a->steps; ++t) {
-        if (a->method == WN_ADVECT_EULER) wn::advect_step<WN_ADVECT_EULER, 3, double>(p, h, h2, h6, gain, drift, velocity);
-        else if (a->method == WN_ADVECT_MIDPOINT) wn::advect_step<WN_ADVECT_MIDPOINT, 3, double>(p, h, h2, h6, gain, drift, velocity);
-        else wn::advect_step<WN_ADVECT_RK4, 3, double>(p, h, h2, h6, gain, drift, velocity);
-        if (a->traj_every && t % a->traj_every == 0) {
-            double *snap = traj + 3 * (size_t)(t / a->traj_every);
-            snap[0] = p[0], snap[1] = p[1], snap[2] = p[2];
-        }
-    }
-    p_out[0] = p[0], p_out[1] = p[1], p_out[2] = p[2];
+    advect_one<double, 3>(*a, p_in, p_out, traj, velocity);
     return 0;
 }
 
