@@ -49,8 +49,9 @@
  * The calls only enqueue on `stream`: no allocation, no synchronisation, no launch on the null stream, no host read after
  * they return.  They can be captured into a graph and replayed on other lists in the same buffers.
  *
- * Not provided: gradient, curl and projected bricks; brick edges other than 8; building a brick list from a mask or a
- * level set (the caller's sparse structure already has it).
+ * Not provided: gradient, curl and projected bricks (gradient and curl bricks: wnoise_brick_fields.h, which includes this
+ * header); brick edges other than 8; building a brick list from a mask or a level set (the caller's sparse structure
+ * already has it).
  */
 #ifndef WNOISE_BRICKS_H
 #define WNOISE_BRICKS_H

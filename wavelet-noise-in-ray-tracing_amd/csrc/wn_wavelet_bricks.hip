@@ -19,35 +19,23 @@
 //
 // Both kernels read a brick's triple with the same address in every lane of a wave and decide in-range per brick, wave-uniformly;
 // an out-of-range brick's slot is not touched.
-#include "wn_brick.hpp"
+//
+// The in-range decision, a sample's coordinate and a box's geometry are wn_brick_list.hpp's, shared with the gradient and curl
+// bricks of wn_wavelet_brick_fields.hip.
+#include "wn_brick_list.hpp"
 #include "wnoise_bricks.h"
-
-#include <climits>
-#include <cstdint>
 
 namespace {
 
+using wn::BrickRange;
 using wn::GridArgs;
+using wn::box_geometry;
+using wn::brick_coord;
+using wn::brick_in_range;
 using wn::kMaxBands;
 
 constexpr int kEdge = WN_BRICK, kSamples = kEdge * kEdge * kEdge;
-
-// The bricks of the volume: 0 <= bx < nbx, 0 <= by < nby, bz0 <= bz < bz1.
-struct BrickRange {
-    int nbx, nby, bz0, bz1;
-};
-
-__device__ __forceinline__ bool brick_in_range(const BrickRange &r, int bx, int by, int bz)
-{
-    return bx >= 0 && bx < r.nbx && by >= 0 && by < r.nby && bz >= r.bz0 && bz < r.bz1;
-}
-
-// The coordinate of lattice index i (x, y and z alike: z indices are absolute), wn::lattice_coord's bits: the division is an
-// exact multiply when den is a power of two (inv_den = wn::inv_den_of(den), else 0).
-__device__ __forceinline__ float brick_coord(const GridArgs &g, float den, float inv_den, int i)
-{
-    return wn::lattice_coord_fast(i, den, inv_den, g.base_range, g.octave_scale, g.post_scale);
-}
+static_assert(kEdge == wn::kBrickEdge && kSamples == wn::kBrickSamples, "wn_brick_list.hpp's brick");
 
 // ---- exact tier --------------------------------------------------------------------------------------------------------------
 struct BricksExactArgs : wn::Bands {
@@ -103,28 +91,6 @@ struct BricksSepArgs {
     int vec4_ok; // out is 16-byte aligned, and with it every slot
     ListBand band[kMaxBands];
 };
-
-// One axis of a band's box under the 8 samples from index `first`: coordinates are monotone in the index, so the mids of the
-// first and the last sample bound all of them; one cell of support on either side.
-__device__ __forceinline__ void box_axis(const GridArgs &g, float den, float inv_den, int first, float qmul, int &lo, int &ext)
-{
-    int m0, m1;
-    float w0, w1, w2;
-    wn::bspline(brick_coord(g, den, inv_den, first) * qmul, m0, w0, w1, w2);
-    wn::bspline(brick_coord(g, den, inv_den, first + kEdge - 1) * qmul, m1, w0, w1, w2);
-    lo = min(m0, m1) - 1;
-    ext = abs(m1 - m0) + 3;
-}
-
-// geo = (ix0, jy0, kz0, ex, ey, ez) of wn::brick_fill; x carries the window's fourth column (zero weight, finite values).
-__device__ __forceinline__ void box_geometry(const GridArgs &g, float den, float inv_den, int bx, int by, int bz, float qmul,
-                                             int geo[6])
-{
-    box_axis(g, den, inv_den, kEdge * bx, qmul, geo[0], geo[3]);
-    box_axis(g, den, inv_den, kEdge * by, qmul, geo[1], geo[4]);
-    box_axis(g, den, inv_den, kEdge * bz, qmul, geo[2], geo[5]);
-    geo[3] += 1;
-}
 
 template <int NB>
 __global__ __launch_bounds__(256) void bricks_sep_kernel(const BricksSepArgs a)
@@ -260,45 +226,25 @@ int sep_try(const wn_tile *tile, const GridArgs &g, const GridArgs &gr, const Br
     return WN_OK;
 }
 
-inline long long floor_div8(long long v) { return v >= 0 ? v / kEdge : -((-v + kEdge - 1) / kEdge); }
-
 // The entry points after their tile (and band) checks; d carries the bands of a multiband call (mb).
 int bricks_call(const wn_tile *tile, const wn_grid *grid, BricksExactArgs d, bool mb, const int32_t *bricks_dev, size_t n,
                 float *out_dev, hipStream_t stream)
 {
-    GridArgs g;
-    int rc = wn::check_grid(grid, true, &g);
-    if (rc) return rc;
-    if (grid->z_mode == WN_Z_CONST)
-        return wn::fail(WN_ERR_INVALID, "wn_grid.z_mode must be WN_Z_LATTICE: bricks are three-dimensional");
-    if (n == 0) return WN_OK;
-    if (!bricks_dev) return wn::fail(WN_ERR_INVALID, "bricks_dev is NULL");
-    if (!out_dev) return wn::fail(WN_ERR_INVALID, "out_dev is NULL");
-    if (n > SIZE_MAX / kSamples) return wn::fail(WN_ERR_INVALID, "n * 512 overflows size_t");
-    if (g.nx == 0 || g.ny == 0 || g.nz == 0) return WN_OK; // an empty volume: no brick is in range
+    wn::BrickListPlan plan;
+    bool launch;
+    int rc = wn::brick_list_plan(grid, bricks_dev, n, 1, out_dev, &plan, &launch);
+    if (!launch) return rc;
+    const GridArgs &g = plan.g;
+    const BrickRange &range = plan.range;
 
-    // the volume in bricks, and the lattice rounded up to whole bricks (what an in-range brick can reach) for the regime
-    const long long bz0 = floor_div8(g.z0), bz1 = -floor_div8(-((long long)g.z0 + g.nz));
-    const BrickRange range{(int)(((long long)g.nx + kEdge - 1) / kEdge), (int)(((long long)g.ny + kEdge - 1) / kEdge), (int)bz0,
-                           (int)bz1};
-    const long long rx = (long long)range.nbx * kEdge, ry = (long long)range.nby * kEdge;
-    const bool roundable = rx <= INT_MAX && ry <= INT_MAX && bz0 * kEdge >= INT_MIN && bz1 * kEdge <= INT_MAX;
-    g.z0 = 0; // the kernels form z coordinates from absolute indices
-    g.nz = 0;
-
-    if (!(grid->flags & WN_GRID_EXACT) && roundable && (!mb || d.nbands >= 1)) {
-        GridArgs gr = g;
-        gr.nx = (int)rx;
-        gr.ny = (int)ry;
-        gr.z0 = (int)(bz0 * kEdge);
-        gr.nz = (int)((bz1 - bz0) * kEdge);
+    if (!(grid->flags & WN_GRID_EXACT) && plan.roundable && (!mb || d.nbands >= 1)) {
         // band b: q = p * (2 * 2^(first_band+b)), factor w_b / out_div * out_scale
         float qmul[kMaxBands] = {1.0f}, f[kMaxBands] = {g.out_scale};
         for (int b = 0; mb && b < d.nbands; ++b) {
             qmul[b] = 2.0f * d.band_scale[b];
             f[b] = (float)((double)d.band_w[b] / (double)d.out_div * (double)g.out_scale);
         }
-        if ((rc = sep_try(tile, g, gr, range, mb ? d.nbands : 1, qmul, f, bricks_dev, n, out_dev, stream)) != wn::kDeclined)
+        if ((rc = sep_try(tile, g, plan.gr, range, mb ? d.nbands : 1, qmul, f, bricks_dev, n, out_dev, stream)) != wn::kDeclined)
             return rc;
     }
     if (mb && d.nbands == 0) {

@@ -13,6 +13,7 @@
 #include "PerlinNoise.hpp"
 #include "WaveletNoise.h"
 #include "wn_host.hpp"
+#include "wnoise_brick_fields.h"
 #include "wnoise_bricks.h"
 #include "wnoise_multiband2d.h"
 
@@ -166,4 +167,49 @@ inline void multibandBricks(WaveletNoise &noise, int den, const int32_t *bricks_
     const wn_grid g = wnhost::brick_lattice(den, bounds, 1.0f, 1.0f, 1.0f, flags);
     wnhost::check(wn_multiband3d_bricks(noise.tile(3), &g, bricks_dev, n, s, firstBand, nbands, w, variance, out_dev, stream),
                   "wn_multiband3d_bricks");
+}
+
+// ---- gradient and curl brick lists (include/wnoise_brick_fields.h; absent from the reference) ---------------------------
+// The same lattices and lists with the derivative fields: CH channel arrays of n slots each, channel ch of brick i at
+// out_dev[(ch n + i) 512 + lx + 8 (ly + 8 lz)]; CH = 4 {value, d/dx, d/dy, d/dz} for the gradient, 3 {vx, vy, vz} for the
+// curl, whose offsets9 = (x, y, z) of psi0, psi1, psi2 default to noise.defaultCurlOffsets() (nullptr).
+inline void waveletGradientBricks(WaveletNoise &noise, int den, const int32_t *bricks_dev, size_t n, int octave, float *out_dev,
+                                  const int *bounds = nullptr, int flags = WN_GRID_DEFAULT, void *stream = nullptr)
+{
+    const wn_grid g = wnhost::brick_lattice(den, bounds, std::pow(2.0f, octave), 2.0f, 1.0f / std::sqrt(0.18402f), flags);
+    wnhost::check(wn_eval3d_grad_bricks(noise.tile(3), &g, bricks_dev, n, out_dev, stream), "wn_eval3d_grad_bricks");
+}
+
+inline void multibandGradientBricks(WaveletNoise &noise, int den, const int32_t *bricks_dev, size_t n, float s, int firstBand,
+                                    int nbands, const float *w, float *out_dev, float variance = 0.18402f,
+                                    const int *bounds = nullptr, int flags = WN_GRID_DEFAULT, void *stream = nullptr)
+{
+    const wn_grid g = wnhost::brick_lattice(den, bounds, 1.0f, 1.0f, 1.0f, flags);
+    wnhost::check(wn_multiband3d_grad_bricks(noise.tile(3), &g, bricks_dev, n, s, firstBand, nbands, w, variance, out_dev, stream),
+                  "wn_multiband3d_grad_bricks");
+}
+
+inline void curlBricks(WaveletNoise &noise, int den, const int32_t *bricks_dev, size_t n, int octave, const int *offsets9,
+                       float *out_dev, const int *bounds = nullptr, int flags = WN_GRID_DEFAULT, void *stream = nullptr)
+{
+    static_assert(sizeof(int) == sizeof(int32_t), "offsets are int32");
+    int def[9];
+    if (!offsets9) noise.defaultCurlOffsets(def);
+    const wn_grid g = wnhost::brick_lattice(den, bounds, std::pow(2.0f, octave), 2.0f, 1.0f / std::sqrt(0.18402f), flags);
+    wnhost::check(wn_eval3d_curl_bricks(noise.tile(3), &g, bricks_dev, n, reinterpret_cast<const int32_t *>(offsets9 ? offsets9 : def),
+                                        out_dev, stream),
+                  "wn_eval3d_curl_bricks");
+}
+
+inline void multibandCurlBricks(WaveletNoise &noise, int den, const int32_t *bricks_dev, size_t n, const int *offsets9, float s,
+                                int firstBand, int nbands, const float *w, float *out_dev, float variance = 0.18402f,
+                                const int *bounds = nullptr, int flags = WN_GRID_DEFAULT, void *stream = nullptr)
+{
+    int def[9];
+    if (!offsets9) noise.defaultCurlOffsets(def);
+    const wn_grid g = wnhost::brick_lattice(den, bounds, 1.0f, 1.0f, 1.0f, flags);
+    wnhost::check(wn_multiband3d_curl_bricks(noise.tile(3), &g, bricks_dev, n,
+                                             reinterpret_cast<const int32_t *>(offsets9 ? offsets9 : def), s, firstBand, nbands, w,
+                                             variance, out_dev, stream),
+                  "wn_multiband3d_curl_bricks");
 }

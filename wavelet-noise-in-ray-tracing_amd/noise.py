@@ -1102,9 +1102,9 @@ def multiband_volume(noise, den, nx, ny, z0, z1, s=-16.0, firstBand=0, nbands=5,
 
 
 # ---- sparse brick lists (include/wnoise_bricks.h) ---------------------------------------------------
-def _bricks_args(den, bricks, bounds, out):
+def _bricks_args(den, bricks, bounds, out, ch=1):
     """The (n, 3) int32 device list, (nx, ny, z0, z1) -- `den` on each axis by default, as the generators do -- and the
-    (n, 8, 8, 8) output, indexed [brick][z][y][x]."""
+    (n, 8, 8, 8) output, indexed [brick][z][y][x]; `ch` such arrays one after the other for the derivative fields."""
     if not (isinstance(bricks, torch.Tensor) and bricks.is_cuda and bricks.dtype == torch.int32 and bricks.dim() == 2
             and bricks.shape[1] == 3 and bricks.is_contiguous()):
         raise ValueError("bricks must be a contiguous (n, 3) int32 CUDA tensor of (bx, by, bz)")
@@ -1112,9 +1112,9 @@ def _bricks_args(den, bricks, bounds, out):
     n = bricks.shape[0]
     edge = _capi.WN_BRICK
     if out is None:
-        out = torch.empty((n, edge, edge, edge), dtype=torch.float32, device="cuda")
-    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == n * edge ** 3):
-        raise ValueError("out must be a contiguous float32 CUDA tensor of n * 512 elements")
+        out = torch.empty((ch * n, edge, edge, edge), dtype=torch.float32, device="cuda")
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == ch * n * edge ** 3):
+        raise ValueError("out must be a contiguous float32 CUDA tensor of %sn * 512 elements" % ("" if ch == 1 else f"{ch} * "))
     return n, (nx, ny, z0, z1), out
 
 
@@ -1141,6 +1141,60 @@ def multiband_bricks(noise, den, bricks, s=-16.0, firstBand=0, nbands=5, w=None,
     check(_lib.wn_multiband3d_bricks(noise._handle(3), C.byref(gc), _ptr(bricks), n, float(s), int(firstBand),
                                      int(nbands), wa, float(variance), _ptr(out), _stream()))
     return out.view(n, _capi.WN_BRICK, _capi.WN_BRICK, _capi.WN_BRICK)
+
+
+# ---- gradient and curl brick lists (include/wnoise_brick_fields.h) ------------------------------------
+def _brick_fields_view(out, ch, n):
+    return out.view(ch, n, _capi.WN_BRICK, _capi.WN_BRICK, _capi.WN_BRICK)
+
+
+def wavelet_gradient_bricks(noise, den, bricks, octave, bounds=None, exact=False, out=None):
+    """wavelet_gradient_volume on the listed 8^3 bricks only (wn_eval3d_grad_bricks): (4, n, 8, 8, 8) -- value, d/dx,
+    d/dy, d/dz as out[channel][i][z][y][x]; list, bounds and untouched bricks as wavelet_bricks."""
+    n, (nx, ny, z0, z1), out = _bricks_args(den, bricks, bounds, out, 4)
+    g = GridSpec(den, nx, ny, z0, z1, octave_scale=_octave_scale(octave), post_scale=2.0,
+                 out_scale=_inv_stddev(0.18402), flags=WN_GRID_EXACT if exact else WN_GRID_DEFAULT)
+    gc = g.c()
+    check(_lib.wn_eval3d_grad_bricks(noise._handle(3), C.byref(gc), _ptr(bricks), n, _ptr(out), _stream()))
+    return _brick_fields_view(out, 4, n)
+
+
+def multiband_gradient_bricks(noise, den, bricks, s=-16.0, firstBand=0, nbands=5, w=None, variance=0.18402, bounds=None,
+                              exact=False, out=None):
+    """multiband_gradient_volume on the listed 8^3 bricks only (wn_multiband3d_grad_bricks): (4, n, 8, 8, 8)."""
+    w = [1.0] * nbands if w is None else list(w)
+    n, (nx, ny, z0, z1), out = _bricks_args(den, bricks, bounds, out, 4)
+    g = GridSpec(den, nx, ny, z0, z1, flags=WN_GRID_EXACT if exact else WN_GRID_DEFAULT)
+    gc = g.c()
+    wa = (C.c_float * max(1, nbands))(*[float(x) for x in w[:nbands]])
+    check(_lib.wn_multiband3d_grad_bricks(noise._handle(3), C.byref(gc), _ptr(bricks), n, float(s), int(firstBand),
+                                          int(nbands), wa, float(variance), _ptr(out), _stream()))
+    return _brick_fields_view(out, 4, n)
+
+
+def curl_bricks(noise, den, bricks, octave, offsets=None, bounds=None, exact=False, out=None):
+    """curl_volume on the listed 8^3 bricks only (wn_eval3d_curl_bricks; `offsets` as WaveletNoise.evaluate3DCurl):
+    (3, n, 8, 8, 8) -- vx, vy, vz as out[component][i][z][y][x]."""
+    n, (nx, ny, z0, z1), out = _bricks_args(den, bricks, bounds, out, 3)
+    g = GridSpec(den, nx, ny, z0, z1, octave_scale=_octave_scale(octave), post_scale=2.0,
+                 out_scale=_inv_stddev(0.18402), flags=WN_GRID_EXACT if exact else WN_GRID_DEFAULT)
+    gc = g.c()
+    check(_lib.wn_eval3d_curl_bricks(noise._handle(3), C.byref(gc), _ptr(bricks), n, noise._curl_offsets(offsets), _ptr(out),
+                                     _stream()))
+    return _brick_fields_view(out, 3, n)
+
+
+def multiband_curl_bricks(noise, den, bricks, s=-16.0, firstBand=0, nbands=5, w=None, variance=0.18402, offsets=None,
+                          bounds=None, exact=False, out=None):
+    """multiband_curl_volume on the listed 8^3 bricks only (wn_multiband3d_curl_bricks): (3, n, 8, 8, 8)."""
+    w = [1.0] * nbands if w is None else list(w)
+    n, (nx, ny, z0, z1), out = _bricks_args(den, bricks, bounds, out, 3)
+    g = GridSpec(den, nx, ny, z0, z1, flags=WN_GRID_EXACT if exact else WN_GRID_DEFAULT)
+    gc = g.c()
+    wa = (C.c_float * max(1, nbands))(*[float(x) for x in w[:nbands]])
+    check(_lib.wn_multiband3d_curl_bricks(noise._handle(3), C.byref(gc), _ptr(bricks), n, noise._curl_offsets(offsets),
+                                          float(s), int(firstBand), int(nbands), wa, float(variance), _ptr(out), _stream()))
+    return _brick_fields_view(out, 3, n)
 
 
 def _grad_out(g, out):
