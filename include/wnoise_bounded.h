@@ -41,7 +41,8 @@
  *
  * Not provided: Bridson's variant that keeps the normal component of Psi; obstacles other than these three kinds; moving
  * obstacles and potentials that change with time; dense grids; the Perlin field (of the Perlin and 2-D fields, the 2-D one
- * has its boundaries in wnoise_bounded2d.h).
+ * has its boundaries in wnoise_bounded2d.h).  Lattices are served on sparse lists of 8 x 8 x 8 bricks, by
+ * wnoise_bounded_bricks.h.
  */
 #ifndef WNOISE_BOUNDED_H
 #define WNOISE_BOUNDED_H

@@ -41,7 +41,8 @@
  *                    wn_*_grad_grid / wn_*_curl_grid call over the same lattice also runs its separable brick kernel,
  *                    the sample has that dense sample's bits.
  *
- * Not provided: projected bricks; bounded curl bricks (wnoise_bounded.h's obstacles); brick edges other than 8.
+ * Not provided: projected bricks; bounded curl bricks (wnoise_bounded.h's obstacles: they are wnoise_bounded_bricks.h's
+ * wn_eval3d_curl_bounded_bricks / wn_multiband3d_curl_bounded_bricks); brick edges other than 8.
  */
 #ifndef WNOISE_BRICK_FIELDS_H
 #define WNOISE_BRICK_FIELDS_H

@@ -30,6 +30,7 @@ from .noise import (  # noqa: E402
     perlin_gradient_volume, turb_gradient_volume, curl_volume, multiband_curl_volume, perlin_curl_volume,
     wavelet_bricks, multiband_bricks,
     wavelet_gradient_bricks, multiband_gradient_bricks, curl_bricks, multiband_curl_bricks,
+    curl_bounded_bricks, multiband_curl_bounded_bricks,
 )
 from .shard import slab_bounds, gather_volume, NativeComm  # noqa: E402
 from . import formats  # noqa: E402
@@ -48,5 +49,6 @@ __all__ = [
     "HipTimer", "wavelet_gradient_volume", "multiband_gradient_volume", "wavelet2d_gradient_image",
     "projected_gradient_volume", "perlin_gradient_volume", "turb_gradient_volume", "curl_volume",
     "multiband_curl_volume", "perlin_curl_volume", "wavelet_bricks", "multiband_bricks",
-    "wavelet_gradient_bricks", "multiband_gradient_bricks", "curl_bricks", "multiband_curl_bricks", "slab_bounds", "gather_volume", "NativeComm", "formats",
+    "wavelet_gradient_bricks", "multiband_gradient_bricks", "curl_bricks", "multiband_curl_bricks",
+    "curl_bounded_bricks", "multiband_curl_bounded_bricks", "slab_bounds", "gather_volume", "NativeComm", "formats",
 ]

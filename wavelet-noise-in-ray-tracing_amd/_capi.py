@@ -1,7 +1,7 @@
 """ctypes binding of libwnoise_hip.so (include/wnoise.h, include/wnoise_perlin_curl.h, include/wnoise_footprint.h,
 include/wnoise_perlin_footprint.h, include/wnoise_multiband2d.h, include/wnoise_advect.h, include/wnoise_bounded.h,
 include/wnoise_perlin_advect.h, include/wnoise_curl2d.h, include/wnoise_bounded2d.h, include/wnoise_bricks.h,
-include/wnoise_brick_fields.h).
+include/wnoise_brick_fields.h, include/wnoise_bounded_bricks.h).
 
 The library is the product: if it is missing or fails to load this module raises, it never
 substitutes a CPU implementation.
@@ -250,6 +250,13 @@ BRICK_FIELDS_SIGNATURES = {
     "wn_multiband3d_curl_bricks": (_i, [_vp, _gp, _vp, _sz, _i32p, _f, _i, _i, _fp, _f, _vp, _vp]),
 }
 
+# name -> (restype, argtypes); every symbol include/wnoise_bounded_bricks.h declares.
+BOUNDED_BRICKS_SIGNATURES = {
+    # tile, grid, bricks, n, offsets9, [s, first_band, nbands, w, var,] obstacles, nobs, out, stream
+    "wn_eval3d_curl_bounded_bricks": (_i, [_vp, _gp, _vp, _sz, _i32p, _op, _i, _vp, _vp]),
+    "wn_multiband3d_curl_bounded_bricks": (_i, [_vp, _gp, _vp, _sz, _i32p, _f, _i, _i, _fp, _f, _op, _i, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -267,7 +274,7 @@ def load():
                               *PERLIN_FOOTPRINT_SIGNATURES.items(), *MULTIBAND2D_SIGNATURES.items(),
                               *ADVECT_SIGNATURES.items(), *BOUNDED_SIGNATURES.items(), *PERLIN_ADVECT_SIGNATURES.items(),
                               *CURL2D_SIGNATURES.items(), *BOUNDED2D_SIGNATURES.items(), *BRICKS_SIGNATURES.items(),
-                              *BRICK_FIELDS_SIGNATURES.items()):
+                              *BRICK_FIELDS_SIGNATURES.items(), *BOUNDED_BRICKS_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

@@ -1,10 +1,13 @@
-// wn_brick_list.hpp -- what the brick-list kernels share: the value bricks of wn_wavelet_bricks.hip (include/wnoise_bricks.h)
-// and the gradient and curl bricks of wn_wavelet_brick_fields.hip (include/wnoise_brick_fields.h).
+// wn_brick_list.hpp -- what the brick-list kernels share: the value bricks of wn_wavelet_bricks.hip (include/wnoise_bricks.h),
+// the gradient and curl bricks of wn_wavelet_brick_fields.hip (include/wnoise_brick_fields.h) and the bounded curl bricks of
+// wn_wavelet_bounded_bricks.hip (include/wnoise_bounded_bricks.h).
 //
 // A brick is 8 x 8 x 8 samples of the lattice a wn_grid describes, named by a device triple (bx, by, bz); the volume's extents
 // say which bricks are in range.  Here: the entry points' checks after their tile and bands, the volume in bricks and the
 // lattice rounded up to whole bricks (what the separable kernels' regime is checked on), and on the device the in-range
-// decision, a sample's coordinate and the geometry of a band's coefficient box under a brick.
+// decision, a sample's coordinate and the geometry of a band's coefficient box under a brick; and, for the two files of
+// derivative fields, the band factors, the separable regime with its argument setup, and the separable kernels' frame
+// (pair_brick, fill_box, store_slots), templated on the kernel's argument struct.
 #pragma once
 
 #include "wn_brick.hpp"
@@ -69,6 +72,46 @@ inline int brick_list_plan(const wn_grid *grid, const int32_t *bricks_dev, size_
     return WN_OK;
 }
 
+// A band of the separable derivative-field kernels (wn_wavelet_brick_fields.hip, wn_wavelet_bounded_bricks.hip).
+struct FieldBand : BrickBand {
+    float fv, fg; // factors of the band's value and of its derivatives: w_b / out_div * out_scale, and that * qmul
+};
+
+// The regime of the separable derivative-field kernels, checked on the lattice rounded up to whole bricks (plan.gr), and
+// their arguments: the regime of the value bricks' sep_try (wn_wavelet_bricks.hip) -- a tile that is not empty, and in every
+// band a step >= 0 below 1/3 cell with coordinates inside the planners' gate; the box of 8 samples then has at most 6 cells
+// per axis and always fits box_cap.  false: outside the regime, *a is not to be launched on.  Args has the fields of
+// FieldsSepArgs (wn_wavelet_brick_fields.hip); a band keeps `boxes` boxes (the curl: one per potential).
+template <typename Args>
+inline bool field_sep_args(const wn_tile *tile, const BrickListPlan &plan, const int *off9, int boxes, int box_cap, int nbands,
+                           const float *qmul, const float *fv, const float *fg, const int32_t *bricks, size_t n, float *out_dev,
+                           Args *a)
+{
+    if (tile->n == 0 || !plan.roundable || nbands < 1 || nbands > kMaxBands) return false;
+    for (int b = 0; b < nbands; ++b) {
+        LatticeStep ls;
+        if (!lattice_step(plan.gr, plan.g.octave_scale * qmul[b], false, false, 0.0, &ls) || !ls.two_mids()) return false;
+        if ((ls.extent(kBrickEdge) + 1) * ls.extent(kBrickEdge) * ls.extent(kBrickEdge) > box_cap) return false; // never inside two_mids
+        a->band[b].qmul = qmul[b];
+        a->band[b].box_off = b * box_cap * boxes;
+        a->band[b].box_cap = box_cap;
+        a->band[b].fv = fv[b];
+        a->band[b].fg = fg[b];
+    }
+    a->coef = tile->dev;
+    a->n = tile->n;
+    a->nmask = pow2_mask(tile->n);
+    for (int i = 0; i < 9; ++i) a->off[i] = off9[i];
+    a->g = plan.g;
+    a->inv_den = inv_den_of(plan.g.den);
+    a->range = plan.range;
+    a->bricks = bricks;
+    a->count = n;
+    a->out = out_dev;
+    a->vec4_ok = (reinterpret_cast<uintptr_t>(out_dev) & 15) == 0;
+    return true;
+}
+
 #if defined(__HIPCC__)
 __device__ __forceinline__ bool brick_in_range(const BrickRange &r, int bx, int by, int bz)
 {
@@ -102,6 +145,49 @@ __device__ __forceinline__ void box_geometry(const GridArgs &g, float den, float
     box_axis(g, den, inv_den, kBrickEdge * by, qmul, geo[1], geo[4]);
     box_axis(g, den, inv_den, kBrickEdge * bz, qmul, geo[2], geo[5]);
     geo[3] += 1;
+}
+
+// ---- the frame of the separable derivative-field kernels: 256 lanes, two bricks per workgroup, 128 lanes per brick.  Args is
+// the kernel's argument struct: bricks, count and range; coef, n and nmask of the linear tile.
+// The brick of this half of the workgroup in pair `pair`: false when the list has ended or the brick is out of range.
+template <typename Args>
+__device__ __forceinline__ bool pair_brick(const Args &a, size_t i, int &bx, int &by, int &bz)
+{
+    bx = by = bz = 0;
+    if (i >= a.count) return false;
+    bx = __builtin_amdgcn_readfirstlane(a.bricks[3 * i]);
+    by = __builtin_amdgcn_readfirstlane(a.bricks[3 * i + 1]);
+    bz = __builtin_amdgcn_readfirstlane(a.bricks[3 * i + 2]);
+    return brick_in_range(a.range, bx, by, bz);
+}
+
+// bb[k][j][i] = coef[Mod(kz0+k+oz)][Mod(jy0+j+oy)][Mod(ix0+i+ox)]: wn::brick_fill's box, the brick's 128 lanes over the flat
+// box (rows are at most 7 cells).
+template <typename Args>
+__device__ __forceinline__ void fill_box(float *bb, const Args &a, const int geo[6], int ox, int oy, int oz, int l)
+{
+    const int ex = geo[3], exy = geo[3] * geo[4], cells = exy * geo[5];
+    for (int c = l; c < cells; c += 128) {
+        const int k = c / exy, r = c - k * exy;
+        const int j = r / ex, ii = r - j * ex;
+        bb[c] = a.coef[((size_t)dmod(geo[2] + k + oz, a.n, a.nmask) * a.n + dmod(geo[1] + j + oy, a.n, a.nmask)) * a.n +
+                       dmod(geo[0] + ii + ox, a.n, a.nmask)];
+    }
+}
+
+// A lane's 4 samples of CH channel arrays (chan floats apart) at dst, its first sample's address in channel 0.
+template <int CH>
+__device__ __forceinline__ void store_slots(float *dst, size_t chan, int vec4_ok, const float (&acc)[CH][4])
+{
+    if (vec4_ok) {
+#pragma unroll
+        for (int ch = 0; ch < CH; ++ch) *reinterpret_cast<v4f *>(dst + ch * chan) = v4f{acc[ch][0], acc[ch][1], acc[ch][2], acc[ch][3]};
+    } else {
+#pragma unroll
+        for (int ch = 0; ch < CH; ++ch)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) dst[ch * chan + q] = acc[ch][q];
+    }
 }
 #endif
 

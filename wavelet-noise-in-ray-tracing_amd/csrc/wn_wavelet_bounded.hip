@@ -9,7 +9,7 @@
 //   curl3d_bounded_advect_kernel<PADDED, MB, METHOD>  one particle per lane in a grid-stride loop; position, stage point and
 //                                                     RK4's running sum in registers.
 //
-// The obstacle list travels by value in the launch arguments (16 x 32 bytes): it is the same for every lane, so the
+// The obstacle list travels by value in the launch arguments (wn_obstacles.hpp; 16 x 32 bytes): it is the same for every lane, so the
 // obstacle loop reads it with scalar loads and branches on the kind as a wave.  A lane that is far from every obstacle
 // runs the unbounded evaluator and nothing else; a near lane then walks its 27 taps a second time for the three potential
 // values (the rows are in cache, the bits are those of one pass), so the far path keeps the unbounded kernel's live set;
@@ -17,8 +17,7 @@
 //
 // A launch integrates at most wn_advect_launch_steps() steps, the cap wn_wavelet_advect.hip measured; a longer trace is a
 // chain of launches on the stream.
-#include "wn_internal.hpp"
-#include "wnoise_bounded.h"
+#include "wn_obstacles.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -26,18 +25,10 @@
 namespace {
 
 using wn::CurlEval;
-
-static_assert(WN_MAX_OBSTACLES == wn::kMaxObstacles && sizeof(wn_obstacle) == 32, "include/wnoise_bounded.h");
-static_assert(WN_OBSTACLE_SPHERE == wn::kObstacleSphere && WN_OBSTACLE_CONTAINER == wn::kObstacleContainer &&
-                  WN_OBSTACLE_HALFSPACE == wn::kObstacleHalfspace,
-              "include/wnoise_bounded.h");
+using wn::Obstacles;
+using wn::obstacle_args;
 
 constexpr size_t kBoundedBlockCap = 256u * 8u; // of the curl point kernel's: the lanes hold 27 row loads each
-
-struct Obstacles {
-    wn_obstacle list[WN_MAX_OBSTACLES];
-    int nobs;
-};
 
 struct BoundedPointsArgs {
     CurlEval e;
@@ -85,15 +76,6 @@ __global__ __launch_bounds__(256) void curl3d_bounded_advect_kernel(const Bounde
             dst[2] = p[2];
         });
     }
-}
-
-int obstacle_args(const wn_obstacle *obstacles_host, int nobs, const char *entry, Obstacles *o)
-{
-    if (const char *why = wn::obstacle_fault(obstacles_host, nobs)) return wn::fail(WN_ERR_INVALID, "%s: %s", entry, why);
-    *o = Obstacles{};
-    std::copy(obstacles_host, obstacles_host + nobs, o->list);
-    o->nobs = nobs;
-    return WN_OK;
 }
 
 int launch_bounded_points(const wn_tile *tile, const CurlEval &e, const Obstacles &o, const float *xyz_dev, size_t n,

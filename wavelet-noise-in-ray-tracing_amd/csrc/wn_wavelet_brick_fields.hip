@@ -29,11 +29,15 @@ namespace {
 
 using wn::BrickRange;
 using wn::CurlEval;
+using wn::FieldBand;
 using wn::GridArgs;
 using wn::box_geometry;
 using wn::brick_coord;
 using wn::brick_in_range;
+using wn::fill_box;
 using wn::kMaxBands;
+using wn::pair_brick;
+using wn::store_slots;
 
 constexpr int kEdge = wn::kBrickEdge, kSamples = wn::kBrickSamples;
 
@@ -90,10 +94,6 @@ constexpr int kBoxCap = 7 * 6 * 6;              // floats per box, as wn_wavelet
 constexpr size_t kSepBlockCap = 256u * 8u;       // workgroups of the pair-stride launches
 constexpr size_t kCurlExactBlockCap = 256u * 8u; // of the exact curl launch: the cap of curl3d_points_kernel, whose body it runs
 
-struct FieldBand : wn::BrickBand {
-    float fv, fg; // factors of the band's value and of its derivatives: w_b / out_div * out_scale, and that * qmul
-};
-
 struct FieldsSepArgs {
     const float *coef; // linear tile
     int n, nmask;
@@ -107,45 +107,6 @@ struct FieldsSepArgs {
     int vec4_ok; // out is 16-byte aligned, and with it every slot of every channel
     FieldBand band[kMaxBands];
 };
-
-// The brick of this half of the workgroup in pair `pair`: false when the list has ended or the brick is out of range.
-__device__ __forceinline__ bool pair_brick(const FieldsSepArgs &a, size_t i, int &bx, int &by, int &bz)
-{
-    bx = by = bz = 0;
-    if (i >= a.count) return false;
-    bx = __builtin_amdgcn_readfirstlane(a.bricks[3 * i]);
-    by = __builtin_amdgcn_readfirstlane(a.bricks[3 * i + 1]);
-    bz = __builtin_amdgcn_readfirstlane(a.bricks[3 * i + 2]);
-    return brick_in_range(a.range, bx, by, bz);
-}
-
-// bb[k][j][i] = coef[Mod(kz0+k+oz)][Mod(jy0+j+oy)][Mod(ix0+i+ox)]: wn::brick_fill's box, the brick's 128 lanes over the flat
-// box (rows are at most 7 cells).
-__device__ __forceinline__ void fill_box(float *bb, const FieldsSepArgs &a, const int geo[6], int ox, int oy, int oz, int l)
-{
-    const int ex = geo[3], exy = geo[3] * geo[4], cells = exy * geo[5];
-    for (int c = l; c < cells; c += 128) {
-        const int k = c / exy, r = c - k * exy;
-        const int j = r / ex, ii = r - j * ex;
-        bb[c] = a.coef[((size_t)wn::dmod(geo[2] + k + oz, a.n, a.nmask) * a.n + wn::dmod(geo[1] + j + oy, a.n, a.nmask)) * a.n +
-                       wn::dmod(geo[0] + ii + ox, a.n, a.nmask)];
-    }
-}
-
-// A lane's 4 samples of CH channel arrays (chan floats apart) at dst, its first sample's address in channel 0.
-template <int CH>
-__device__ __forceinline__ void store_slots(float *dst, size_t chan, int vec4_ok, const float (&acc)[CH][4])
-{
-    if (vec4_ok) {
-#pragma unroll
-        for (int ch = 0; ch < CH; ++ch) *reinterpret_cast<v4f *>(dst + ch * chan) = v4f{acc[ch][0], acc[ch][1], acc[ch][2], acc[ch][3]};
-    } else {
-#pragma unroll
-        for (int ch = 0; ch < CH; ++ch)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) dst[ch * chan + q] = acc[ch][q];
-    }
-}
 
 template <int NB>
 __global__ __launch_bounds__(256) void grad_bricks_sep_kernel(const FieldsSepArgs a)
@@ -331,35 +292,13 @@ __global__ __launch_bounds__(256) void curl_bricks_sep_kernel(const FieldsSepArg
     }
 }
 
-// Launches a separable kernel when the lattice, rounded up to whole bricks (plan.gr), is in the regime of the value bricks'
-// sep_try (wn_wavelet_bricks.hip): a tile that is not empty, and in every band a step >= 0 below 1/3 cell with coordinates
-// inside the planners' gate; the box of 8 samples then has at most 6 cells per axis and always fits.
+// Launches a separable kernel when the lattice, rounded up to whole bricks (plan.gr), is in the regime of
+// wn::field_sep_args (wn_brick_list.hpp): that of the value bricks' sep_try (wn_wavelet_bricks.hip).
 int sep_try(const wn_tile *tile, const wn::BrickListPlan &plan, const CurlEval &e, bool curl, int nbands, const float *qmul,
             const float *fv, const float *fg, const int32_t *bricks, size_t n, float *out_dev, hipStream_t stream)
 {
-    if (tile->n == 0 || !plan.roundable || nbands < 1 || nbands > kMaxBands) return wn::kDeclined;
     FieldsSepArgs a{};
-    for (int b = 0; b < nbands; ++b) {
-        wn::LatticeStep ls;
-        if (!wn::lattice_step(plan.gr, plan.g.octave_scale * qmul[b], false, false, 0.0, &ls) || !ls.two_mids()) return wn::kDeclined;
-        if ((ls.extent(kEdge) + 1) * ls.extent(kEdge) * ls.extent(kEdge) > kBoxCap) return wn::kDeclined; // never inside two_mids
-        a.band[b].qmul = qmul[b];
-        a.band[b].box_off = b * kBoxCap * (curl ? 3 : 1);
-        a.band[b].box_cap = kBoxCap;
-        a.band[b].fv = fv[b];
-        a.band[b].fg = fg[b];
-    }
-    a.coef = tile->dev;
-    a.n = tile->n;
-    a.nmask = wn::pow2_mask(tile->n);
-    std::copy(e.off, e.off + 9, a.off);
-    a.g = plan.g;
-    a.inv_den = wn::inv_den_of(plan.g.den);
-    a.range = plan.range;
-    a.bricks = bricks;
-    a.count = n;
-    a.out = out_dev;
-    a.vec4_ok = (reinterpret_cast<uintptr_t>(out_dev) & 15) == 0;
+    if (!wn::field_sep_args(tile, plan, e.off, curl ? 3 : 1, kBoxCap, nbands, qmul, fv, fg, bricks, n, out_dev, &a)) return wn::kDeclined;
     const dim3 blocks(wn::stride_blocks((n + 1) / 2 * 256, kSepBlockCap)), block(256);
     wn::brick_dispatch(nbands, [&](auto nb) {
         if (curl) hipLaunchKernelGGL(curl_bricks_sep_kernel<decltype(nb)::value>, blocks, block, 0, stream, a);

@@ -13,6 +13,7 @@
 #include "PerlinNoise.hpp"
 #include "WaveletNoise.h"
 #include "wn_host.hpp"
+#include "wnoise_bounded_bricks.h"
 #include "wnoise_brick_fields.h"
 #include "wnoise_bricks.h"
 #include "wnoise_multiband2d.h"
@@ -212,4 +213,35 @@ inline void multibandCurlBricks(WaveletNoise &noise, int den, const int32_t *bri
                                              reinterpret_cast<const int32_t *>(offsets9 ? offsets9 : def), s, firstBand, nbands, w,
                                              variance, out_dev, stream),
                   "wn_multiband3d_curl_bricks");
+}
+
+// ---- curl brick lists with solid boundaries (include/wnoise_bounded_bricks.h; absent from the reference) ----------------
+// curlBricks / multibandCurlBricks with the potential faded to zero towards the nobs obstacles of include/wnoise_bounded.h,
+// which live in the coordinate the derivative is taken in: the sample's noise-space coordinate, or the multiband lattice's p.
+// nobs == 0 gives the unbounded bits.
+inline void curlBoundedBricks(WaveletNoise &noise, int den, const int32_t *bricks_dev, size_t n, int octave, const int *offsets9,
+                              const wn_obstacle *obstacles, int nobs, float *out_dev, const int *bounds = nullptr,
+                              int flags = WN_GRID_DEFAULT, void *stream = nullptr)
+{
+    int def[9];
+    if (!offsets9) noise.defaultCurlOffsets(def);
+    const wn_grid g = wnhost::brick_lattice(den, bounds, std::pow(2.0f, octave), 2.0f, 1.0f / std::sqrt(0.18402f), flags);
+    wnhost::check(wn_eval3d_curl_bounded_bricks(noise.tile(3), &g, bricks_dev, n,
+                                                reinterpret_cast<const int32_t *>(offsets9 ? offsets9 : def), obstacles, nobs,
+                                                out_dev, stream),
+                  "wn_eval3d_curl_bounded_bricks");
+}
+
+inline void multibandCurlBoundedBricks(WaveletNoise &noise, int den, const int32_t *bricks_dev, size_t n, const int *offsets9,
+                                       float s, int firstBand, int nbands, const float *w, const wn_obstacle *obstacles,
+                                       int nobs, float *out_dev, float variance = 0.18402f, const int *bounds = nullptr,
+                                       int flags = WN_GRID_DEFAULT, void *stream = nullptr)
+{
+    int def[9];
+    if (!offsets9) noise.defaultCurlOffsets(def);
+    const wn_grid g = wnhost::brick_lattice(den, bounds, 1.0f, 1.0f, 1.0f, flags);
+    wnhost::check(wn_multiband3d_curl_bounded_bricks(noise.tile(3), &g, bricks_dev, n,
+                                                     reinterpret_cast<const int32_t *>(offsets9 ? offsets9 : def), s, firstBand,
+                                                     nbands, w, variance, obstacles, nobs, out_dev, stream),
+                  "wn_multiband3d_curl_bounded_bricks");
 }

@@ -1197,6 +1197,38 @@ def multiband_curl_bricks(noise, den, bricks, s=-16.0, firstBand=0, nbands=5, w=
     return _brick_fields_view(out, 3, n)
 
 
+# ---- curl brick lists with solid boundaries (include/wnoise_bounded_bricks.h) --------------------------
+def curl_bounded_bricks(noise, den, bricks, octave, obstacles, offsets=None, bounds=None, exact=False, out=None):
+    """curl_bricks with its potential faded to zero towards every solid of `obstacles` (wn_eval3d_curl_bounded_bricks):
+    (3, n, 8, 8, 8).  `obstacles` as WaveletNoise.evaluate3DCurlBounded takes them, in the samples' noise-space coordinates
+    ((i / den) * 4 * 2^octave * 2); a sample inside a solid gets 0, one at distance >= d0 from all of them (and
+    obstacles=[]) the bits of curl_bricks."""
+    n, (nx, ny, z0, z1), out = _bricks_args(den, bricks, bounds, out, 3)
+    g = GridSpec(den, nx, ny, z0, z1, octave_scale=_octave_scale(octave), post_scale=2.0,
+                 out_scale=_inv_stddev(0.18402), flags=WN_GRID_EXACT if exact else WN_GRID_DEFAULT)
+    gc = g.c()
+    obs, nobs = noise._obstacles(obstacles)
+    check(_lib.wn_eval3d_curl_bounded_bricks(noise._handle(3), C.byref(gc), _ptr(bricks), n, noise._curl_offsets(offsets),
+                                             obs, nobs, _ptr(out), _stream()))
+    return _brick_fields_view(out, 3, n)
+
+
+def multiband_curl_bounded_bricks(noise, den, bricks, obstacles, s=-16.0, firstBand=0, nbands=5, w=None, variance=0.18402,
+                                  offsets=None, bounds=None, exact=False, out=None):
+    """multiband_curl_bricks with the solids of `obstacles` (wn_multiband3d_curl_bounded_bricks): (3, n, 8, 8, 8); the
+    obstacles live in the lattice coordinate p = (i / den) * 4."""
+    w = [1.0] * nbands if w is None else list(w)
+    n, (nx, ny, z0, z1), out = _bricks_args(den, bricks, bounds, out, 3)
+    g = GridSpec(den, nx, ny, z0, z1, flags=WN_GRID_EXACT if exact else WN_GRID_DEFAULT)
+    gc = g.c()
+    wa = (C.c_float * max(1, nbands))(*[float(x) for x in w[:nbands]])
+    obs, nobs = noise._obstacles(obstacles)
+    check(_lib.wn_multiband3d_curl_bounded_bricks(noise._handle(3), C.byref(gc), _ptr(bricks), n, noise._curl_offsets(offsets),
+                                                  float(s), int(firstBand), int(nbands), wa, float(variance), obs, nobs,
+                                                  _ptr(out), _stream()))
+    return _brick_fields_view(out, 3, n)
+
+
 def _grad_out(g, out):
     n = 4 * g.nz * g.ny * g.nx
     if out is None:
