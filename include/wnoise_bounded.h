@@ -40,9 +40,9 @@
  * A result has the bits of the host's wnhost_eval3d_curl_bounded / wnhost_eval3d_curl_bounded_advect.
  *
  * Not provided: Bridson's variant that keeps the normal component of Psi; obstacles other than these three kinds; moving
- * obstacles and potentials that change with time; dense grids; the Perlin field (of the Perlin and 2-D fields, the 2-D one
- * has its boundaries in wnoise_bounded2d.h).  Lattices are served on sparse lists of 8 x 8 x 8 bricks, by
- * wnoise_bounded_bricks.h.
+ * obstacles and potentials that change with time; dense grids.  The Perlin and 2-D fields have their boundaries in headers
+ * of their own: wnoise_perlin_bounded.h (fp64, with this header's wn_obstacle) and wnoise_bounded2d.h.  Lattices are served
+ * on sparse lists of 8 x 8 x 8 bricks, by wnoise_bounded_bricks.h.
  */
 #ifndef WNOISE_BOUNDED_H
 #define WNOISE_BOUNDED_H

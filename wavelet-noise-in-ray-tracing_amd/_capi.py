@@ -1,7 +1,7 @@
 """ctypes binding of libwnoise_hip.so (include/wnoise.h, include/wnoise_perlin_curl.h, include/wnoise_footprint.h,
 include/wnoise_perlin_footprint.h, include/wnoise_multiband2d.h, include/wnoise_advect.h, include/wnoise_bounded.h,
 include/wnoise_perlin_advect.h, include/wnoise_curl2d.h, include/wnoise_bounded2d.h, include/wnoise_bricks.h,
-include/wnoise_brick_fields.h, include/wnoise_bounded_bricks.h).
+include/wnoise_brick_fields.h, include/wnoise_bounded_bricks.h, include/wnoise_perlin_bounded.h).
 
 The library is the product: if it is missing or fails to load this module raises, it never
 substitutes a CPU implementation.
@@ -202,6 +202,19 @@ PERLIN_ADVECT_SIGNATURES = {
     "wn_perlin_advect_launch_steps": (_i, [_i, _i, _i]),
 }
 
+# name -> (restype, argtypes); every symbol include/wnoise_perlin_bounded.h declares.  (The name leads with SIGNATURES:
+# tests/test_bounded_bricks_host.py pins the set of names that end with it.)
+SIGNATURES_PERLIN_BOUNDED = {
+    # perm, xyz, n, [kind, depth,] offsets9, [obstacles, nobs,] out3, stream
+    "wn_perlin_curl_potential_points_f64": (_i, [_vp, _vp, _sz, _i32p, _vp, _vp]),
+    "wn_perlin_curl_potential_points_f32": (_i, [_vp, _vp, _sz, _i, _i, _i32p, _vp, _vp]),
+    "wn_perlin_curl_bounded_points_f64": (_i, [_vp, _vp, _sz, _i32p, _op, _i, _vp, _vp]),
+    "wn_perlin_curl_bounded_points_f32": (_i, [_vp, _vp, _sz, _i, _i, _i32p, _op, _i, _vp, _vp]),
+    # perm, xyz_in, n, kind, depth, offsets9, obstacles, nobs, a, xyz_out, traj, stream
+    "wn_perlin_curl_bounded_advect_points_f64": (_i, [_vp, _vp, _sz, _i, _i, _i32p, _op, _i, _ap, _vp, _vp, _vp]),
+    "wn_perlin_bounded_advect_launch_steps": (_i, [_i, _i, _i, _i]),
+}
+
 # name -> (restype, argtypes); every symbol include/wnoise_curl2d.h declares, and its wn_advect2d.
 class wn_advect2d(C.Structure):
     _fields_ = [("method", C.c_int32), ("steps", C.c_int32), ("h", C.c_float), ("gain", C.c_float),
@@ -274,7 +287,8 @@ def load():
                               *PERLIN_FOOTPRINT_SIGNATURES.items(), *MULTIBAND2D_SIGNATURES.items(),
                               *ADVECT_SIGNATURES.items(), *BOUNDED_SIGNATURES.items(), *PERLIN_ADVECT_SIGNATURES.items(),
                               *CURL2D_SIGNATURES.items(), *BOUNDED2D_SIGNATURES.items(), *BRICKS_SIGNATURES.items(),
-                              *BRICK_FIELDS_SIGNATURES.items(), *BOUNDED_BRICKS_SIGNATURES.items()):
+                              *BRICK_FIELDS_SIGNATURES.items(), *BOUNDED_BRICKS_SIGNATURES.items(),
+                              *SIGNATURES_PERLIN_BOUNDED.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

@@ -1,5 +1,5 @@
-// wn_advect.hpp -- a particle's trace through a velocity field, stated once for the five advection kernels (wn_wavelet_advect,
-// wn_wavelet_bounded, wn_perlin_advect, wn_wavelet_curl2d, wn_wavelet_bounded2d .hip) and for the host's wnhost_*_advect
+// wn_advect.hpp -- a particle's trace through a velocity field, stated once for the six advection kernels (wn_wavelet_advect,
+// wn_wavelet_bounded, wn_perlin_advect, wn_perlin_bounded, wn_wavelet_curl2d, wn_wavelet_bounded2d .hip) and for the host's wnhost_*_advect
 // (host/scalar_eval.cpp): the steps of one launch with their trajectory snapshots (advect_trace, around wn::advect_step of
 // wn_eval.hpp), and the chain that cuts a call's trace into launches (advect_chain).  A field supplies its velocity functor
 // and its steps-per-launch rule.  Like wn_eval.hpp, no HIP header: a plain C++ compiler includes it.

@@ -618,7 +618,7 @@ WN_EVAL_FN void multiband_curl_exact(const A &a, const float p[3], float v[3])
 // to it, and the velocity is the curl of the faded potential, v = curl(A Psi) = A curl Psi + grad A x Psi: still
 // divergence-free, and on a solid A -> 0 and grad A is parallel to the normal, so the normal component of v vanishes.
 // O is wn_obstacle (kind, c[3], r, d0), or wn_obstacle2d (c[2]) for the 2-D field further down; this header includes neither.
-// Everything below is float32 and unfused.
+// The wavelet fields are float32, the Perlin field float64; everything is unfused.
 constexpr int kMaxObstacles = 16; // WN_MAX_OBSTACLES
 constexpr int kObstacleSphere = 0, kObstacleContainer = 1, kObstacleHalfspace = 2;
 
@@ -648,64 +648,70 @@ inline const char *obstacle_fault(const O *obs, int nobs)
     return nullptr;
 }
 
-// The signed distance d of x to obstacle o (positive in the fluid) and its gradient nrm.
-//     sphere, container  dx = x - c, l = sqrtf((dx0*dx0 + dx1*dx1) + dx2*dx2), m = dx / l (0 when l == 0);
+// The signed distance d of x to obstacle o (positive in the fluid) and its gradient nrm, in the scalar type T of the point:
+// float for the wavelet fields (sqrtf), double for the Perlin field (include/wnoise_perlin_bounded.h: c, r and d0 are widened
+// from float, which is exact, sqrt and / are IEEE double).
+//     sphere, container  dx = x - c, l = sqrt((dx0*dx0 + dx1*dx1) + dx2*dx2), m = dx / l (0 when l == 0);
 //                        sphere: d = l - r, nrm = m; container: d = r - l, nrm = -m
 //     half-space         d = ((n0*x0 + n1*x1) + n2*x2) - o, nrm = n as given (not normalised: d is linear with gradient n)
-// D == 2: the same with the third component dropped, l = sqrtf(dx0*dx0 + dx1*dx1) and d = (n0*x0 + n1*x1) - o.
-template <int D = 3, typename O>
-WN_EVAL_FN float obstacle_distance(const O &o, const float x[D], float nrm[D])
+// D == 2: the same with the third component dropped, l = sqrt(dx0*dx0 + dx1*dx1) and d = (n0*x0 + n1*x1) - o.
+WN_EVAL_FN float ramp_sqrt(float x) { return sqrtf(x); }
+WN_EVAL_FN double ramp_sqrt(double x) { return sqrt(x); }
+
+template <int D = 3, typename T, typename O>
+WN_EVAL_FN T obstacle_distance(const O &o, const T x[D], T nrm[D])
 {
     if (o.kind == kObstacleHalfspace) {
         WN_UNROLL
-        for (int c = 0; c < D; ++c) nrm[c] = o.c[c];
-        float dot = o.c[0] * x[0] + o.c[1] * x[1];
-        if constexpr (D == 3) dot = dot + o.c[2] * x[2];
-        return dot - o.r;
+        for (int c = 0; c < D; ++c) nrm[c] = (T)o.c[c];
+        T dot = (T)o.c[0] * x[0] + (T)o.c[1] * x[1];
+        if constexpr (D == 3) dot = dot + (T)o.c[2] * x[2];
+        return dot - (T)o.r;
     }
-    float dx[D];
+    T dx[D];
     WN_UNROLL
-    for (int c = 0; c < D; ++c) dx[c] = x[c] - o.c[c];
-    float l2 = dx[0] * dx[0] + dx[1] * dx[1];
+    for (int c = 0; c < D; ++c) dx[c] = x[c] - (T)o.c[c];
+    T l2 = dx[0] * dx[0] + dx[1] * dx[1];
     if constexpr (D == 3) l2 = l2 + dx[2] * dx[2];
-    const float l = sqrtf(l2);
+    const T l = ramp_sqrt(l2);
     const bool solid = o.kind == kObstacleSphere;
     WN_UNROLL
     for (int c = 0; c < D; ++c) {
-        const float m = l == 0.0f ? 0.0f : dx[c] / l;
+        const T m = l == T(0) ? T(0) : dx[c] / l;
         nrm[c] = solid ? m : -m;
     }
-    return solid ? l - o.r : o.r - l;
+    return solid ? l - (T)o.r : (T)o.r - l;
 }
 
-// Where x lies, and for a near point the product A of the obstacles' ramps and its gradient G.
+// Where x lies, and for a near point the product A of the obstacles' ramps and its gradient G, in the type T of the point.
 //     inside  some obstacle has d <= 0: v = 0
 //     far     every obstacle has d >= d0: the unbounded field (A = 1, G = 0; the potential values are not needed)
 //     near    every other point.  Obstacles in list order, those with d >= d0 skipped; Bridson's quintic of r = d / d0,
-//             alpha = r * (1.875f + r2 * (-1.25f + r2 * 0.375f)), r2 = r * r, and its derivative
-//             dalpha = (1.875f * (q * q)) / d0, q = 1.0f - r2; per component G = G * alpha + (A * dalpha) * nrm, then
-//             A = A * alpha.  Overlapping ramps multiply: A stays C1 across every d = d0.
+//             alpha = r * (1.875 + r2 * (-1.25 + r2 * 0.375)), r2 = r * r, and its derivative
+//             dalpha = (1.875 * (q * q)) / d0, q = 1 - r2 (the constants are exact in float); per component
+//             G = G * alpha + (A * dalpha) * nrm, then A = A * alpha.  Overlapping ramps multiply: A stays C1 across
+//             every d = d0.
 constexpr int kBoundFar = 0, kBoundNear = 1, kBoundInside = 2;
-template <int D = 3, typename O>
-WN_EVAL_FN int obstacle_ramp(const O *obs, int nobs, const float x[D], float &A, float G[D])
+template <int D = 3, typename T, typename O>
+WN_EVAL_FN int obstacle_ramp(const O *obs, int nobs, const T x[D], T &A, T G[D])
 {
-    A = 1.0f;
+    A = T(1);
     WN_UNROLL
-    for (int c = 0; c < D; ++c) G[c] = 0.0f;
+    for (int c = 0; c < D; ++c) G[c] = T(0);
     int where = kBoundFar;
     for (int j = 0; j < nobs; ++j) {
-        float nrm[D];
-        const float d = obstacle_distance<D>(obs[j], x, nrm);
-        const float d0 = obs[j].d0;
-        if (d <= 0.0f) return kBoundInside;
+        T nrm[D];
+        const T d = obstacle_distance<D>(obs[j], x, nrm);
+        const T d0 = (T)obs[j].d0;
+        if (d <= T(0)) return kBoundInside;
         if (d >= d0) continue;
         where = kBoundNear;
-        const float r = d / d0;
-        const float r2 = r * r;
-        const float alpha = r * (1.875f + r2 * (-1.25f + r2 * 0.375f));
-        const float q = 1.0f - r2;
-        const float dalpha = (1.875f * (q * q)) / d0;
-        const float ad = A * dalpha;
+        const T r = d / d0;
+        const T r2 = r * r;
+        const T alpha = r * (T(1.875) + r2 * (T(-1.25) + r2 * T(0.375)));
+        const T q = T(1) - r2;
+        const T dalpha = (T(1.875) * (q * q)) / d0;
+        const T ad = A * dalpha;
         WN_UNROLL
         for (int c = 0; c < D; ++c) G[c] = G[c] * alpha + ad * nrm[c];
         A = A * alpha;
@@ -792,20 +798,20 @@ WN_EVAL_FN void multiband_potential_values(const A &a, const float p[3], float p
 // The bounded velocity at p from `where`, A, G of obstacle_ramp: curl(v) writes the unbounded curl c (its entry point's
 // bits), values(psi) the potential values.  inside: 0.  far: c, and values is not called.  near:
 // v = A * c + G x Psi, e.g. v0 = A * c0 + (G1 * psi2 - G2 * psi1), each operation rounded on its own.
-template <typename Curl, typename Values>
-WN_EVAL_FN void bounded_velocity(int where, float A, const float G[3], float v[3], const Curl &curl, const Values &values)
+template <typename T, typename Curl, typename Values>
+WN_EVAL_FN void bounded_velocity(int where, T A, const T G[3], T v[3], const Curl &curl, const Values &values)
 {
     if (where == kBoundInside) {
-        v[0] = v[1] = v[2] = 0.0f;
+        v[0] = v[1] = v[2] = T(0);
         return;
     }
     curl(v);
     if (where == kBoundFar) return;
-    float psi[3];
+    T psi[3];
     values(psi);
-    const float x0 = G[1] * psi[2] - G[2] * psi[1];
-    const float x1 = G[2] * psi[0] - G[0] * psi[2];
-    const float x2 = G[0] * psi[1] - G[1] * psi[0];
+    const T x0 = G[1] * psi[2] - G[2] * psi[1];
+    const T x1 = G[2] * psi[0] - G[0] * psi[2];
+    const T x2 = G[0] * psi[1] - G[1] * psi[0];
     v[0] = A * v[0] + x0;
     v[1] = A * v[1] + x1;
     v[2] = A * v[2] + x2;
@@ -1246,10 +1252,15 @@ WN_EVAL_FN double perlin_fractal_footprint(const Table perm, float x, float y, f
 // & 255).  Of each potential's gradient two partials enter the curl; s holds the six in the order
 //     {d psi0/dy, d psi0/dz, d psi1/dx, d psi1/dz, d psi2/dx, d psi2/dy}.
 // One octave at the double point (x, y, z): floor, fractional parts, fade and fade' once, the hashes three times, each
-// partial from perlin_sample_grad's own expression (its value and the third partial are unused and not computed).
+// partial from perlin_sample_grad's own expression (the third partial is unused and not computed).
 // ADD: s += the octave's partials (turb, fractal_noise); else s = them (noise).
-template <bool ADD, typename Table>
-WN_EVAL_FN void perlin_curl_octave(const Table perm, double x, double y, double z, const int *off, double s[6])
+// VALUES: the value perlin_sample_grad returns -- perlin_exact's bits on the shifted hashes -- enters psi as well:
+// psi[k] = value (noise), psi[k] += weight * value (ADD: perlin_turb's accum += weight * noise, and perlin_fractal's
+// result += noise * amplitude, the same product).  Without VALUES the value is not computed and psi is not read.  The
+// partials are the same expressions either way, so their bits do not depend on the flag.
+template <bool ADD, bool VALUES = false, typename Table>
+WN_EVAL_FN void perlin_curl_octave(const Table perm, double x, double y, double z, const int *off, double s[6],
+                                   double *psi = nullptr, double weight = 1.0)
 {
     const double fx = floor(x), fy = floor(y), fz = floor(z);
     const int X = (int)fx & 255, Y = (int)fy & 255, Z = (int)fz & 255;
@@ -1272,10 +1283,11 @@ WN_EVAL_FN void perlin_curl_octave(const Table perm, double x, double y, double 
                              pgrad(h[6], x, y - 1, z - 1), pgrad(h[7], x - 1, y - 1, z - 1)};
         double P0[3], P1[3], g[3];
         perlin_corner_blend(h, v, w, P0, P1);
-        perlin_sample_grad(a, u, v, w, du, dv, dw, P0, P1, g);
+        const double value = perlin_sample_grad(a, u, v, w, du, dv, dw, P0, P1, g);
         const double first = g[k == 0 ? 1 : 0], second = g[k == 2 ? 1 : 2];
         s[2 * k] = ADD ? s[2 * k] + first : first;
         s[2 * k + 1] = ADD ? s[2 * k + 1] + second : second;
+        if constexpr (VALUES) psi[k] = ADD ? psi[k] + weight * value : value;
     }
 }
 
@@ -1287,26 +1299,33 @@ WN_EVAL_FN void perlin_curl_of(const double s[6], double v[3])
     v[2] = s[2] - s[0];
 }
 
+// The three fields as one walk over their octaves, which gives the curl and, with VALUES, the potential values
+// Psi = (psi0, psi1, psi2) as well (include/wnoise_perlin_bounded.h).
+//
 // The curl of three perlin::noise potentials: each component has the bits of the subtraction of two perlin_grad_exact
-// channels on the shifted cells.
-template <typename Table>
-WN_EVAL_FN void perlin_curl_exact(const Table perm, double x, double y, double z, const int *off, double v[3])
+// channels on the shifted cells; psi_k those of perlin_exact on them.
+template <bool VALUES, typename Table>
+WN_EVAL_FN void perlin_curl_walk(const Table perm, double x, double y, double z, const int *off, double v[3], double *psi)
 {
     double s[6];
-    perlin_curl_octave<false>(perm, x, y, z, off, s);
+    perlin_curl_octave<false, VALUES>(perm, x, y, z, off, s, psi);
     perlin_curl_of(s, v);
 }
 
 // ... of three turb potentials WITHOUT the final fabs (|.| is not differentiable, and the curl of |S| is not
-// divergence-free where S = 0): psi_k = sum_i 2^-i noise_k(2^i p).  Each partial is the plain sum of the octaves' noise
-// partials in octave order, as in perlin_turb_grad, without its sign.  The offsets act on every octave's own cell index.
-// depth == 0: 0 in all three components.
-template <typename Table>
-WN_EVAL_FN void perlin_turb_curl(const Table perm, float x, float y, float z, int depth, const int *off, double v[3])
+// divergence-free where S = 0): psi_k = sum_i 2^-i noise_k(2^i p), accumulated as perlin_turb accumulates it.  Each
+// partial is the plain sum of the octaves' noise partials in octave order, as in perlin_turb_grad, without its sign.  The
+// offsets act on every octave's own cell index.  depth == 0: 0 in all three components and in Psi.
+template <bool VALUES, typename Table>
+WN_EVAL_FN void perlin_turb_curl_walk(const Table perm, float x, float y, float z, int depth, const int *off, double v[3],
+                                      double *psi)
 {
     double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    double weight = 1.0;
+    if constexpr (VALUES) psi[0] = psi[1] = psi[2] = 0.0;
     for (int i = 0; i < depth; ++i) {
-        perlin_curl_octave<true>(perm, (double)x, (double)y, (double)z, off, s);
+        perlin_curl_octave<true, VALUES>(perm, (double)x, (double)y, (double)z, off, s, psi, weight);
+        if constexpr (VALUES) weight *= 0.5;
         x *= 2.0f;
         y *= 2.0f;
         z *= 2.0f;
@@ -1315,21 +1334,83 @@ WN_EVAL_FN void perlin_turb_curl(const Table perm, float x, float y, float z, in
 }
 
 // ... of three fractal_noise potentials: each partial is (sum of the six octaves' noise partials) / max_value, as
-// perlin_fractal_grad forms it.
-template <typename Table>
-WN_EVAL_FN void perlin_fractal_curl(const Table perm, float x, float y, float z, const int *off, double v[3])
+// perlin_fractal_grad forms it; psi_k is perlin_fractal's result / max_value.
+template <bool VALUES, typename Table>
+WN_EVAL_FN void perlin_fractal_curl_walk(const Table perm, float x, float y, float z, const int *off, double v[3], double *psi)
 {
     double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     double amplitude = 1.0, frequency = 1.0, max_value = 0.0;
+    if constexpr (VALUES) psi[0] = psi[1] = psi[2] = 0.0;
     for (int i = 0; i < 6; ++i) {
-        perlin_curl_octave<true>(perm, x * frequency, y * frequency, z * frequency, off, s);
+        perlin_curl_octave<true, VALUES>(perm, x * frequency, y * frequency, z * frequency, off, s, psi, amplitude);
         max_value += amplitude;
         amplitude *= 0.5;
         frequency *= 2.0;
     }
     WN_UNROLL
     for (int j = 0; j < 6; ++j) s[j] = s[j] / max_value;
+    if constexpr (VALUES) {
+        WN_UNROLL
+        for (int k = 0; k < 3; ++k) psi[k] = psi[k] / max_value;
+    }
     perlin_curl_of(s, v);
+}
+
+// The curl alone (wn_perlin_curl_points, _points_vec3, the grids' generic kernel, advection): the walks without values.
+template <typename Table>
+WN_EVAL_FN void perlin_curl_exact(const Table perm, double x, double y, double z, const int *off, double v[3])
+{
+    perlin_curl_walk<false>(perm, x, y, z, off, v, nullptr);
+}
+template <typename Table>
+WN_EVAL_FN void perlin_turb_curl(const Table perm, float x, float y, float z, int depth, const int *off, double v[3])
+{
+    perlin_turb_curl_walk<false>(perm, x, y, z, depth, off, v, nullptr);
+}
+template <typename Table>
+WN_EVAL_FN void perlin_fractal_curl(const Table perm, float x, float y, float z, const int *off, double v[3])
+{
+    perlin_fractal_curl_walk<false>(perm, x, y, z, off, v, nullptr);
+}
+
+// ---- solid boundaries of that curl field (include/wnoise_perlin_bounded.h; absent from the reference) -------------------
+// `kind`: 0 noise, 1 turb, 2 fractal_noise (WN_PERLIN_CURL_*).  The point type P is double (wn_perlin_curl_points: noise
+// only) or float (wn_perlin_curl_points_vec3: noise widens it, turb and fractal_noise take it as it is).
+template <int KIND, bool VALUES, typename P, typename Table>
+WN_EVAL_FN void perlin_curl_kind_walk(const Table perm, P x, P y, P z, int depth, const int *off, double v[3], double *psi)
+{
+    static_assert(KIND >= 0 && KIND <= 2, "noise, turb or fractal_noise");
+    if constexpr (KIND == 0) perlin_curl_walk<VALUES>(perm, (double)x, (double)y, (double)z, off, v, psi);
+    else if constexpr (KIND == 1) perlin_turb_curl_walk<VALUES>(perm, (float)x, (float)y, (float)z, depth, off, v, psi);
+    else perlin_fractal_curl_walk<VALUES>(perm, (float)x, (float)y, (float)z, off, v, psi);
+}
+
+// The potential values alone: the walk above with its partials unused.
+template <int KIND, typename P, typename Table>
+WN_EVAL_FN void perlin_curl_potential(const Table perm, P x, P y, P z, int depth, const int *off, double psi[3])
+{
+    double v[3];
+    perlin_curl_kind_walk<KIND, true>(perm, x, y, z, depth, off, v, psi);
+}
+
+// The bounded velocity at the point the evaluator receives: the ramp (obstacle_ramp in double) at that point widened to
+// double, then bounded_velocity around ONE walk.  An inside point evaluates nothing; every other point takes the VALUES
+// walk, whose partials are those of the plain walk, so a far point and nobs == 0 carry the unbounded entry point's bits and
+// a near point composes the bits of the curl and potential entry points.  The value costs two lerps and one product-sum per
+// potential and octave beside the six partials, which is why a far lane is not given a walk of its own.
+template <int KIND, typename P, typename Table, typename O>
+WN_EVAL_FN void perlin_curl_bounded(const Table perm, P x, P y, P z, int depth, const int *off, const O *obs, int nobs,
+                                    double v[3])
+{
+    const double q[3] = {(double)x, (double)y, (double)z};
+    double A, G[3], walked[3];
+    const int where = obstacle_ramp(obs, nobs, q, A, G);
+    bounded_velocity(
+        where, A, G, v, [&](double *c) { perlin_curl_kind_walk<KIND, true>(perm, x, y, z, depth, off, c, walked); },
+        [&](double *psi) {
+            WN_UNROLL
+            for (int k = 0; k < 3; ++k) psi[k] = walked[k];
+        });
 }
 
 // ---- the texture adaptors' per-point arithmetic (texture.h:37-43, 67-107) ----------------------------------------------

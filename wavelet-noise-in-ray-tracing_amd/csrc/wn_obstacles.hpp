@@ -1,6 +1,7 @@
 // wn_obstacles.hpp -- the obstacle list of include/wnoise_bounded.h as the kernels take it: by value in the launch arguments
 // (16 x 32 bytes).  It is the same for every lane, so wn::obstacle_ramp's loop reads it with scalar loads and branches on the
-// kind as a wave.  Shared by wn_wavelet_bounded.hip (point lists, advection) and wn_wavelet_bounded_bricks.hip (brick lists).
+// kind as a wave.  Shared by wn_wavelet_bounded.hip (point lists, advection), wn_wavelet_bounded_bricks.hip (brick lists) and
+// wn_perlin_bounded.hip (the Perlin field, whose ramp is the double instantiation).
 #pragma once
 
 #include "wn_internal.hpp"

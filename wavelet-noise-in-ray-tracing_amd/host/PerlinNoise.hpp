@@ -10,6 +10,7 @@
 #include "scalar_eval.h"
 #include "wn_host.hpp"
 #include "wnoise_perlin_advect.h"
+#include "wnoise_perlin_bounded.h"
 #include "wnoise_perlin_curl.h"
 
 class PerlinNoise {
@@ -83,6 +84,45 @@ class PerlinNoise {
                      double *traj = nullptr) const
     {
         wnhost::perlin_advect_batch(perm_, xyz, n, WN_PERLIN_CURL_NOISE, 0, curl_offsets(offsets9), a, xyz_out, traj);
+    }
+
+    // additive: that field with solid boundaries (include/wnoise_perlin_bounded.h; the obstacle list is wnoise_bounded.h's),
+    // NOISE potentials only.  curl_potential: Psi; curl_bounded: v = A curl Psi + grad A x Psi; advect_curl_bounded:
+    // advect_curl through it.  Scalar on the host, batched through the GPU; bit-identical to each other.
+    void curl_potential(double x, double y, double z, double psi[3], const int *offsets9 = nullptr) const
+    {
+        wnhost_perlin_curl_potential(p.data(), x, y, z, curl_offsets(offsets9), psi);
+    }
+    void curl_potential(const double *xyz, size_t n, double *out3, const int *offsets9 = nullptr) const
+    {
+        wnhost::perlin_bounded_points_batch(perm_, xyz, n, WN_PERLIN_CURL_NOISE, 0, curl_offsets(offsets9), nullptr, -1, out3);
+    }
+    void curl_bounded(double x, double y, double z, const wn_obstacle *obstacles, int nobs, double v[3],
+                      const int *offsets9 = nullptr) const
+    {
+        const double xyz[3] = {x, y, z};
+        if (wnhost_perlin_curl_bounded(p.data(), WN_PERLIN_CURL_NOISE, 0, xyz, curl_offsets(offsets9), obstacles, nobs, v))
+            throw std::runtime_error("curl_bounded: an obstacle list that include/wnoise_bounded.h refuses");
+    }
+    void curl_bounded(const double *xyz, size_t n, const wn_obstacle *obstacles, int nobs, double *out3,
+                      const int *offsets9 = nullptr) const
+    {
+        wnhost::perlin_bounded_points_batch(perm_, xyz, n, WN_PERLIN_CURL_NOISE, 0, curl_offsets(offsets9), obstacles,
+                                            nobs < 0 ? WN_MAX_OBSTACLES + 1 : nobs, out3);
+    }
+    void advect_curl_bounded(double x, double y, double z, const wn_advect &a, const int *offsets9, const wn_obstacle *obstacles,
+                             int nobs, double p_out[3], double *traj = nullptr) const
+    {
+        const double xyz[3] = {x, y, z};
+        if (wnhost_perlin_curl_bounded_advect(p.data(), WN_PERLIN_CURL_NOISE, 0, xyz, curl_offsets(offsets9), obstacles, nobs, &a,
+                                              p_out, traj))
+            throw std::runtime_error("advect_curl_bounded: what advect_curl or curl_bounded refuses");
+    }
+    void advect_curl_bounded(const double *xyz, size_t n, const wn_advect &a, const int *offsets9, const wn_obstacle *obstacles,
+                             int nobs, double *xyz_out, double *traj = nullptr) const
+    {
+        wnhost::perlin_bounded_advect_batch(perm_, xyz, n, WN_PERLIN_CURL_NOISE, 0, curl_offsets(offsets9), obstacles, nobs, a,
+                                            xyz_out, traj);
     }
 
     const std::vector<int> &table() const { return p; }

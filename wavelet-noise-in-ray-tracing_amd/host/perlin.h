@@ -18,6 +18,7 @@
 #include "vec3.h"
 #include "wn_host.hpp"
 #include "wnoise_perlin_advect.h"
+#include "wnoise_perlin_bounded.h"
 #include "wnoise_perlin_curl.h"
 #include "wnoise_perlin_footprint.h"
 
@@ -168,6 +169,60 @@ class perlin {
         wnhost::perlin_advect_batch(perm_, xyz, n, kind, depth, offsets9 ? offsets9 : default_curl_offsets(), a, xyz_out, traj);
     }
 
+    // ---- additive: that curl field with solid boundaries (absent from the reference; include/wnoise_perlin_bounded.h, whose
+    // obstacle list is wnoise_bounded.h's: at most 16 spheres, containers and half-spaces in the coordinates of the points).
+    // curl_potential: Psi = (psi0, psi1, psi2), the potentials the curl members differentiate.  curl_bounded:
+    // v = A curl Psi + grad A x Psi, zero inside a solid, the curl member's bits far from all of them.  advect_curl_bounded:
+    // advect_curl through it.  kind, depth and offsets9 as in advect_curl; NOISE evaluates at the double point, TURB and
+    // FRACTAL at the point rounded to float.  Scalar members on the host (scalar_eval.h), batched ones (host pointers; double
+    // points: NOISE only) through the GPU; bit-identical to each other.
+    void curl_potential(const double xyz[3], int kind, int depth, const int *offsets9, double psi[3]) const
+    {
+        const int *off = offsets9 ? offsets9 : default_curl_offsets();
+        const float q[3] = {(float)xyz[0], (float)xyz[1], (float)xyz[2]};
+        if (kind == WN_PERLIN_CURL_NOISE) wnhost_perlin_curl_potential(p.data(), xyz[0], xyz[1], xyz[2], off, psi);
+        else if (kind == WN_PERLIN_CURL_TURB && depth >= 0) wnhost_perlin_turb_curl_potential(p.data(), q, depth, off, psi);
+        else if (kind == WN_PERLIN_CURL_FRACTAL) wnhost_perlin_fractal_curl_potential(p.data(), q, off, psi);
+        else throw std::runtime_error("curl_potential: a kind outside 0..2 or a negative depth");
+    }
+    void curl_potential(const double *xyz, size_t n, const int *offsets9, double *out3) const
+    {
+        wnhost::perlin_bounded_points_batch(perm_, xyz, n, WN_PERLIN_CURL_NOISE, 0, curl_offsets_int(offsets9), nullptr, -1, out3);
+    }
+    void curl_potential(const float *xyz, size_t n, int kind, int depth, const int *offsets9, double *out3) const
+    {
+        wnhost::perlin_bounded_points_batch(perm_, xyz, n, kind, depth, curl_offsets_int(offsets9), nullptr, -1, out3);
+    }
+    void curl_bounded(const double xyz[3], int kind, int depth, const int *offsets9, const wn_obstacle *obstacles, int nobs,
+                      double v[3]) const
+    {
+        if (wnhost_perlin_curl_bounded(p.data(), kind, depth, xyz, curl_offsets_int(offsets9), obstacles, nobs, v))
+            throw std::runtime_error("curl_bounded: a kind outside 0..2, a negative depth, or an obstacle list that "
+                                     "include/wnoise_bounded.h refuses");
+    }
+    void curl_bounded(const double *xyz, size_t n, const int *offsets9, const wn_obstacle *obstacles, int nobs, double *out3) const
+    {
+        wnhost::perlin_bounded_points_batch(perm_, xyz, n, WN_PERLIN_CURL_NOISE, 0, curl_offsets_int(offsets9), obstacles,
+                                            nobs < 0 ? WN_MAX_OBSTACLES + 1 : nobs, out3);
+    }
+    void curl_bounded(const float *xyz, size_t n, int kind, int depth, const int *offsets9, const wn_obstacle *obstacles, int nobs,
+                      double *out3) const
+    {
+        wnhost::perlin_bounded_points_batch(perm_, xyz, n, kind, depth, curl_offsets_int(offsets9), obstacles,
+                                            nobs < 0 ? WN_MAX_OBSTACLES + 1 : nobs, out3);
+    }
+    void advect_curl_bounded(const double xyz[3], const wn_advect &a, int kind, int depth, const int *offsets9,
+                             const wn_obstacle *obstacles, int nobs, double p_out[3], double *traj = nullptr) const
+    {
+        if (wnhost_perlin_curl_bounded_advect(p.data(), kind, depth, xyz, curl_offsets_int(offsets9), obstacles, nobs, &a, p_out, traj))
+            throw std::runtime_error("advect_curl_bounded: what advect_curl or curl_bounded refuses");
+    }
+    void advect_curl_bounded(const double *xyz, size_t n, const wn_advect &a, int kind, int depth, const int *offsets9,
+                             const wn_obstacle *obstacles, int nobs, double *xyz_out, double *traj = nullptr) const
+    {
+        wnhost::perlin_bounded_advect_batch(perm_, xyz, n, kind, depth, curl_offsets_int(offsets9), obstacles, nobs, a, xyz_out, traj);
+    }
+
     // ---- additive: octave limiting by a footprint per sample (absent from the reference; include/wnoise_perlin_footprint.h)
     // s = log2 of the sample's footprint in the noise space of q: octave i runs while (s + bias) + i < 0; fade: the finest
     // surviving octave enters with min(1, -t_i) instead of popping.  Scalar members: evaluated on the host, bit-identical
@@ -243,6 +298,7 @@ class perlin {
         else wnhost::check(wn_perlin_fractal_footprint_grad_points(perm_, in.as<float>(), fp.as<float>(), n, octaves, bias, f, res.as<double>(), nullptr), "wn_perlin_fractal_footprint_grad_points");
         res.download(out);
     }
+    static const int *curl_offsets_int(const int *offsets9) { return offsets9 ? offsets9 : default_curl_offsets(); }
     static const int32_t *curl_offsets(const int *offsets9)
     {
         static_assert(sizeof(int) == sizeof(int32_t), "offsets are int32");

@@ -13,6 +13,7 @@
 #include "wnoise_bounded.h"
 #include "wnoise_bounded2d.h"
 #include "wnoise_curl2d.h"
+#include "wnoise_perlin_bounded.h"
 #include "wnoise_perlin_curl.h"
 
 namespace {
@@ -305,6 +306,50 @@ int wnhost_perlin_curl_advect(const int *perm, int kind, int depth, const double
         if (kind == WN_PERLIN_CURL_NOISE) wn::perlin_curl_exact(perm, q[0], q[1], q[2], offsets9, v);
         else if (kind == WN_PERLIN_CURL_TURB) wn::perlin_turb_curl(perm, (float)q[0], (float)q[1], (float)q[2], depth, offsets9, v);
         else wn::perlin_fractal_curl(perm, (float)q[0], (float)q[1], (float)q[2], offsets9, v);
+    };
+    advect_one<double, 3>(*a, p_in, p_out, traj, velocity);
+    return 0;
+}
+
+void wnhost_perlin_curl_potential(const int *perm, double x, double y, double z, const int offsets9[9], double psi[3])
+{
+    wn::perlin_curl_potential<WN_PERLIN_CURL_NOISE>(perm, x, y, z, 0, offsets9, psi);
+}
+
+void wnhost_perlin_turb_curl_potential(const int *perm, const float q[3], int depth, const int offsets9[9], double psi[3])
+{
+    wn::perlin_curl_potential<WN_PERLIN_CURL_TURB>(perm, q[0], q[1], q[2], depth, offsets9, psi);
+}
+
+void wnhost_perlin_fractal_curl_potential(const int *perm, const float q[3], const int offsets9[9], double psi[3])
+{
+    wn::perlin_curl_potential<WN_PERLIN_CURL_FRACTAL>(perm, q[0], q[1], q[2], 0, offsets9, psi);
+}
+
+int wnhost_perlin_curl_bounded(const int *perm, int kind, int depth, const double p[3], const int offsets9[9],
+                               const wn_obstacle *obstacles, int nobs, double v[3])
+{
+    if (kind < WN_PERLIN_CURL_NOISE || kind > WN_PERLIN_CURL_FRACTAL || (kind == WN_PERLIN_CURL_TURB && depth < 0)) return 1;
+    if (wn::obstacle_fault(obstacles, nobs)) return 1;
+    if (kind == WN_PERLIN_CURL_NOISE)
+        wn::perlin_curl_bounded<WN_PERLIN_CURL_NOISE>(perm, p[0], p[1], p[2], 0, offsets9, obstacles, nobs, v);
+    else if (kind == WN_PERLIN_CURL_TURB)
+        wn::perlin_curl_bounded<WN_PERLIN_CURL_TURB>(perm, (float)p[0], (float)p[1], (float)p[2], depth, offsets9, obstacles,
+                                                     nobs, v);
+    else
+        wn::perlin_curl_bounded<WN_PERLIN_CURL_FRACTAL>(perm, (float)p[0], (float)p[1], (float)p[2], 0, offsets9, obstacles,
+                                                        nobs, v);
+    return 0;
+}
+
+int wnhost_perlin_curl_bounded_advect(const int *perm, int kind, int depth, const double p_in[3], const int offsets9[9],
+                                      const wn_obstacle *obstacles, int nobs, const wn_advect *a, double p_out[3], double *traj)
+{
+    if (kind < WN_PERLIN_CURL_NOISE || kind > WN_PERLIN_CURL_FRACTAL || (kind == WN_PERLIN_CURL_TURB && depth < 0)) return 1;
+    if (wn::obstacle_fault(obstacles, nobs)) return 1;
+    if (!advect_ok(a, traj)) return 1;
+    const auto velocity = [&](const double q[3], double v[3]) {
+        wnhost_perlin_curl_bounded(perm, kind, depth, q, offsets9, obstacles, nobs, v);
     };
     advect_one<double, 3>(*a, p_in, p_out, traj, velocity);
     return 0;

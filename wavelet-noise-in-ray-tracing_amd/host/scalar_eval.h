@@ -169,6 +169,25 @@ WNHOST_API void wnhost_perlin_fractal_curl(const int *perm, const float q[3], co
 // and writes nothing when kind, depth or `a` is one that entry point refuses.
 WNHOST_API int wnhost_perlin_curl_advect(const int *perm, int kind, int depth, const double p_in[3], const int offsets9[9],
                                          const struct wn_advect *a, double p_out[3], double *traj);
+// Those curl fields with solid boundaries (absent from the reference; include/wnoise_perlin_bounded.h, whose wn_obstacle list
+// is wnoise_bounded.h's).  The potential values Psi = (psi0, psi1, psi2) on the shifted cells: noise / turb's accumulated sum
+// before its fabs / fractal_noise -- with all nine offsets 0 the bits of wnhost_perlin, (up to the sign) wnhost_perlin_turb
+// and wnhost_perlin_fractal: the bits of wn_perlin_curl_potential_points_f64 / _points_vec3.
+WNHOST_API void wnhost_perlin_curl_potential(const int *perm, double x, double y, double z, const int offsets9[9], double psi[3]);
+WNHOST_API void wnhost_perlin_turb_curl_potential(const int *perm, const float q[3], int depth, const int offsets9[9],
+                                                  double psi[3]);
+WNHOST_API void wnhost_perlin_fractal_curl_potential(const int *perm, const float q[3], const int offsets9[9], double psi[3]);
+// The bounded velocity v = A curl Psi + grad A x Psi at p: NOISE evaluates the ramp and the field at the double point p, TURB
+// and FRACTAL at (float)p (the ramp at that float widened to double) -- zero inside a solid, the bits of wnhost_perlin_curl /
+// _turb_curl / _fractal_curl far from all of them and with nobs == 0: the bits of wn_perlin_curl_bounded_points_f64 /
+// _points_vec3.  wnhost_perlin_curl_bounded_advect traces one particle through it as wnhost_perlin_curl_advect does through
+// the unbounded field: the bits of wn_perlin_curl_bounded_advect_points_f64.  Both return 0, or 1 and write nothing for a kind,
+// depth, obstacle list or `a` that the entry point refuses.
+WNHOST_API int wnhost_perlin_curl_bounded(const int *perm, int kind, int depth, const double p[3], const int offsets9[9],
+                                          const struct wn_obstacle *obstacles, int nobs, double v[3]);
+WNHOST_API int wnhost_perlin_curl_bounded_advect(const int *perm, int kind, int depth, const double p_in[3],
+                                                 const int offsets9[9], const struct wn_obstacle *obstacles, int nobs,
+                                                 const struct wn_advect *a, double p_out[3], double *traj);
 // grey level of texture::value (texture.h); use_3d = 0: the 2-D tile and branch; coef == NULL: the no-tile grey
 WNHOST_API float wnhost_wavelet_texture_value(const float *coef, int n, int use_3d, double scale, int octave,
                                               const float xyz[3]);                    // texture.h:67-107

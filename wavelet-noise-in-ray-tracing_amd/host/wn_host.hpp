@@ -13,6 +13,7 @@
 
 #include "wnoise.h"
 #include "wnoise_perlin_advect.h"
+#include "wnoise_perlin_bounded.h"
 
 namespace wnhost {
 
@@ -91,6 +92,44 @@ inline void perlin_advect_batch(const wn_perm *perm, const double *xyz, size_t n
           "wn_perlin_curl_advect_points");
     if (snaps) check(wn_copy_d2h(traj, path.get(), traj_bytes, nullptr), "wn_copy_d2h");
     pos.download(xyz_out);
+}
+
+// The batched advect_curl_bounded members of perlin and PerlinNoise: perlin_advect_batch around
+// wn_perlin_curl_bounded_advect_points_f64 (include/wnoise_perlin_bounded.h).
+inline void perlin_bounded_advect_batch(const wn_perm *perm, const double *xyz, size_t n, int kind, int depth, const int *offsets9,
+                                        const wn_obstacle *obstacles, int nobs, const wn_advect &a, double *xyz_out, double *traj)
+{
+    if (!n) return;
+    const bool snaps = a.traj_every >= 1 && a.steps >= 0 && traj;
+    const size_t traj_bytes = snaps ? ((size_t)(a.steps / a.traj_every) + 1) * 3 * n * sizeof(double) : 0;
+    DeviceBuffer pos(3 * n * sizeof(double)), path(traj_bytes ? traj_bytes : sizeof(double));
+    pos.upload(xyz);
+    check(wn_perlin_curl_bounded_advect_points_f64(perm, pos.as<double>(), n, kind, depth, reinterpret_cast<const int32_t *>(offsets9),
+                                               obstacles, nobs, &a, pos.as<double>(), snaps ? path.as<double>() : nullptr, nullptr),
+          "wn_perlin_curl_bounded_advect_points_f64");
+    if (snaps) check(wn_copy_d2h(traj, path.get(), traj_bytes, nullptr), "wn_copy_d2h");
+    pos.download(xyz_out);
+}
+
+// The batched curl_potential and curl_bounded members (host pointers): n points of three T (double: the NOISE entry points on
+// doubles; float: the _vec3 ones) in, n records of three doubles out.  obstacles == nullptr with nobs < 0: the potential
+// values; otherwise the bounded velocity.
+template <typename T>
+inline void perlin_bounded_points_batch(const wn_perm *perm, const T *xyz, size_t n, int kind, int depth, const int *offsets9,
+                                        const wn_obstacle *obstacles, int nobs, double *out3)
+{
+    if (!n) return;
+    DeviceBuffer in(3 * n * sizeof(T)), res(3 * n * sizeof(double));
+    in.upload(xyz);
+    const int32_t *off = reinterpret_cast<const int32_t *>(offsets9);
+    if constexpr (sizeof(T) == sizeof(double)) {
+        if (nobs < 0) check(wn_perlin_curl_potential_points_f64(perm, in.as<double>(), n, off, res.as<double>(), nullptr), "wn_perlin_curl_potential_points_f64");
+        else check(wn_perlin_curl_bounded_points_f64(perm, in.as<double>(), n, off, obstacles, nobs, res.as<double>(), nullptr), "wn_perlin_curl_bounded_points_f64");
+    } else {
+        if (nobs < 0) check(wn_perlin_curl_potential_points_f32(perm, in.as<float>(), n, kind, depth, off, res.as<double>(), nullptr), "wn_perlin_curl_potential_points_f32");
+        else check(wn_perlin_curl_bounded_points_f32(perm, in.as<float>(), n, kind, depth, off, obstacles, nobs, res.as<double>(), nullptr), "wn_perlin_curl_bounded_points_f32");
+    }
+    res.download(out3);
 }
 
 } // namespace wnhost

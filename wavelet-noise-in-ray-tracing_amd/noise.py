@@ -738,6 +738,87 @@ class perlin:
                                                 self._curl_offsets(offsets), C.byref(a), _ptr(out), _ptr(traj), _stream()))
         return out if traj is None else (out, traj)
 
+    # -- that curl field with solid boundaries (include/wnoise_perlin_bounded.h; absent from the reference): the potential
+    # values Psi, the bounded velocity, and particles moved through it.  (N, 3) float64 CUDA tensors.
+    def _potential(self, pts, kind, depth, offsets):
+        out = torch.empty((pts.shape[0], 3), dtype=torch.float64, device="cuda")
+        check(_lib.wn_perlin_curl_potential_points_f32(self._h, _ptr(pts), pts.shape[0], kind, int(depth),
+                                                        self._curl_offsets(offsets), _ptr(out), _stream()))
+        return out
+
+    def noise_potential(self, p, offsets=None):
+        """The vector potential Psi = (psi0, psi1, psi2) that noise_curl differentiates: noise() on cells shifted by the
+        whole-cell `offsets`.  float64 input follows noise(double, double, double) (wn_perlin_curl_potential_points_f64),
+        anything else noise(const point3&) on floats (wn_perlin_curl_potential_points_f32)."""
+        is64 = (p.dtype == torch.float64) if isinstance(p, torch.Tensor) else (np.asarray(p).dtype == np.float64)
+        if not is64:
+            return self._potential(_dev(p, torch.float32).reshape(-1, 3), _capi.WN_PERLIN_CURL_NOISE, 0, offsets)
+        pts = _dev(p, torch.float64).reshape(-1, 3)
+        out = torch.empty((pts.shape[0], 3), dtype=torch.float64, device="cuda")
+        check(_lib.wn_perlin_curl_potential_points_f64(self._h, _ptr(pts), pts.shape[0], self._curl_offsets(offsets), _ptr(out),
+                                                   _stream()))
+        return out
+
+    def turb_potential(self, p, depth=7, offsets=None):
+        """The potential of turb_curl: turb's octave sum before its fabs, per shifted potential."""
+        return self._potential(_dev(p, torch.float32).reshape(-1, 3), _capi.WN_PERLIN_CURL_TURB, depth, offsets)
+
+    def fractal_noise_potential(self, p, offsets=None):
+        """The potential of fractal_noise_curl: fractal_noise per shifted potential."""
+        return self._potential(_dev(p, torch.float32).reshape(-1, 3), _capi.WN_PERLIN_CURL_FRACTAL, 0, offsets)
+
+    def _curl_bounded(self, pts, kind, depth, obstacles, offsets):
+        out = torch.empty((pts.shape[0], 3), dtype=torch.float64, device="cuda")
+        obs, nobs = WaveletNoise._obstacles(obstacles)
+        check(_lib.wn_perlin_curl_bounded_points_f32(self._h, _ptr(pts), pts.shape[0], kind, int(depth),
+                                                      self._curl_offsets(offsets), obs, nobs, _ptr(out), _stream()))
+        return out
+
+    def noise_curl_bounded(self, p, obstacles, offsets=None):
+        """noise_curl with its potential faded to zero towards every solid of `obstacles` (wn_perlin_curl_bounded_points_f64 /
+        _points_vec3): v = A curl Psi + grad A x Psi in float64, still divergence-free, with no normal component on a
+        solid's surface.  `obstacles`: the list WaveletNoise.evaluate3DCurlBounded takes, in the coordinates of p.  A point
+        inside a solid gets 0, a point at distance >= d0 from all of them (and obstacles=[]) the bits of noise_curl."""
+        is64 = (p.dtype == torch.float64) if isinstance(p, torch.Tensor) else (np.asarray(p).dtype == np.float64)
+        if not is64:
+            return self._curl_bounded(_dev(p, torch.float32).reshape(-1, 3), _capi.WN_PERLIN_CURL_NOISE, 0, obstacles, offsets)
+        pts = _dev(p, torch.float64).reshape(-1, 3)
+        out = torch.empty((pts.shape[0], 3), dtype=torch.float64, device="cuda")
+        obs, nobs = WaveletNoise._obstacles(obstacles)
+        check(_lib.wn_perlin_curl_bounded_points_f64(self._h, _ptr(pts), pts.shape[0], self._curl_offsets(offsets), obs, nobs,
+                                                 _ptr(out), _stream()))
+        return out
+
+    def turb_curl_bounded(self, p, obstacles, depth=7, offsets=None):
+        """noise_curl_bounded around turb_curl and turb_potential."""
+        return self._curl_bounded(_dev(p, torch.float32).reshape(-1, 3), _capi.WN_PERLIN_CURL_TURB, depth, obstacles, offsets)
+
+    def fractal_noise_curl_bounded(self, p, obstacles, offsets=None):
+        """noise_curl_bounded around fractal_noise_curl and fractal_noise_potential."""
+        return self._curl_bounded(_dev(p, torch.float32).reshape(-1, 3), _capi.WN_PERLIN_CURL_FRACTAL, 0, obstacles, offsets)
+
+    def advect_curl_bounded(self, pts, h, steps, obstacles, kind="noise", depth=7, method="rk4", offsets=None, gain=1.0,
+                            drift=None, trajectory_every=0):
+        """advect_curl through gain * v + drift with the bounded v of noise_curl_bounded / turb_curl_bounded /
+        fractal_noise_curl_bounded, all steps inside the kernel (wn_perlin_curl_bounded_advect_points_f64): particles flow
+        around the solids.  A particle inside one moves by drift alone."""
+        methods = WaveletNoise._ADVECT_METHODS
+        if method not in methods:
+            raise ValueError(f"method: one of {sorted(methods)}")
+        if kind not in self._CURL_KINDS:
+            raise ValueError(f"kind: one of {sorted(self._CURL_KINDS)}")
+        obs, nobs = WaveletNoise._obstacles(obstacles)
+        pts = _dev(pts, torch.float64).reshape(-1, 3)
+        n, steps, every = pts.shape[0], int(steps), int(trajectory_every)
+        a = _capi.wn_advect(methods[method], steps, float(h), float(gain),
+                            (C.c_float * 3)(*([0.0] * 3 if drift is None else [float(x) for x in drift])), every)
+        out = torch.empty((n, 3), dtype=torch.float64, device="cuda")
+        traj = torch.empty((steps // every + 1, n, 3), dtype=torch.float64, device="cuda") if every >= 1 and steps >= 0 else None
+        check(_lib.wn_perlin_curl_bounded_advect_points_f64(self._h, _ptr(pts), n, self._CURL_KINDS[kind], int(depth),
+                                                        self._curl_offsets(offsets), obs, nobs, C.byref(a), _ptr(out),
+                                                        _ptr(traj), _stream()))
+        return out if traj is None else (out, traj)
+
     # -- octave limiting by a footprint per sample (absent from the reference; include/wnoise_perlin_footprint.h)
     def _footprint(self, fn, p, s, octaves, bias, fade, channels):
         pts = _dev(p, torch.float32).reshape(-1, 3)
