@@ -19,7 +19,12 @@ Tolerance of the default tier, per component k (a = (k+1) % 3, b = (k+2) % 3), a
 the derivation of tests/test_bounded_host.py::test_host_twin_against_float64 with the default tier's bounds in place of the
 exact evaluators': T the curl bricks' 2 G (tests/test_gpu_brick_fields.py's Env.tol), V the 1e-5 that
 tests/test_gpu_bricks.py holds the default-tier value bricks to, dA and dG the ramp's float32 rounding bounds of
-tests/_ref64_bounded.py (zero against the exact tier, whose ramp has the same bits)."""
+tests/_ref64_bounded.py (zero against the exact tier, whose ramp has the same bits).  component_tolerance is that expression.
+
+This module stays within 5 bricks of the origin in x and y; its one far test moves the volume and the scene in z on den 512,
+where every coordinate is exact in float32.  Far from the origin on all three axes, on lattices that round and with a sphere
+in every listed brick: tests/test_gpu_brick_fields_far.py (which imports component_tolerance) and the field-bricks family of
+tests/test_gpu_lattice_sweep.py."""
 import ctypes as C
 import os
 import re
@@ -87,6 +92,19 @@ def sixteen(h):
 
 def far_away(h):
     return [("sphere", (1000.0 * h, -500.0 * h, 2000.0 * h), 3.0 * h, 2.0 * h), ("halfspace", (0.0, 0.0, 1.0), -900.0 * h, 5.0 * h)]
+
+
+def component_tolerance(T, Ar, G, dA, dG, c, psi):
+    """The module text's tolerance, (N, 3): T the curl bricks' 2 G; A (N,), G (N, 3), dA (N,), dG (N,) of
+    tests/_ref64_bounded.py's ramp, c (N, 3) the unbounded curl and psi (N, 3) the potential values in float64.
+    tests/test_gpu_brick_fields_far.py holds the far rows to the same expression."""
+    tol = np.empty((len(Ar), 3))
+    for k in range(3):
+        a, b = (k + 1) % 3, (k + 2) % 3
+        tol[:, k] = T * Ar + V_TOL * (np.abs(G[:, a]) + np.abs(G[:, b])) + dA * np.abs(c[:, k]) \
+            + dG * (np.abs(psi[:, a]) + np.abs(psi[:, b])) \
+            + 8.0 * EPS * (Ar * np.abs(c[:, k]) + np.abs(G[:, a] * psi[:, b]) + np.abs(G[:, b] * psi[:, a]))
+    return tol
 
 
 def classes(obstacles, pts):
@@ -222,13 +240,7 @@ class Env(tbf.Env):
                 psi = np.stack([RG.multiband_grad_points(t, pts, s, first, nb, weights(nb), VAR)[:, 0]
                                 for t in RC.rolled_tiles(self.coefs[tile], MIXED)], axis=1)
         want = R.velocity(where, Ar, G, c, psi)
-        T = self.tol("curl", octave, mb)
-        tol = np.empty((n, 3))
-        for k in range(3):
-            a, b = (k + 1) % 3, (k + 2) % 3
-            tol[:, k] = T * Ar + V_TOL * (np.abs(G[:, a]) + np.abs(G[:, b])) + dA * np.abs(c[:, k]) \
-                + dG * (np.abs(psi[:, a]) + np.abs(psi[:, b])) \
-                + 8.0 * EPS * (Ar * np.abs(c[:, k]) + np.abs(G[:, a] * psi[:, b]) + np.abs(G[:, b] * psi[:, a]))
+        tol = component_tolerance(self.tol("curl", octave, mb), Ar, G, dA, dG, c, psi)
         shape = (len(bricks), 512, 3)
         return want.reshape(shape).transpose(2, 0, 1), tol.reshape(shape).transpose(2, 0, 1)
 

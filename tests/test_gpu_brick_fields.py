@@ -9,7 +9,11 @@ The references are computed once per lattice and shared: the dense derivative gr
 (wavelet_gradient_volume / curl_volume and their multiband forms), gathered brick by brick; the point entries at the samples'
 float coordinates; the float64 references of tests/_ref64_grad.py and tests/_ref64_curl.py with their tolerance() -- G =
 1e-5 |out_scale| (multiband: * sum_b |w_b| 2^(first_band+b+1) / out_div) for the gradient, 2 G for the curl.  The curl calls
-use tests/test_gpu_curl.py's MIXED offsets, and the library's default offsets once."""
+use tests/test_gpu_curl.py's MIXED offsets, and the library's default offsets once.
+
+This module stays within 5 bricks of the origin in x and y; its one far test moves the volume in z on den 512, where every
+coordinate is exact in float32.  Far from the origin on all three axes, on lattices that round, at the planner's edges and
+on drawn lattices: tests/test_gpu_brick_fields_far.py and the field-bricks family of tests/test_gpu_lattice_sweep.py."""
 import ctypes as C
 import functools
 import os

@@ -16,7 +16,11 @@ GPU, every call writing into a guarded Frame (tests/_frame.py: every sample writ
    kernel, whose bits tests/test_gpu_multiband2d.py holds to the host evaluator), in full up to 300 k samples, else around
    every trip boundary, at the end and at 8,192 random samples;
  * brick lists (wn_eval3d_bricks / wn_multiband3d_bricks), per (seed, part): the checks of tests/test_gpu_bricks_far.py on
-   lists of at most 40 bricks, classified with _far_plan.bricks_route.
+   lists of at most 40 bricks, classified with _far_plan.bricks_route;
+ * gradient, curl and bounded curl brick lists (the six entry points of include/wnoise_brick_fields.h and
+   include/wnoise_bounded_bricks.h), per (family, seed, part): the same drawn lists through the checks of
+   tests/test_gpu_brick_fields_far.py (check_fields), classified with _far_plan.fields_bricks_route, the bounded calls on
+   that module's scene of each list (one sphere per distinct in-range brick, at most 16).
 The sweep traces no kernel: its routes come from the CPU model, which tests/test_gpu_gradient.py, test_gpu_curl.py,
 test_gpu_point_dispatch.py and test_gpu_far_lattice.py pin against traced kernels.
 """
@@ -191,6 +195,51 @@ def test_bricks_sweep_host_evaluator_within_the_bound(ora, gold):
             worst = max(worst, float(np.abs(bf.host_exact(host, coefs[c.tile], c, pts) - bf.ref64(coefs[c.tile], c, pts)).max()))
     print(f"bricks sweep: largest |host exact - ref64| {worst:.3e}")
     assert worst <= bf.TOL / 4
+
+
+def test_field_bricks_sweep_reaches_every_route_and_class():
+    """The drawn lists through _far_plan.fields_bricks_route: in each of the three families every sep<NB> and every decline
+    at least 3 times; every list's bounded scene within the cap on samples left out of the float64 comparison, float32 and
+    float64 classifying the others alike; and every part of a seed with at least 5 separable cases that hold far, near and
+    inside samples."""
+    import test_gpu_brick_fields_far as ff
+    cases = [c for seed in S.BRICKS_SEEDS for c in S.bricks_cases(seed)]
+    assert len(cases) == 60
+    for family in ff.FAMILIES:
+        routes = collections.Counter(ff.field_route(c, family) for c in cases)
+        for nb in range(1, 9):
+            assert routes[(f"sep<{nb}>", None)] >= 3, (family, routes)
+        for check in S.BRICKS_DECLINES:
+            assert routes[("exact", check)] >= 3, (family, routes)
+        assert all(ff.field_route(c, family) == c.route for c in cases)
+    full = {}
+    for c in cases:
+        assert bricks_live(c).any() and 1 <= len(ff.scene_of(c)) <= ff.MAX_OBSTACLES, c.name
+        kinds, share, alike, w32 = ff.scene_report(c)
+        assert alike and share <= ff.LEFT_OUT_CAP, (c.name, share)
+        assert all(k == {0, 1, 2} for k in kinds.values()), (c.name, kinds)        # far, near, inside in every brick with a sphere
+        full[c.name] = set(np.unique(w32).tolist()) == {0, 1, 2}
+    for seed in S.BRICKS_SEEDS:
+        for part in range(S.PARTS):
+            assert sum(c.route[1] is None and full[c.name] for c in S.bricks_cases(seed)[part::S.PARTS]) >= 5
+
+
+def bricks_live(c):
+    return S.bricks_in_range(c)
+
+
+@pytest.mark.parametrize("family", ("grad", "curl", "bounded"))
+def test_field_bricks_sweep_host_evaluators_within_a_quarter_of_the_tolerance(ora, gold, family):
+    """The CPU precondition of tests/test_gpu_brick_fields_far.py on the drawn cases: libwnoise_host.so's exact evaluators
+    stay within a quarter of the family's tolerance of the float64 reference at every in-range sample."""
+    import test_gpu_brick_fields_far as ff
+    import test_gpu_dispatch as td
+    coefs = {"t128": ora.tile3d(128, 12345), "t32": ora.tile3d(32, td.SEED32), "t8": gold["tile3d_8_7"], "t6": gold["tile3d_5odd_11"],
+             "empty": np.empty(0, np.float32)}
+    host, bhost = ff.tf.Host(), ff.B.load_host()
+    worst = max(ff.host_margin(host, bhost, coefs[c.tile], c, family) for seed in S.BRICKS_SEEDS for c in S.bricks_cases(seed))
+    print(f"{family} bricks sweep: largest |host exact - ref64| / tolerance {worst:.3f}")
+    assert worst <= 0.25
 
 
 def test_the_mirrored_constants_are_those_of_the_sources():
@@ -496,3 +545,25 @@ def test_bricks_sweep(wn, tiles, seed, part):
             worst = max(worst, e_fe)
     print(f"bricks sweep seed {seed} part {part}: largest |default - exact| {worst:.3e}")
     assert 0.0 < worst <= bf.TOL
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("part", range(S.PARTS))
+@pytest.mark.parametrize("seed", S.BRICKS_SEEDS)
+@pytest.mark.parametrize("family", ("grad", "curl", "bounded"))
+def test_field_bricks_sweep(wn, tiles, family, seed, part):
+    """The checks of tests/test_gpu_brick_fields_far.py (check_fields) on the drawn lists, per family: the frame, the exact
+    tier's bits against the point entry, the default tier within the family's tolerance of the float64 reference and of the
+    exact tier, the route by bits, the ties to the value bricks, the composition and the unbounded curl, and the first
+    in-range brick alone."""
+    import test_gpu_brick_fields_far as ff
+    env = ff.Env(wn, tiles)
+    worst = [0.0, 0.0]
+    for c in S.bricks_cases(seed)[part::S.PARTS]:
+        assert ff.field_route(c, family) == c.route
+        r_ref, r_ex = ff.check_fields(env, family, c, c.route)
+        if c.route[1] is None:
+            worst = [max(worst[0], r_ref), max(worst[1], r_ex)]
+    print(f"{family} bricks sweep seed {seed} part {part}: largest |default - ref64| / tolerance {worst[0]:.3f}, "
+          f"|default - exact| / tolerance {worst[1]:.3f}")
+    assert 0.0 < worst[1] <= 1.0
