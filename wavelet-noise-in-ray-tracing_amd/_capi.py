@@ -202,6 +202,18 @@ PERLIN_ADVECT_SIGNATURES = {
     "wn_perlin_advect_launch_steps": (_i, [_i, _i, _i]),
 }
 
+# name -> (restype, argtypes); every symbol include/wnoise_perlin_bricks.h declares.  (Named as SIGNATURES_PERLIN_BOUNDED is.)
+SIGNATURES_PERLIN_BRICKS = {
+    # perm, grid, [kind,] [depth,] [offsets9,] bricks, n, out, stream
+    "wn_perlin_bricks": (_i, [_vp, _gp, _vp, _sz, _vp, _vp]),
+    "wn_perlin_turb_bricks": (_i, [_vp, _gp, _i, _vp, _sz, _vp, _vp]),
+    "wn_perlin_fractal_bricks": (_i, [_vp, _gp, _vp, _sz, _vp, _vp]),
+    "wn_perlin_grad_bricks": (_i, [_vp, _gp, _vp, _sz, _vp, _vp]),
+    "wn_perlin_turb_grad_bricks": (_i, [_vp, _gp, _i, _vp, _sz, _vp, _vp]),
+    "wn_perlin_fractal_grad_bricks": (_i, [_vp, _gp, _vp, _sz, _vp, _vp]),
+    "wn_perlin_curl_bricks": (_i, [_vp, _gp, _i, _i, _i32p, _vp, _sz, _vp, _vp]),
+}
+
 # name -> (restype, argtypes); every symbol include/wnoise_perlin_bounded.h declares.  (The name leads with SIGNATURES:
 # tests/test_bounded_bricks_host.py pins the set of names that end with it.)
 SIGNATURES_PERLIN_BOUNDED = {
@@ -288,7 +300,7 @@ def load():
                               *ADVECT_SIGNATURES.items(), *BOUNDED_SIGNATURES.items(), *PERLIN_ADVECT_SIGNATURES.items(),
                               *CURL2D_SIGNATURES.items(), *BOUNDED2D_SIGNATURES.items(), *BRICKS_SIGNATURES.items(),
                               *BRICK_FIELDS_SIGNATURES.items(), *BOUNDED_BRICKS_SIGNATURES.items(),
-                              *SIGNATURES_PERLIN_BOUNDED.items()):
+                              *SIGNATURES_PERLIN_BOUNDED.items(), *SIGNATURES_PERLIN_BRICKS.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

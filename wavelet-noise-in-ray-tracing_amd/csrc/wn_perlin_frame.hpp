@@ -16,6 +16,8 @@
 //     with one lane per entry; a lane fetches its 8 corners' entries with 8 ds_read_b128;
 //   * per sample what is left is 8 x (2 and + 1 xor + 1 fp64 add) for the gradients and the lerps (unfused, reference order).
 // Each kernel keeps what is its own: the LDS layout, the walk over the cells a run crosses, accumulation and finishing.
+// The brick kernels (wn_perlin_bricks.hip) are the same form on rows of 8 samples, one row per lane: they take the octave walk
+// (RunOctaveWalker), the hashes (run_hash_corners) and the corner entries in registers (run_corner_entries) from here.
 #pragma once
 
 #include "wn_internal.hpp"
@@ -115,8 +117,8 @@ struct RunAxisEntryD {
 };
 
 // The octaves of a run kernel: known at compile time for noise and fractal_noise; turb's depth comes from the host.
-template <int KIND>
-__device__ __forceinline__ int run_depth(const PerlinGridFrame &a)
+template <int KIND, typename Args>
+__device__ __forceinline__ int run_depth(const Args &a)
 {
     return (KIND == kNoise) ? 1 : ((KIND == kFractal) ? kFractalOctaves : a.depth);
 }
@@ -126,19 +128,31 @@ __device__ __forceinline__ void run_load_perm(uint8_t *perm, const uint8_t *gper
     for (int i = tid; i < 128; i += threads) reinterpret_cast<uint32_t *>(perm)[i] = reinterpret_cast<const uint32_t *>(gperm)[i];
 }
 
-// The octave walk of coordinate p: store(octave, cell, f) with the lattice cell (& 255) and the fractional part.
-template <int KIND, typename Store>
-__device__ __forceinline__ void run_octave_walk(float p, int depth, Store &&store)
-{
+// The octave walk of coordinate p, one octave per step(): store(cell, f) with the lattice cell (& 255) and the fractional
+// part.  The dense run kernels walk all octaves at once (run_octave_walk); the brick kernels (wn_perlin_bricks.hip) keep a
+// walker per axis index and tabulate one octave at a time, so they have no depth cap.
+template <int KIND>
+struct RunOctaveWalker {
+    float p;
     float cur = p;          // turb: the float point doubles per octave
     double frequency = 1.0; // fractal_noise: float point times a double frequency (perlin.h:82-84)
-    for (int i = 0; i < depth; ++i) {
+    template <typename Store>
+    __device__ __forceinline__ void step(Store &&store)
+    {
         const double c = (KIND == kFractal) ? (double)p * frequency : (double)cur;
         const double fl = floor(c);
-        store(i, (int)fl & 255, c - fl);
+        store((int)fl & 255, c - fl);
         cur *= 2.0f;
         frequency *= 2.0;
     }
+};
+
+// ... of all `depth` octaves: store(octave, cell, f).
+template <int KIND, typename Store>
+__device__ __forceinline__ void run_octave_walk(float p, int depth, Store &&store)
+{
+    RunOctaveWalker<KIND> walker{p};
+    for (int i = 0; i < depth; ++i) walker.step([&](int cell, double f) { store(i, cell, f); });
 }
 
 // Coordinate of x / y sample i of n, and of plane zi of the call; a block's tail repeats the last sample.
@@ -177,17 +191,38 @@ __device__ __forceinline__ void run_publish_ktab(RunKEntry *ktab, int lane, doub
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
 }
 
-// Hashes the 8 corners of cell (X, Y, Z) (perlin.h:55-61) and fetches their {K, mm, t}.
-__device__ __forceinline__ void run_hash_cell(const uint8_t *perm, int X, int Y, int Z, const RunKEntry *ktab, int (&h)[8],
-                                              double (&K)[8], uint32_t (&mm)[8], uint32_t (&tt)[8])
+// Hashes the 8 corners of cell (X, Y, Z) (perlin.h:55-61): corner c = cx + 2 cy + 4 cz.
+__device__ __forceinline__ void run_hash_corners(const uint8_t *perm, int X, int Y, int Z, int (&h)[8])
 {
     const int A = perm[X] + Y, AA = perm[A] + Z, AB = perm[A + 1] + Z;
     const int B = perm[X + 1] + Y, BA = perm[B] + Z, BB = perm[B + 1] + Z;
     h[0] = perm[AA], h[1] = perm[BA], h[2] = perm[AB], h[3] = perm[BB];
     h[4] = perm[AA + 1], h[5] = perm[BA + 1], h[6] = perm[AB + 1], h[7] = perm[BB + 1];
+}
+
+// ... and fetches their {K, mm, t} from the row's table.
+__device__ __forceinline__ void run_hash_cell(const uint8_t *perm, int X, int Y, int Z, const RunKEntry *ktab, int (&h)[8],
+                                              double (&K)[8], uint32_t (&mm)[8], uint32_t (&tt)[8])
+{
+    run_hash_corners(perm, X, Y, Z, h);
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
         const RunKEntry e = ktab[(c >> 1) * 16 + (h[c] & 15)];
+        K[c] = e.K;
+        mm[c] = e.mm;
+        tt[c] = e.t;
+    }
+}
+
+// The 8 corners' {K, mm, t} formed in registers from the hashes: run_publish_ktab's entries without the table, for a lane
+// whose row is its own (wn_perlin_bricks.hip: the 64 lanes of a wave hold 64 rows, so there is no row a table could serve).
+__device__ __forceinline__ void run_corner_entries(const int (&h)[8], double yf, double zf, double (&K)[8], uint32_t (&mm)[8],
+                                                   uint32_t (&tt)[8])
+{
+    const double ym1 = yf - 1.0, zm1 = zf - 1.0;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        const RunKEntry e = run_k_entry(h[c] & 15, (c & 2) ? ym1 : yf, (c & 4) ? zm1 : zf);
         K[c] = e.K;
         mm[c] = e.mm;
         tt[c] = e.t;

@@ -17,6 +17,7 @@
 #include "wnoise_brick_fields.h"
 #include "wnoise_bricks.h"
 #include "wnoise_multiband2d.h"
+#include "wnoise_perlin_bricks.h"
 
 namespace wnhost {
 
@@ -244,4 +245,79 @@ inline void multibandCurlBoundedBricks(WaveletNoise &noise, int den, const int32
                                                      reinterpret_cast<const int32_t *>(offsets9 ? offsets9 : def), s, firstBand,
                                                      nbands, w, variance, obstacles, nobs, out_dev, stream),
                   "wn_multiband3d_curl_bounded_bricks");
+}
+
+// ---- sparse brick lists of Perlin noise (include/wnoise_perlin_bricks.h; absent from the reference) ---------------------
+// The lattice of generatePerlinNoise3DSliced on all three axes, p = ((i / den) * 4) * 2^octave (octave 0: turb's p), on the
+// same device lists and slots: one array of n slots for the values; 4 {value, d/dx, d/dy, d/dz} for the gradients and
+// 3 {vx, vy, vz} for the curl, laid out as the wavelet derivative bricks above.  Every sample has the bits of the dense
+// wn_perlin_*_grid call over the lattice.  Perlin: `perlin` (perlin.h) or `PerlinNoise`, anything with perm().  kind:
+// WN_PERLIN_CURL_NOISE / _TURB / _FRACTAL, depth read by TURB only; offsets9 = (x, y, z) of psi0, psi1, psi2, nullptr:
+// perlin::default_curl_offsets()'s values.
+namespace wnhost {
+inline wn_grid perlin_brick_lattice(int den, const int *bounds, int octave)
+{
+    return brick_lattice(den, bounds, std::pow(2.0f, octave), 1.0f, 1.0f, WN_GRID_DEFAULT);
+}
+} // namespace wnhost
+
+template <class Perlin>
+inline void perlinBricks(const Perlin &perlin, int den, const int32_t *bricks_dev, size_t n, int octave, float *out_dev,
+                         const int *bounds = nullptr, void *stream = nullptr)
+{
+    const wn_grid g = wnhost::perlin_brick_lattice(den, bounds, octave);
+    wnhost::check(wn_perlin_bricks(perlin.perm(), &g, bricks_dev, n, out_dev, stream), "wn_perlin_bricks");
+}
+
+template <class Perlin>
+inline void turbBricks(const Perlin &perlin, int den, const int32_t *bricks_dev, size_t n, float *out_dev, int depth = 7,
+                       int octave = 0, const int *bounds = nullptr, void *stream = nullptr)
+{
+    const wn_grid g = wnhost::perlin_brick_lattice(den, bounds, octave);
+    wnhost::check(wn_perlin_turb_bricks(perlin.perm(), &g, depth, bricks_dev, n, out_dev, stream), "wn_perlin_turb_bricks");
+}
+
+template <class Perlin>
+inline void fractalBricks(const Perlin &perlin, int den, const int32_t *bricks_dev, size_t n, float *out_dev, int octave = 0,
+                          const int *bounds = nullptr, void *stream = nullptr)
+{
+    const wn_grid g = wnhost::perlin_brick_lattice(den, bounds, octave);
+    wnhost::check(wn_perlin_fractal_bricks(perlin.perm(), &g, bricks_dev, n, out_dev, stream), "wn_perlin_fractal_bricks");
+}
+
+template <class Perlin>
+inline void perlinGradientBricks(const Perlin &perlin, int den, const int32_t *bricks_dev, size_t n, int octave, float *out_dev,
+                                 const int *bounds = nullptr, void *stream = nullptr)
+{
+    const wn_grid g = wnhost::perlin_brick_lattice(den, bounds, octave);
+    wnhost::check(wn_perlin_grad_bricks(perlin.perm(), &g, bricks_dev, n, out_dev, stream), "wn_perlin_grad_bricks");
+}
+
+template <class Perlin>
+inline void turbGradientBricks(const Perlin &perlin, int den, const int32_t *bricks_dev, size_t n, float *out_dev, int depth = 7,
+                               int octave = 0, const int *bounds = nullptr, void *stream = nullptr)
+{
+    const wn_grid g = wnhost::perlin_brick_lattice(den, bounds, octave);
+    wnhost::check(wn_perlin_turb_grad_bricks(perlin.perm(), &g, depth, bricks_dev, n, out_dev, stream), "wn_perlin_turb_grad_bricks");
+}
+
+template <class Perlin>
+inline void fractalGradientBricks(const Perlin &perlin, int den, const int32_t *bricks_dev, size_t n, float *out_dev,
+                                  int octave = 0, const int *bounds = nullptr, void *stream = nullptr)
+{
+    const wn_grid g = wnhost::perlin_brick_lattice(den, bounds, octave);
+    wnhost::check(wn_perlin_fractal_grad_bricks(perlin.perm(), &g, bricks_dev, n, out_dev, stream), "wn_perlin_fractal_grad_bricks");
+}
+
+template <class Perlin>
+inline void perlinCurlBricks(const Perlin &perlin, int den, const int32_t *bricks_dev, size_t n, int octave, float *out_dev,
+                             int kind = WN_PERLIN_CURL_NOISE, int depth = 7, const int *offsets9 = nullptr,
+                             const int *bounds = nullptr, void *stream = nullptr)
+{
+    static_assert(sizeof(int) == sizeof(int32_t), "offsets are int32");
+    static const int def[9] = {0, 0, 0, 85, 85, 85, 170, 170, 170};
+    const wn_grid g = wnhost::perlin_brick_lattice(den, bounds, octave);
+    wnhost::check(wn_perlin_curl_bricks(perlin.perm(), &g, kind, depth, reinterpret_cast<const int32_t *>(offsets9 ? offsets9 : def),
+                                        bricks_dev, n, out_dev, stream),
+                  "wn_perlin_curl_bricks");
 }

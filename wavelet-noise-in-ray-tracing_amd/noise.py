@@ -1452,3 +1452,54 @@ def perlin_curl_volume(perlin_obj, den, nx, ny, z0, z1, octave, kind="noise", de
     check(_lib.wn_perlin_curl_grid(perlin_obj._h, C.byref(gc), _PERLIN_CURL_KINDS[kind], int(depth),
                                    perlin._curl_offsets(offsets), _ptr(out), _stream()))
     return out[: 3 * g.nz * ny * nx].view(3, g.nz, ny, nx)
+
+
+# ---- sparse brick lists of Perlin noise (include/wnoise_perlin_bricks.h) ---------------------------------
+def _perlin_bricks(fn, perlin_obj, den, bricks, octave, bounds, out, ch, *mid):
+    """One wn_perlin_*_bricks call on perlin_volume's lattice p = (i/den)*4 * 2^octave (octave 0: turb_volume's); `mid`:
+    the arguments between the grid and the list."""
+    n, (nx, ny, z0, z1), out = _bricks_args(den, bricks, bounds, out, ch)
+    gc = GridSpec(den, nx, ny, z0, z1, octave_scale=_octave_scale(octave)).c()
+    check(fn(perlin_obj._h, C.byref(gc), *mid, _ptr(bricks), n, _ptr(out), _stream()))
+    edge = _capi.WN_BRICK
+    return out.view(n, edge, edge, edge) if ch == 1 else _brick_fields_view(out, ch, n)
+
+
+def perlin_bricks(perlin_obj, den, bricks, octave, bounds=None, out=None):
+    """perlin_volume on the listed 8^3 bricks of the lattice only (wn_perlin_bricks): brick (bx, by, bz) holds the samples
+    [8bz, 8bz+8) x [8by, 8by+8) x [8bx, 8bx+8) of perlin_volume(perlin_obj, den, ...), as out[i][z][y][x], bit for bit.
+    Bricks outside `bounds` (nx, ny, z0, z1; `den` on each axis by default) are left untouched."""
+    return _perlin_bricks(_lib.wn_perlin_bricks, perlin_obj, den, bricks, octave, bounds, out, 1)
+
+
+def turb_bricks(perlin_obj, den, bricks, depth=7, octave=0, bounds=None, out=None):
+    """turb_volume on the listed bricks only (wn_perlin_turb_bricks): turb(p = (i/den)*4 * 2^octave, depth)."""
+    return _perlin_bricks(_lib.wn_perlin_turb_bricks, perlin_obj, den, bricks, octave, bounds, out, 1, int(depth))
+
+
+def fractal_bricks(perlin_obj, den, bricks, octave=0, bounds=None, out=None):
+    """fractal_noise(p = (i/den)*4 * 2^octave) on the listed bricks only (wn_perlin_fractal_bricks)."""
+    return _perlin_bricks(_lib.wn_perlin_fractal_bricks, perlin_obj, den, bricks, octave, bounds, out, 1)
+
+
+def perlin_gradient_bricks(perlin_obj, den, bricks, octave, bounds=None, out=None):
+    """perlin_gradient_volume on the listed bricks only (wn_perlin_grad_bricks): (4, n, 8, 8, 8) -- value, d/dx, d/dy,
+    d/dz as out[channel][i][z][y][x]."""
+    return _perlin_bricks(_lib.wn_perlin_grad_bricks, perlin_obj, den, bricks, octave, bounds, out, 4)
+
+
+def turb_gradient_bricks(perlin_obj, den, bricks, depth=7, octave=0, bounds=None, out=None):
+    """turb_gradient_volume on the listed bricks only (wn_perlin_turb_grad_bricks): (4, n, 8, 8, 8)."""
+    return _perlin_bricks(_lib.wn_perlin_turb_grad_bricks, perlin_obj, den, bricks, octave, bounds, out, 4, int(depth))
+
+
+def fractal_gradient_bricks(perlin_obj, den, bricks, octave=0, bounds=None, out=None):
+    """fractal_noise with its gradient on the listed bricks only (wn_perlin_fractal_grad_bricks): (4, n, 8, 8, 8)."""
+    return _perlin_bricks(_lib.wn_perlin_fractal_grad_bricks, perlin_obj, den, bricks, octave, bounds, out, 4)
+
+
+def perlin_curl_bricks(perlin_obj, den, bricks, octave, kind="noise", depth=7, offsets=None, bounds=None, out=None):
+    """perlin_curl_volume on the listed bricks only (wn_perlin_curl_bricks; `kind`, `depth` and `offsets` as there):
+    (3, n, 8, 8, 8) -- vx, vy, vz as out[component][i][z][y][x]."""
+    return _perlin_bricks(_lib.wn_perlin_curl_bricks, perlin_obj, den, bricks, octave, bounds, out, 3,
+                          _PERLIN_CURL_KINDS[kind], int(depth), perlin._curl_offsets(offsets))
