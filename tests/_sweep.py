@@ -9,6 +9,8 @@ assert what the committed seeds reach.
   deriv_cases(family, seed)   gradient / curl bricks: grad3d_ / curl3d_grid_sep_kernel<1..8>, _direct_kernel<true / false>
   perlin_cases(variant, seed) Perlin value / gradient / curl grids: run form and generic kernel
   mb2d_cases(cus, seed)       multiband2d_grid_kernel: the span walk over trips of 2 * cus * 1024 samples
+  bricks_cases(seed)          wavelet brick lists: every sep<NB> and every declining check
+  perlin_bricks_cases(variant, seed)  Perlin brick lists: perlin_cases' slots on drawn volumes and lists (segment trips 1..8)
 
 A plain helper module (not a conftest): the tests import it by name.
 """
@@ -637,5 +639,140 @@ def bricks_cases(seed):
             raise AssertionError(f"the generator cannot place bricks seed {seed} case {idx}: {target} {near}")
         c.route, c.name = (label, why), f"bricks-{seed}-{idx:02d}"
         assert 1 <= len(c.bricks) <= BRICKS_MAX_LIST
+        cases.append(c)
+    return cases
+
+
+# ---- Perlin brick lists --------------------------------------------------------------------------------------------------------
+PERLIN_BRICKS_SEED = 20257
+PERLIN_BRICKS_MAX_LIST = 40
+PERLIN_COORD_LIMIT = 2.0 ** 30         # the finest octave's coordinate (tests/test_gpu_far_lattice.py's far point sets keep it)
+PERLIN_DEFAULT_OFFSETS = ((0, 0, 0), (85, 85, 85), (170, 170, 170))
+_PB_POST = (1.0, 2.0, 0.75, 1.3)
+_PB_EXTENTS = (9, 21, 40, 133, 4099, 8 * 50000 + 3, 8 << 17)      # short, ragged and very long
+_PB_Z0 = (0, 3, -5, -4099)
+_PB_NZ = (1, 9, 24, 70, 4100, 8 * 30000 + 5)
+
+
+def perlin_finest(kind, depth):
+    """The factor of the finest octave's coordinate (0: the call evaluates no octave)."""
+    return 1.0 if kind == "noise" else (32.0 if kind == "fractal" else (2.0 ** (depth - 1) if depth >= 1 else 0.0))
+
+
+def perlin_octave_cells(p, kind, depth):
+    """Per octave, the lattice cell (floor, before & 255) of the float32 coordinates p, as RunOctaveWalker::step
+    (csrc/wn_perlin_frame.hpp) forms it: noise reads p, turb doubles the FLOAT per octave, fractal_noise multiplies the float
+    by a double frequency."""
+    p = np.asarray(p, f32)
+    if kind == "noise":
+        return [np.floor(p.astype(np.float64)).astype(np.int64)]
+    if kind == "fractal":
+        return [np.floor(p.astype(np.float64) * 2.0 ** i).astype(np.int64) for i in range(FRACTAL_OCTAVES)]
+    out, cur = [], p.copy()
+    for _ in range(depth):
+        out.append(np.floor(cur.astype(np.float64)).astype(np.int64))
+        cur = cur * f32(2.0)
+    return out
+
+
+def perlin_row_trips(cells8):
+    """Segment trips of one brick row and octave (csrc/wn_perlin_bricks.hip): segments are matched on the cell BYTE
+    (cell_at(q) == X), so the loop takes one trip per distinct byte."""
+    return len(set((np.asarray(cells8) & 255).tolist()))
+
+
+def perlin_row_has_hole(cells8):
+    """Two samples share a cell byte and a sample between them does not: the mask `mine` is no run of adjacent samples."""
+    b = (np.asarray(cells8) & 255).tolist()
+    return any(b[i] == b[j] and any(b[k] != b[i] for k in range(i + 1, j)) for i in range(8) for j in range(i + 2, 8))
+
+
+def perlin_trip_counts(x_rows, calls):
+    """(the set of segment-trip counts over the (n, 8) float32 x rows, the calls and their octaves, whether a mask has a hole)."""
+    counts, hole = set(), False
+    for kind, depth in calls:
+        for cells in perlin_octave_cells(x_rows, kind, depth):
+            for c8 in cells:
+                counts.add(perlin_row_trips(c8))
+                hole = hole or perlin_row_has_hole(c8)
+    return counts, hole
+
+
+def perlin_bricks_coords(c, bricks):
+    """(n, 512, 3) float32 coordinates of the bricks' samples in slot order, in lattice_coord's order of operations from the
+    int64 index."""
+    b = np.asarray(bricks, np.int64).reshape(-1, 3)
+    l = np.arange(512)
+    idx = np.stack([8 * b[:, None, 0] + (l & 7), 8 * b[:, None, 1] + ((l >> 3) & 7), 8 * b[:, None, 2] + (l >> 6)], -1)
+    p = (idx.astype(f32) / f32(c.den)) * f32(c.base_range)
+    p = p * f32(c.octave_scale)
+    return p * f32(c.post_scale)
+
+
+def perlin_bricks_live(c):
+    nbx, nby, bz0, bz1 = fp.brick_range(fp.Grid(c.den, c.nx, c.ny, c.z0, c.z1 - c.z0))
+    b = np.asarray(c.bricks, np.int64)
+    return (b[:, 0] >= 0) & (b[:, 0] < nbx) & (b[:, 1] >= 0) & (b[:, 1] < nby) & (b[:, 2] >= bz0) & (b[:, 2] < bz1)
+
+
+def perlin_bricks_box(c):
+    """(nx, ny, z0, z1) of the bounding lattice of the in-range bricks, whole bricks from x = y = 0; None beyond CAP samples."""
+    b = np.asarray(c.bricks, np.int64)[c.live]
+    box = (8 * int(b[:, 0].max() + 1), 8 * int(b[:, 1].max() + 1), 8 * int(b[:, 2].min()), 8 * int(b[:, 2].max() + 1))
+    return box if box[0] * box[1] * (box[3] - box[2]) <= CAP else None
+
+
+def _draw_perlin_brick_list(rng, c, idx):
+    """1 to 40 bricks, odd counts at odd idx: in-range bricks drawn over the whole volume with the far corner first; from 2
+    bricks on the last is out of range (every sixth list holds a second); from 3 on one has bz = bz0; from 4 on one is a
+    duplicate."""
+    nbx, nby, bz0, bz1 = fp.brick_range(fp.Grid(c.den, c.nx, c.ny, c.z0, c.z1 - c.z0))
+    n = 2 * int(rng.integers(1, PERLIN_BRICKS_MAX_LIST // 2 + 1)) - idx % 2
+    b = np.stack([rng.integers(0, nbx, n), rng.integers(0, nby, n), rng.integers(bz0, bz1, n)], -1)
+    b[0] = (nbx - 1, nby - 1, bz1 - 1)
+    sides = [(-1, 0, bz0), (nbx, 0, bz0), (0, -1, bz0), (0, nby, bz0), (0, 0, bz0 - 1), (0, 0, bz1)]
+    if n >= 3:
+        b[2, 2] = bz0
+    if n >= 4:
+        free = [j for j in range(2, n - 1) if j != n // 2 or n < 6]
+        b[1] = b[int(rng.choice(free))]
+    if n >= 6 and idx % 6 == 0:
+        b[n // 2] = sides[(idx // 6 + 3) % 6]
+    if n >= 2:
+        b[n - 1] = sides[idx % 6]
+    return np.ascontiguousarray(b, np.int32)
+
+
+def perlin_bricks_cases(variant, seed=PERLIN_BRICKS_SEED):
+    """One case per slot of _PERLIN_SLOTS (kind, depth, step class, flags n and d; a slot flagged z draws a lattice z range like
+    every other: bricks refuse WN_Z_CONST).  A case whose finest octave would see a coordinate past 2^30 is drawn again from
+    the same stream."""
+    assert variant in PERLIN_CHANNELS
+    rng = np.random.default_rng([seed, list(PERLIN_CHANNELS).index(variant)])
+    cases = []
+    for idx, (kind, depth, _rows, cls, flags) in enumerate(_PERLIN_SLOTS):
+        for _attempt in range(400):
+            c = SimpleNamespace(variant=variant, kind=kind, depth=depth, lead=idx % 4, seed=12345, calls=[(kind, depth)])
+            c.base_range = float(rng.choice([-4.0, -3.0])) if "n" in flags else float(rng.choice([4.0, 4.0, 2.5]))
+            c.octave_scale = float(f32(rng.choice([3.7, 0.6, 5.3]))) if "d" in flags else float(rng.choice([1.0, 2.0, 4.0, 16.0]))
+            c.post_scale = float(f32(rng.choice(_PB_POST)))
+            target = float(rng.uniform(*_STEP_RANGE[cls]))
+            c.den = max(1, int(round(abs(c.base_range) * c.octave_scale * c.post_scale / target)))
+            c.nx, c.ny = int(rng.choice(_PB_EXTENTS)), int(rng.choice(_PB_EXTENTS))
+            c.z0 = int(rng.choice(_PB_Z0))
+            c.z1 = c.z0 + int(rng.choice(_PB_NZ))
+            c.bounds = (c.nx, c.ny, c.z0, c.z1)
+            c.out_scale = float(rng.choice([1.0, 0.75, -2.5]))
+            c.offsets = PERLIN_DEFAULT_OFFSETS
+            if variant == "curl" and idx % 5 != 4:
+                c.offsets = tuple(tuple(int(v) for v in rng.integers(-300, 1100, 3)) for _ in range(3))
+            c.bricks = _draw_perlin_brick_list(rng, c, idx)
+            c.live = perlin_bricks_live(c)
+            c.pmax = float(np.abs(perlin_bricks_coords(c, c.bricks[c.live])).max())
+            if perlin_step_class(c) == cls and c.pmax * perlin_finest(kind, depth) <= PERLIN_COORD_LIMIT:
+                break
+        else:
+            raise AssertionError(f"the generator cannot place perlin bricks {variant} case {idx}")
+        c.name = f"perlin-bricks-{variant}-{idx:02d}-{kind}{depth}"
         cases.append(c)
     return cases

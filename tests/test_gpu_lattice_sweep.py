@@ -20,7 +20,11 @@ GPU, every call writing into a guarded Frame (tests/_frame.py: every sample writ
  * gradient, curl and bounded curl brick lists (the six entry points of include/wnoise_brick_fields.h and
    include/wnoise_bounded_bricks.h), per (family, seed, part): the same drawn lists through the checks of
    tests/test_gpu_brick_fields_far.py (check_fields), classified with _far_plan.fields_bricks_route, the bounded calls on
-   that module's scene of each list (one sphere per distinct in-range brick, at most 16).
+   that module's scene of each list (one sphere per distinct in-range brick, at most 16);
+ * Perlin brick lists (include/wnoise_perlin_bricks.h), per variant: drawn lattices (negative steps, post_scale not 1, short
+   to very long extents, z0 of either sign) and lists of 1 to 40 bricks through checks 1 and 2 of
+   tests/test_gpu_perlin_bricks_far.py, and on bits against the dense entry point where the listed bricks' bounding lattice
+   is within CAP.
 The sweep traces no kernel: its routes come from the CPU model, which tests/test_gpu_gradient.py, test_gpu_curl.py,
 test_gpu_point_dispatch.py and test_gpu_far_lattice.py pin against traced kernels.
 """
@@ -124,6 +128,43 @@ def test_perlin_sweep_reaches_both_forms_and_every_step_class(variant):
     assert all(0 < c.nx * c.ny * c.nz <= S.CAP for c in cases)
     if variant == "curl":
         assert any(c.offsets is None for c in cases) and any(c.offsets is not None and min(min(o) for o in c.offsets) < 0 for c in cases)
+
+
+@pytest.mark.parametrize("variant", list(S.PERLIN_CHANNELS))
+def test_perlin_bricks_sweep_reaches_every_step_class_and_segment_count(variant):
+    cases = S.perlin_bricks_cases(variant)
+    assert len(cases) == len(S._PERLIN_SLOTS) and len({c.name for c in cases}) == len(cases)
+    steps = collections.Counter(S.perlin_step_class(c) for c in cases)
+    assert steps["small"] >= 3 and steps["mid"] >= 3 and steps["big"] >= 3 and set(steps) == {"small", "mid", "big"}, steps
+    assert sum(c.base_range < 0 for c in cases) >= 3 and sum(bool((c.bricks[c.live][:, 2] < 0).any()) for c in cases) >= 3
+    assert {len(c.bricks) % 2 for c in cases} == {0, 1}
+    assert {c.depth for c in cases if c.kind == "turb"} >= {0, 1, 8, 9, 12} and {c.kind for c in cases} == {"noise", "turb", "fractal"}
+    assert any(np.log2(c.octave_scale) % 1 for c in cases) and len({c.post_scale for c in cases}) >= 3
+    assert {c.z0 for c in cases} == {0, 3, -5, -4099} and {c.lead for c in cases} == {0, 1, 2, 3}
+    assert len({c.out_scale for c in cases}) == 3
+    extents = [e for c in cases for e in (c.nx, c.ny)]
+    assert min(extents) <= 21 and max(extents) >= 8 << 17 and any(e % 8 for e in extents)
+    trips, dense = set(), 0
+    for c in cases:
+        n, live = len(c.bricks), c.live
+        assert 1 <= n <= S.PERLIN_BRICKS_MAX_LIST and live[0] and (live == S.perlin_bricks_live(c)).all()
+        assert (~live).sum() == (0 if n == 1 else (2 if n >= 6 and int(c.name.split("-")[3]) % 6 == 0 else 1)), c.name
+        if n >= 4:
+            assert len({tuple(b) for b in c.bricks.tolist()}) < n, c.name                    # a duplicate
+        assert np.abs(c.bricks).max() < 1 << 27                                               # 8 b + 7 is an ordinary int32
+        pts = S.perlin_bricks_coords(c, c.bricks[live])
+        assert float(np.abs(pts).max()) * S.perlin_finest(c.kind, c.depth) <= S.PERLIN_COORD_LIMIT, c.name
+        trips |= S.perlin_trip_counts(pts[:, :8, 0], c.calls)[0]
+        box = S.perlin_bricks_box(c)
+        dense += box is not None
+        assert box is None or box[0] * box[1] * (box[3] - box[2]) <= S.CAP
+    assert 1 in trips and 8 in trips and trips & set(range(2, 8)), trips
+    assert dense >= 3
+    if variant == "curl":
+        assert any(c.offsets == S.PERLIN_DEFAULT_OFFSETS for c in cases)
+        assert any(min(min(o) for o in c.offsets) < 0 for c in cases) and any(max(max(o) for o in c.offsets) >= 256 for c in cases)
+    again = S.perlin_bricks_cases(variant)
+    assert all((a.bricks == b.bricks).all() and a.bounds == b.bounds and a.den == b.den for a, b in zip(cases, again))
 
 
 @pytest.mark.parametrize("cus", [MI355X_CUS, 304, 64])
@@ -492,6 +533,33 @@ def test_perlin_sweep(wn, nm, variant):
             assert (got == 0.0).all()
         forms[c.form] += 1
     print(f"sweep perlin {variant}: {dict(forms)}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("variant", list(S.PERLIN_CHANNELS))
+def test_perlin_bricks_sweep(wn, variant):
+    """Checks 1 and 2 of tests/test_gpu_perlin_bricks_far.py on the drawn lists: the frame, and the bits of (float)(point
+    entry) * out_scale at the restated coordinates; where the bounding lattice of the in-range bricks is within CAP, the
+    bits of the dense entry point as well."""
+    import test_gpu_perlin_bricks as tpb
+    import test_gpu_perlin_bricks_far as pbf
+    env = tpb.Env(wn)
+    dense = 0
+    for c in S.perlin_bricks_cases(variant):
+        live, off = c.live, tpb.c_off(c.offsets)
+        got = env.run(c.seed, variant, c.kind, c.depth, c, c.bricks, c.lead, bounds=c.bounds, offsets=off)
+        pts = S.perlin_bricks_coords(c, c.bricks[live]).reshape(-1, 3)
+        rec = env.records(c.seed, variant, c.kind, c.depth, pts, c.offsets)
+        tpb.same_bits(got[:, live], pbf.scaled(rec, c, int(live.sum())), f"{c.name}: against the point entry")
+        box = S.perlin_bricks_box(c)
+        if box is not None:
+            want = pbf.gather(pbf.dense(env, c, variant, c.kind, c.depth, box), c.bricks[live], box[2])
+            tpb.same_bits(got[:, live], want, f"{c.name}: against the dense grid over {box}")
+            dense += 1
+        if c.kind == "turb" and c.depth == 0:
+            assert (got[:, live] == 0.0).all()
+    print(f"sweep perlin bricks {variant}: {dense} lists compared with the dense grid")
+    assert dense >= 3
 
 
 # ---- multiband2d -----------------------------------------------------------------------------------------------------------------

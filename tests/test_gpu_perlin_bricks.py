@@ -58,8 +58,34 @@ def symbol(field, kind, what):
     return "wn_perlin_" + {"noise": "", "turb": "turb_", "fractal": "fractal_"}[kind] + ("grad_" if field == "grad" else "") + what
 
 
-def c_off():
-    return (C.c_int32 * 9)(*[int(v) for t in OFF for v in t])
+def c_off(offsets=OFF):
+    return (C.c_int32 * 9)(*[int(v) for t in offsets for v in t])
+
+
+def lattice_of(lattice):
+    """(den, base_range, octave_scale, post_scale, out_scale) of a lattice: a (den, octave, out_scale) triple of LATTICES in
+    perlin_volume's mapping, or any object with those five fields (tests/test_gpu_perlin_bricks_far.py, the sweep)."""
+    if isinstance(lattice, tuple):
+        den, octave, scale = lattice
+        return den, 4.0, float(f32(2.0 ** octave)), 1.0, scale
+    return lattice.den, lattice.base_range, lattice.octave_scale, lattice.post_scale, lattice.out_scale
+
+
+def sample_index(bricks):
+    """(n, 512, 3) int64 lattice indices of the samples of `bricks`, in slot order lx + 8 (ly + 8 lz)."""
+    b = np.asarray(bricks, np.int64).reshape(-1, 3)
+    l = np.arange(512)
+    return np.stack([8 * b[:, None, 0] + (l & 7), 8 * b[:, None, 1] + ((l >> 3) & 7), 8 * b[:, None, 2] + (l >> 6)], -1)
+
+
+def sample_coords(lattice, bricks):
+    """The float32 coordinates of every sample of `bricks`, (n * 512, 3), as lattice_coord forms them from the absolute
+    index: ((f32(i) / f32(den)) * range) * oscale * post, f32(i) converted from the int64 index."""
+    den, base_range, octave_scale, post_scale, _ = lattice_of(lattice)
+    c = (sample_index(bricks).astype(f32) / f32(den)) * f32(base_range)
+    c = c * f32(octave_scale)
+    c = c * f32(post_scale)
+    return np.ascontiguousarray(c.reshape(-1, 3))
 
 
 class Env:
@@ -71,14 +97,14 @@ class Env:
 
     def grid(self, lattice, bounds):
         nm = self.nm
-        den, octave, scale = lattice
+        den, base_range, octave_scale, post_scale, scale = lattice_of(lattice)
         nx, ny, z0, z1 = bounds
-        return nm.wn_grid(den, nx, ny, z0, z1, 4.0, nm._octave_scale(octave), 1.0, 0, 0.0, scale, 0)
+        return nm.wn_grid(den, nx, ny, z0, z1, base_range, octave_scale, post_scale, 0, 0.0, scale, 0)
 
     def mid(self, field, kind, depth, offsets="OFF"):
         """The arguments between the grid and the list (dense: the output)."""
         if field == "curl":
-            return (KINDS[kind] if isinstance(kind, str) else kind, depth, c_off() if offsets == "OFF" else offsets)
+            return (KINDS[kind] if isinstance(kind, str) else kind, depth, c_off() if isinstance(offsets, str) else offsets)
         return (depth,) if kind == "turb" else ()
 
     def call(self, seed, field, kind, depth, g, bricks_ptr, n, out_ptr, **kw):
@@ -94,14 +120,14 @@ class Env:
         return fn(h, C.byref(g) if g is not None else None, *self.mid(field, kind, depth, kw.get("offsets", "OFF")), out_ptr,
                   self.nm._stream())
 
-    def run(self, seed, field, kind, depth, lattice, bricks, lead, bounds=BOUNDS):
+    def run(self, seed, field, kind, depth, lattice, bricks, lead, bounds=BOUNDS, offsets="OFF"):
         """One call into a frame: the (ch, n, 512) payload, after the checks of what was written -- the guards intact, every
         in-range slot of every channel written, every other still the sentinel, the list unchanged."""
         import torch
         ch, n = CHANNELS[field], len(bricks)
         dev = torch.from_numpy(np.ascontiguousarray(bricks)).cuda()
         frame = Frame(ch * 512 * n, lead)
-        rc = self.call(seed, field, kind, depth, self.grid(lattice, bounds), self.nm._ptr(dev), n, frame.ptr)
+        rc = self.call(seed, field, kind, depth, self.grid(lattice, bounds), self.nm._ptr(dev), n, frame.ptr, offsets=offsets)
         assert rc == 0, self.nm._lib.wn_last_error()
         live = in_range(bricks, bounds)
         got = frame.result(written=np.tile(np.repeat(live, 512), ch), what=f"{field} {kind} {depth} {lattice}").reshape(ch, n, 512)
@@ -121,20 +147,13 @@ class Env:
 
     def coords(self, lattice, bricks):
         """The float coordinates of every sample of `bricks`, (n * 512, 3): grid_coord at the absolute index."""
-        g = self.grid(lattice, BOUNDS)
-        l = np.arange(512)
-        idx = np.stack([8 * bricks[:, None, 0] + (l & 7), 8 * bricks[:, None, 1] + ((l >> 3) & 7),
-                        8 * bricks[:, None, 2] + (l >> 6)], -1).astype(f32)
-        c = (idx / f32(lattice[0])) * f32(g.base_range)
-        c = c * f32(g.octave_scale)
-        c = c * f32(g.post_scale)
-        return np.ascontiguousarray(c.reshape(-1, 3))
+        return sample_coords(lattice, bricks)
 
-    def points(self, seed, field, kind, depth, lattice, bricks):
-        """(float) of the matching point entry at the samples' float coordinates, times out_scale: (ch, n, 512)."""
+    def records(self, seed, field, kind, depth, pts, offsets=OFF):
+        """The float64 records of the matching point entry at the float32 points `pts`: (N, ch) on the host."""
         import torch
         p = self.perlins[seed]
-        pts = torch.from_numpy(self.coords(lattice, bricks)).cuda()
+        pts = torch.from_numpy(np.ascontiguousarray(pts, f32)).cuda()
         if field == "value":
             v = {"noise": lambda: p.noise(pts), "turb": lambda: p.turb(pts, depth), "fractal": lambda: p.fractal_noise(pts)}[kind]()
             v = v.reshape(-1, 1)
@@ -142,8 +161,13 @@ class Env:
             v = {"noise": lambda: p.noise_gradient(pts), "turb": lambda: p.turb_gradient(pts, depth),
                  "fractal": lambda: p.fractal_noise_gradient(pts)}[kind]()
         else:
-            v = p._curl(pts, KINDS[kind], depth, OFF)
-        v = v.cpu().numpy().astype(f32) * f32(lattice[2])
+            v = p._curl(pts, KINDS[kind], depth, offsets)
+        return v.cpu().numpy()
+
+    def points(self, seed, field, kind, depth, lattice, bricks, offsets=OFF):
+        """(float) of the matching point entry at the samples' float coordinates, times out_scale: (ch, n, 512)."""
+        v = self.records(seed, field, kind, depth, self.coords(lattice, bricks), offsets)
+        v = v.astype(f32) * f32(lattice_of(lattice)[4])
         return np.ascontiguousarray(v.T).reshape(CHANNELS[field], len(bricks), 512)
 
     def oracle(self, ora, seed, kind, depth, lattice, bricks):
