@@ -395,7 +395,7 @@ def field_box_cap(family):
 
 def fields_bricks_route(g, tile_n, exact, family, bands=None, nobs=0):
     """fields_call + sep_try (csrc/wn_wavelet_brick_fields.hip), bounded_bricks_call + sep_try
-    (csrc/wn_wavelet_bounded_bricks.hip), wn::brick_list_plan and wn::field_sep_args (csrc/wn_brick_list.hpp) of the
+    (csrc/wn_wavelet_bounded_bricks.hip), wn::brick_list_plan and wn::brick_sep_args (csrc/wn_brick_list.hpp) of the
     gradient, curl and bounded curl brick lists, single band (bands None) or multiband (bands = (s, first, nbands)):
     bricks_route's pairs, with the checks in the order these sources make them.  A bounded call without obstacles
     (nobs == 0) is forwarded to the curl entry point."""
@@ -416,7 +416,7 @@ def fields_bricks_route(g, tile_n, exact, family, bands=None, nobs=0):
     if bands is not None and nb < 1:
         return "exact", "no active band"
     qmul = [1.0] if bands is None else [float(f32(2.0) * f32(2.0 ** (bands[1] + b))) for b in range(nb)]
-    # field_sep_args
+    # brick_sep_args
     if tile_n == 0:
         return "exact", "empty tile"
     if not roundable:

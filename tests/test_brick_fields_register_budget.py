@@ -12,13 +12,14 @@ import pytest
 from _device_asm import PKG, assert_no_scratch, descriptor, device_assembly, kernels, waves_per_simd
 
 
-def mangled(name, targs, arg):
-    return f"_ZN12_GLOBAL__N_1{len(name)}{name}I{targs}EEvNS_{len(arg)}{arg}E"
+def mangled(name, targs, arg, shared=False):
+    """A kernel of the file's unnamed namespace; its argument struct is the file's own, or wn::'s (shared)."""
+    return f"_ZN12_GLOBAL__N_1{len(name)}{name}I{targs}EEv" + (f"N2wn{len(arg)}{arg}E" if shared else f"NS_{len(arg)}{arg}E")
 
 
 EXACT = [mangled("brick_fields_exact_kernel", f"Lb{p}ELb{m}ELb{c}E", "FieldsExactArgs") for p in (0, 1) for m in (0, 1) for c in (0, 1)]
-GRAD = {nb: mangled("grad_bricks_sep_kernel", f"Li{nb}E", "FieldsSepArgs") for nb in range(1, 9)}
-CURL = {nb: mangled("curl_bricks_sep_kernel", f"Li{nb}E", "FieldsSepArgs") for nb in range(1, 9)}
+GRAD = {nb: mangled("grad_bricks_sep_kernel", f"Li{nb}E", "BrickSepArgs", True) for nb in range(1, 9)}
+CURL = {nb: mangled("curl_bricks_sep_kernel", f"Li{nb}E", "BrickSepArgs", True) for nb in range(1, 9)}
 KERNELS = EXACT + list(GRAD.values()) + list(CURL.values())
 
 

@@ -12,7 +12,7 @@ import pytest
 from _device_asm import PKG, assert_no_scratch, descriptor, device_assembly, kernels, waves_per_simd
 
 EXACT = "_ZN12_GLOBAL__N_119bricks_exact_kernelILb{}ELb{}EEEvNS_15BricksExactArgsE"
-SEP = "_ZN12_GLOBAL__N_117bricks_sep_kernelILi{}EEEvNS_13BricksSepArgsE"
+SEP = "_ZN12_GLOBAL__N_117bricks_sep_kernelILi{}EEEvN2wn12BrickSepArgsE"   # the brick lists' one argument struct
 KERNELS = [EXACT.format(p, m) for p in (0, 1) for m in (0, 1)] + [SEP.format(nb) for nb in range(1, 9)]
 
 

@@ -6,7 +6,7 @@ wn_multiband3d_curl_bounded_bricks.
 A brick list is the one entry point that reaches x and y far from the origin, so only here do grad_bricks_sep_kernel<NB>,
 curl_bricks_sep_kernel<NB> and curl_bounded_bricks_sep_kernel<NB> meet float32 x and y coordinates that round: the derivative
 columns xw.d of wn::brick_x_window, the y and z derivative weights, the curl's three shifted boxes, the bounded kernel's ramp,
-and wn::field_sep_args (csrc/wn_brick_list.hpp), a second statement of the value bricks' regime.  tests/_far_plan.py's
+and wn::brick_sep_args (csrc/wn_brick_list.hpp), the regime the value bricks share.  tests/_far_plan.py's
 fields_bricks_route restates that planner from its sources; the CPU tests hold it to bricks_route on every row and drawn case
 (whose bands the value module already holds to wn::lattice_step itself: test_bricks_route_uses_the_headers_lattice_step) and
 move the same rows under the same three mutations.
@@ -292,7 +292,7 @@ def test_the_far_z_rows_are_what_the_module_says():
 
 
 def test_the_field_route_is_the_value_bricks_route():
-    """wn::field_sep_args' header comment, "the regime of the value bricks' sep_try", held to: on every row and every drawn
+    """wn::brick_sep_args is the regime of the value bricks and of the field bricks alike: on every row and every drawn
     case fields_bricks_route gives bricks_route's pair in all three families; a bounded call without obstacles is the curl's."""
     seen = set()
     sweep = [c for seed in S.BRICKS_SEEDS for c in S.bricks_cases(seed)]

@@ -5,8 +5,10 @@
 // curl 3, one per potential, of one geometry) in LDS once, periodic wrap resolved, x fastest.  A lane owns 4 consecutive x
 // samples, a wave rows (y, z) of the brick; 4 consecutive samples span at most two mids, so their taps lie in the 4 box
 // columns m0 - 1 .. m0 + 2, and each sample's x weights are placed in that window (zero outside its three taps).  The
-// kernels keep what differs: the column contraction between "z, y" and "x", their factors and the channel count.  The frame
-// sums nothing: a sample's bits depend on its own weights and coefficients only, not on its place in a brick or z-slab.
+// arithmetic between staging and store -- the value, gradient and curl contractions of those columns over z, then y, then
+// x -- is stated here once, for these two kernels and for the brick-list kernels of wn_brick_list.hpp, which promise the
+// dense grids' bits; so are the bands' factors (wn::band_factors).  A sample's bits depend on its own weights and
+// coefficients only, not on its place in a brick or z-slab.
 //
 // The geometry step (first and last mids per band and axis -> s_geo) stays written out in both kernels: as a forceinline
 // helper (storing to s_geo itself, or returning the first cell and the extent) it takes grad3d_grid_sep_kernel<1> from 80
@@ -80,6 +82,29 @@ int brick_dispatch(int nbands, F &&f)
     }
 }
 
+// The bands of a separable launch and their factors.  evaluate3D (mb == false): one band, q = p, every factor out_scale.
+// WMultibandNoise: band b at q = p * qmul, qmul = 2 * 2^(first_band+b) (exact), with the factor of its value
+// fv = w_b / out_div * out_scale and of its derivatives fg = fv * qmul, formed in double and rounded once each.  Written
+// as one expression, w / div * scale * qmul associates left to right into the same double operations as fv's then * qmul.
+struct BandFactors {
+    int nbands;
+    float qmul[kMaxBands], fv[kMaxBands], fg[kMaxBands];
+};
+
+inline BandFactors band_factors(const Bands &d, bool mb, float out_scale)
+{
+    BandFactors f{1, {1.0f}, {out_scale}, {out_scale}};
+    if (!mb) return f;
+    f.nbands = d.nbands;
+    for (int b = 0; b < d.nbands; ++b) {
+        f.qmul[b] = 2.0f * d.band_scale[b];
+        const double v = (double)d.band_w[b] / (double)d.out_div * (double)out_scale;
+        f.fv[b] = (float)v;
+        f.fg[b] = (float)(v * (double)f.qmul[b]);
+    }
+    return f;
+}
+
 #if defined(__HIPCC__)
 // The box of geometry geo fits the cap floats the planner reserved for it: always (the planner bounds the box from the same
 // coordinates); the kernels return when it does not, uniformly, so that no fill can write past its box.
@@ -121,6 +146,76 @@ __device__ __forceinline__ void brick_x_window(const float px[4], float qmul, in
             xw.d[q][c] = sh ? (c == 0 ? 0.0f : d[q][c - 1]) : (c == 3 ? 0.0f : d[q][c]);
         }
     }
+}
+
+// ---- the column contractions of the separable kernels, dense grids and brick lists alike: the one statement of their
+// arithmetic.  Under a lane's 4 samples lie 4 box columns; a column's z tap k, y tap j lies (k * ey + j) * ex floats behind
+// its first tap.  Per column
+//     z:  Z_j = sum_k wz_k C[k][j],  Z'_j = sum_k dz_k C[k][j]
+//     y:  A = sum_j wy_j Z_j,  B = sum_j dy_j Z_j,  D = sum_j wy_j Z'_j
+// and per sample, with its x weights placed in the window (XWin: Wx, Dx, zero outside its three taps),
+//     x:  value = sum_i Wx_i A_i,  d/dx = sum_i Dx_i A_i,  d/dy = sum_i Wx_i B_i,  d/dz = sum_i Wx_i D_i.
+// Every sum runs in this order, fused: a sample's bits are the same in every kernel that calls these, which is what the
+// brick lists promise of the dense default-tier grids and the bounded curl bricks of the gradient bricks' channel 0.
+//
+// The value (A and the sum over Wx) has one kernel, bricks_sep_kernel, which writes it out from tap3.  The column steps of
+// the gradient (z, y -> A, B, D) and of the curl stay written out, from tap3, in their kernels; only their x steps (grad_x,
+// curl_x) are functions.  The gradient's, as a function of one column, takes either
+// grad3d_grid_sep_kernel<1> from 80 to 81 VGPRs (indexed as here; 95 with the whole 4-column loop inside), 6 waves per SIMD
+// to 5, or, indexed k * (ex * ey) + j * ex (78 VGPRs), the brick lists of five bands 3 % of their time.  The curl's, as one
+// function of the 4-column loop, keeps every kernel's waves but costs curl_bricks_sep_kernel 4 to 6 VGPRs and timed 0.1 to
+// 0.8 % over the parent on the curl and bounded curl brick lists, outside the bound the parent's own two runs allow
+// (profiles/sep_contraction_refactor.txt).
+
+// One tap triple: w_2 c2 + (w_1 c1 + w_0 c0).
+__device__ __forceinline__ float tap3(const float *w, float c0, float c1, float c2)
+{
+    return __builtin_fmaf(w[2], c2, __builtin_fmaf(w[1], c1, w[0] * c0));
+}
+
+// The gradient: a sample's four channels from its Wx (w) and Dx (d) and the columns' A, B and D.
+struct GradSample {
+    float v, gx, gy, gz;
+};
+
+__device__ __forceinline__ GradSample grad_x(const float *w, const float *d, const float *A, const float *B, const float *D)
+{
+    GradSample s{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        s.v = __builtin_fmaf(w[c], A[c], s.v);
+        s.gx = __builtin_fmaf(d[c], A[c], s.gx);
+        s.gy = __builtin_fmaf(w[c], B[c], s.gy);
+        s.gz = __builtin_fmaf(w[c], D[c], s.gz);
+    }
+    return s;
+}
+
+// The curl of the potentials psi0, psi1, psi2 (one box each, of one geometry).  v = (d psi2/dy - d psi1/dz,
+// d psi0/dz - d psi2/dx, d psi1/dx - d psi0/dy) needs two of the three column contractions per potential:
+//     psi0: B, D      psi1: A, D      psi2: A, B  (no Z' at all)
+//     vx = sum_i Wx_i (B2 - D1),  vy = sum_i (Wx_i D0 - Dx_i A2),  vz = sum_i (Dx_i A1 - Wx_i B0)
+// the components accumulated with signs.  P = B2 - D1.  The kernels fill a CurlColumns column by column, one
+// sched_barrier per column (wn_wavelet_curl.hip has its measured numbers); curl_x is the x step.
+struct CurlColumns {
+    float P[4], D0[4], A2[4], A1[4], B0[4];
+};
+
+// acc[component][q] += fg * v_component of sample q (w, d: its Wx, Dx).
+__device__ __forceinline__ void curl_x(const float *w, const float *d, const CurlColumns &cols, float fg, float (&acc)[3][4], int q)
+{
+    float vx = 0.0f, vy = 0.0f, vz = 0.0f;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        vx = __builtin_fmaf(w[c], cols.P[c], vx);
+        vy = __builtin_fmaf(w[c], cols.D0[c], vy);
+        vy = __builtin_fmaf(-d[c], cols.A2[c], vy);
+        vz = __builtin_fmaf(d[c], cols.A1[c], vz);
+        vz = __builtin_fmaf(-w[c], cols.B0[c], vz);
+    }
+    acc[0][q] = __builtin_fmaf(fg, vx, acc[0][q]);
+    acc[1][q] = __builtin_fmaf(fg, vy, acc[1][q]);
+    acc[2][q] = __builtin_fmaf(fg, vz, acc[2][q]);
 }
 
 // Stores a lane's 4 samples of CH channel volumes (vol floats apart) at dst, the first sample's address in channel 0:

@@ -5,9 +5,10 @@
 // A brick is 8 x 8 x 8 samples of the lattice a wn_grid describes, named by a device triple (bx, by, bz); the volume's extents
 // say which bricks are in range.  Here: the entry points' checks after their tile and bands, the volume in bricks and the
 // lattice rounded up to whole bricks (what the separable kernels' regime is checked on), and on the device the in-range
-// decision, a sample's coordinate and the geometry of a band's coefficient box under a brick; and, for the two files of
-// derivative fields, the band factors, the separable regime with its argument setup, and the separable kernels' frame
-// (pair_brick, fill_box, store_slots), templated on the kernel's argument struct.
+// decision, a sample's coordinate and the geometry of a band's coefficient box under a brick; and the separable kernels'
+// one argument struct with its regime check and setup, and their frame (pair_brick, fill_box, store_slots).  Their
+// arithmetic between staging and store is wn_brick.hpp's column contractions.  Each file still states its own box and
+// launch caps (kBoxCap, k*BlockCap) and passes its kBoxCap to brick_sep_args.
 #pragma once
 
 #include "wn_brick.hpp"
@@ -72,36 +73,49 @@ inline int brick_list_plan(const wn_grid *grid, const int32_t *bricks_dev, size_
     return WN_OK;
 }
 
-// A band of the separable derivative-field kernels (wn_wavelet_brick_fields.hip, wn_wavelet_bounded_bricks.hip).
+// ---- the separable kernels of the three files: value, gradient, curl and bounded curl bricks
 struct FieldBand : BrickBand {
-    float fv, fg; // factors of the band's value and of its derivatives: w_b / out_div * out_scale, and that * qmul
+    float fv, fg; // factors of the band's value and of its derivatives (wn::band_factors)
 };
 
-// The regime of the separable derivative-field kernels, checked on the lattice rounded up to whole bricks (plan.gr), and
-// their arguments: the regime of the value bricks' sep_try (wn_wavelet_bricks.hip) -- a tile that is not empty, and in every
-// band a step >= 0 below 1/3 cell with coordinates inside the planners' gate; the box of 8 samples then has at most 6 cells
-// per axis and always fits box_cap.  false: outside the regime, *a is not to be launched on.  Args has the fields of
-// FieldsSepArgs (wn_wavelet_brick_fields.hip); a band keeps `boxes` boxes (the curl: one per potential).
-template <typename Args>
-inline bool field_sep_args(const wn_tile *tile, const BrickListPlan &plan, const int *off9, int boxes, int box_cap, int nbands,
-                           const float *qmul, const float *fv, const float *fg, const int32_t *bricks, size_t n, float *out_dev,
-                           Args *a)
+// What a separable kernel launches on; the bounded curl bricks add their obstacles.
+struct BrickSepArgs {
+    const float *coef; // linear tile
+    int n, nmask;
+    int off[9]; // curl: (x, y, z) of psi0, psi1, psi2, each in [0, n); else 0
+    GridArgs g; // z0 == 0
+    float inv_den;
+    BrickRange range;
+    const int32_t *bricks;
+    size_t count;
+    float *out;
+    int vec4_ok; // out is 16-byte aligned, and with it every slot of every channel
+    FieldBand band[kMaxBands];
+};
+
+// The regime of the separable kernels, checked on the lattice rounded up to whole bricks (plan.gr), and their arguments: a
+// tile that is not empty, and in every band a step >= 0 below 1/3 cell (LatticeStep::two_mids) with coordinates inside the
+// planners' gate; the box of 8 samples then has at most 6 cells per axis and always fits box_cap (the file's kBoxCap).
+// false: outside the regime, *a is not to be launched on.  A band keeps `boxes` boxes (the curl: one per potential, shifted
+// by off9).
+inline bool brick_sep_args(const wn_tile *tile, const BrickListPlan &plan, const int *off9, int boxes, int box_cap,
+                           const BandFactors &f, const int32_t *bricks, size_t n, float *out_dev, BrickSepArgs *a)
 {
-    if (tile->n == 0 || !plan.roundable || nbands < 1 || nbands > kMaxBands) return false;
-    for (int b = 0; b < nbands; ++b) {
+    if (tile->n == 0 || !plan.roundable || f.nbands < 1 || f.nbands > kMaxBands) return false;
+    for (int b = 0; b < f.nbands; ++b) {
         LatticeStep ls;
-        if (!lattice_step(plan.gr, plan.g.octave_scale * qmul[b], false, false, 0.0, &ls) || !ls.two_mids()) return false;
+        if (!lattice_step(plan.gr, plan.g.octave_scale * f.qmul[b], false, false, 0.0, &ls) || !ls.two_mids()) return false;
         if ((ls.extent(kBrickEdge) + 1) * ls.extent(kBrickEdge) * ls.extent(kBrickEdge) > box_cap) return false; // never inside two_mids
-        a->band[b].qmul = qmul[b];
+        a->band[b].qmul = f.qmul[b];
         a->band[b].box_off = b * box_cap * boxes;
         a->band[b].box_cap = box_cap;
-        a->band[b].fv = fv[b];
-        a->band[b].fg = fg[b];
+        a->band[b].fv = f.fv[b];
+        a->band[b].fg = f.fg[b];
     }
     a->coef = tile->dev;
     a->n = tile->n;
     a->nmask = pow2_mask(tile->n);
-    for (int i = 0; i < 9; ++i) a->off[i] = off9[i];
+    for (int i = 0; i < 9; ++i) a->off[i] = off9 ? off9[i] : 0;
     a->g = plan.g;
     a->inv_den = inv_den_of(plan.g.den);
     a->range = plan.range;
@@ -147,11 +161,10 @@ __device__ __forceinline__ void box_geometry(const GridArgs &g, float den, float
     geo[3] += 1;
 }
 
-// ---- the frame of the separable derivative-field kernels: 256 lanes, two bricks per workgroup, 128 lanes per brick.  Args is
-// the kernel's argument struct: bricks, count and range; coef, n and nmask of the linear tile.
-// The brick of this half of the workgroup in pair `pair`: false when the list has ended or the brick is out of range.
-template <typename Args>
-__device__ __forceinline__ bool pair_brick(const Args &a, size_t i, int &bx, int &by, int &bz)
+// ---- the frame of the separable kernels: 256 lanes, two bricks per workgroup, 128 lanes per brick.
+// Brick i of the list, read with the same address in every lane of a wave: false when the list has ended or the brick is
+// out of range.
+__device__ __forceinline__ bool pair_brick(const BrickSepArgs &a, size_t i, int &bx, int &by, int &bz)
 {
     bx = by = bz = 0;
     if (i >= a.count) return false;
@@ -162,9 +175,8 @@ __device__ __forceinline__ bool pair_brick(const Args &a, size_t i, int &bx, int
 }
 
 // bb[k][j][i] = coef[Mod(kz0+k+oz)][Mod(jy0+j+oy)][Mod(ix0+i+ox)]: wn::brick_fill's box, the brick's 128 lanes over the flat
-// box (rows are at most 7 cells).
-template <typename Args>
-__device__ __forceinline__ void fill_box(float *bb, const Args &a, const int geo[6], int ox, int oy, int oz, int l)
+// box (rows are at most 7 cells: brick_fill's row per wave would leave 57 of 64 lanes idle).
+__device__ __forceinline__ void fill_box(float *bb, const BrickSepArgs &a, const int geo[6], int ox, int oy, int oz, int l)
 {
     const int ex = geo[3], exy = geo[3] * geo[4], cells = exy * geo[5];
     for (int c = l; c < cells; c += 128) {

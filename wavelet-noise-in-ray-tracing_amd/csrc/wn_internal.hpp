@@ -154,6 +154,16 @@ struct Bands {
     float band_scale[kMaxBands], band_w[kMaxBands]; // 2^(first_band+b) and w_host[b] of the active bands
     float out_div;
     int apply_div;
+
+    // A multiband call in which no band contributes runs the exact kernels on one band of weight 0: the result,
+    // 0 (/ out_div) * out_scale in every channel, is evaluated on the device.
+    void zero_band_if_none()
+    {
+        if (nbands != 0) return;
+        nbands = 1;
+        band_scale[0] = 1.0f;
+        band_w[0] = 0.0f;
+    }
 };
 inline int multiband_bands(float s, int first_band, int nbands, const float *w_host, float var_per_band, Bands *a)
 {

@@ -7,9 +7,9 @@
 //                                    brick_fields_exact_kernel<.., CURL = true> -- one sample per lane, a brick's 512 samples in
 //                                    consecutive lanes, grid-stride -- around wn::eval3d_curl_bounded_exact /
 //                                    multiband_curl_bounded_exact: the bits of the bounded point lists.  No LDS.
-//   curl_bounded_bricks_sep_kernel<NB>       the default tier: the frame and the column contraction of curl_bricks_sep_kernel,
-//                                    the same fused multiply-adds in the same order, so a far sample has that kernel's bits.
-//                                    The y-z contraction A0 of psi0 beside A1 and A2, and three more x contractions, give the
+//   curl_bounded_bricks_sep_kernel<NB>       the default tier: the frame of curl_bricks_sep_kernel around the same curl
+//                                    contraction (wn_brick.hpp), line for line, so a far sample has that kernel's bits.  The
+//                                    y-z contraction A0 of psi0 beside A1 and A2, and three more x contractions, give the
 //                                    potential values of grad A x Psi with the bits of grad_bricks_sep_kernel's channel 0 on
 //                                    the tile rolled by the potential's offset; the boxes are walked once.
 //
@@ -27,14 +27,12 @@ namespace {
 
 using wn::BrickRange;
 using wn::CurlEval;
-using wn::FieldBand;
 using wn::GridArgs;
 using wn::Obstacles;
 using wn::box_geometry;
 using wn::brick_coord;
 using wn::brick_in_range;
 using wn::fill_box;
-using wn::kMaxBands;
 using wn::pair_brick;
 using wn::store_slots;
 
@@ -85,18 +83,7 @@ constexpr int kBoxCap = 7 * 6 * 6;                 // floats per box, as wn_wave
 constexpr int kFlagBytes = 4 * 4;                   // one int per wave: does the wave hold a sample that is not inside
 constexpr size_t kBoundedSepBlockCap = 256u * 8u;   // workgroups of the pair-stride launch, as curl_bricks_sep_kernel's
 
-struct BoundedSepArgs {
-    const float *coef; // linear tile
-    int n, nmask;
-    int off[9]; // (x, y, z) of psi0, psi1, psi2, each in [0, n)
-    GridArgs g; // z0 == 0
-    float inv_den;
-    BrickRange range;
-    const int32_t *bricks;
-    size_t count;
-    float *out;
-    int vec4_ok; // out is 16-byte aligned, and with it every slot of every component
-    FieldBand band[kMaxBands];
+struct BoundedSepArgs : wn::BrickSepArgs {
     Obstacles o;
 };
 
@@ -171,7 +158,7 @@ __global__ __launch_bounds__(256) void curl_bounded_bricks_sep_kernel(const Boun
             continue;
         }
 
-        // ---- curl_bricks_sep_kernel's contraction per band, bands one after the other; with a near sample in the wave, the
+        // ---- the curl contraction (wn_brick.hpp) per band, bands one after the other; with a near sample in the wave, the
         // potential values beside it
 #pragma unroll
         for (int k = 0; k < 3; ++k)
@@ -191,8 +178,9 @@ __global__ __launch_bounds__(256) void curl_bounded_bricks_sep_kernel(const Boun
             wn::bspline_grad(pz * qm, mz, wz, dz);
             const int ex = geo[3], ey = geo[4];
             const float *base = box[half][b][0] + ((mz - 1 - geo[2]) * ey + (my - 1 - geo[1])) * ex + xw.col;
-            // per window column: P = B2 - D1 (for vx), D0 and A2 (vy), A1 and B0 (vz); A0, A1, A2 for the values
-            float P[4], D0[4], A2[4], A1[4], B0[4], A0[4] = {};
+            float A0[4] = {}; // psi0's A beside A1 and A2 with a near sample in the wave: the three values
+            // per window column (wn_brick.hpp): P = B2 - D1 (for vx), D0 and A2 (vy), A1 and B0 (vz)
+            wn::CurlColumns cols;
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 float zw[3][3], zd[2][3]; // [potential][fy]: Z for all three, Z' for psi0 and psi1
@@ -202,36 +190,23 @@ __global__ __launch_bounds__(256) void curl_bounded_bricks_sep_kernel(const Boun
                     for (int fy = 0; fy < 3; ++fy) {
                         const float *bk = base + k3 * kBoxCap;
                         const float c0 = bk[(0 * ey + fy) * ex + c], c1 = bk[(1 * ey + fy) * ex + c], c2 = bk[(2 * ey + fy) * ex + c];
-                        zw[k3][fy] = __builtin_fmaf(wz[2], c2, __builtin_fmaf(wz[1], c1, wz[0] * c0));
-                        if (k3 < 2) zd[k3][fy] = __builtin_fmaf(dz[2], c2, __builtin_fmaf(dz[1], c1, dz[0] * c0));
+                        zw[k3][fy] = wn::tap3(wz, c0, c1, c2);
+                        if (k3 < 2) zd[k3][fy] = wn::tap3(dz, c0, c1, c2);
                     }
-                B0[c] = __builtin_fmaf(dy[2], zw[0][2], __builtin_fmaf(dy[1], zw[0][1], dy[0] * zw[0][0]));
-                D0[c] = __builtin_fmaf(wy[2], zd[0][2], __builtin_fmaf(wy[1], zd[0][1], wy[0] * zd[0][0]));
-                A1[c] = __builtin_fmaf(wy[2], zw[1][2], __builtin_fmaf(wy[1], zw[1][1], wy[0] * zw[1][0]));
-                const float D1 = __builtin_fmaf(wy[2], zd[1][2], __builtin_fmaf(wy[1], zd[1][1], wy[0] * zd[1][0]));
-                A2[c] = __builtin_fmaf(wy[2], zw[2][2], __builtin_fmaf(wy[1], zw[2][1], wy[0] * zw[2][0]));
-                const float B2 = __builtin_fmaf(dy[2], zw[2][2], __builtin_fmaf(dy[1], zw[2][1], dy[0] * zw[2][0]));
-                P[c] = B2 - D1;
-                if (wave_near) A0[c] = __builtin_fmaf(wy[2], zw[0][2], __builtin_fmaf(wy[1], zw[0][1], wy[0] * zw[0][0]));
+                cols.B0[c] = wn::tap3(dy, zw[0][0], zw[0][1], zw[0][2]);
+                cols.D0[c] = wn::tap3(wy, zd[0][0], zd[0][1], zd[0][2]);
+                cols.A1[c] = wn::tap3(wy, zw[1][0], zw[1][1], zw[1][2]);
+                const float D1 = wn::tap3(wy, zd[1][0], zd[1][1], zd[1][2]);
+                cols.A2[c] = wn::tap3(wy, zw[2][0], zw[2][1], zw[2][2]);
+                const float B2 = wn::tap3(dy, zw[2][0], zw[2][1], zw[2][2]);
+                cols.P[c] = B2 - D1;
+                if (wave_near) A0[c] = wn::tap3(wy, zw[0][0], zw[0][1], zw[0][2]);
                 // one column's 27 LDS reads in flight, not all 108, as in curl_bricks_sep_kernel
                 __builtin_amdgcn_sched_barrier(0);
             }
             const float fg = a.band[b].fg;
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                float vx = 0.0f, vy = 0.0f, vz = 0.0f;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    vx = __builtin_fmaf(xw.w[q][c], P[c], vx);
-                    vy = __builtin_fmaf(xw.w[q][c], D0[c], vy);
-                    vy = __builtin_fmaf(-xw.d[q][c], A2[c], vy);
-                    vz = __builtin_fmaf(xw.d[q][c], A1[c], vz);
-                    vz = __builtin_fmaf(-xw.w[q][c], B0[c], vz);
-                }
-                acc[0][q] = __builtin_fmaf(fg, vx, acc[0][q]);
-                acc[1][q] = __builtin_fmaf(fg, vy, acc[1][q]);
-                acc[2][q] = __builtin_fmaf(fg, vz, acc[2][q]);
-            }
+            for (int q = 0; q < 4; ++q) wn::curl_x(xw.w[q], xw.d[q], cols, fg, acc, q);
             if (wave_near) {
                 // grad_bricks_sep_kernel's channel 0 on the three boxes: the value sum over the window, folded with fv
                 const float fv = a.band[b].fv;
@@ -241,8 +216,8 @@ __global__ __launch_bounds__(256) void curl_bounded_bricks_sep_kernel(const Boun
 #pragma unroll
                     for (int c = 0; c < 4; ++c) {
                         v0 = __builtin_fmaf(xw.w[q][c], A0[c], v0);
-                        v1 = __builtin_fmaf(xw.w[q][c], A1[c], v1);
-                        v2 = __builtin_fmaf(xw.w[q][c], A2[c], v2);
+                        v1 = __builtin_fmaf(xw.w[q][c], cols.A1[c], v1);
+                        v2 = __builtin_fmaf(xw.w[q][c], cols.A2[c], v2);
                     }
                     psi[0][q] = __builtin_fmaf(fv, v0, psi[0][q]);
                     psi[1][q] = __builtin_fmaf(fv, v1, psi[1][q]);
@@ -279,16 +254,16 @@ __global__ __launch_bounds__(256) void curl_bounded_bricks_sep_kernel(const Boun
     }
 }
 
-// Launches the separable kernel when the lattice is in the regime of wn::field_sep_args (wn_brick_list.hpp): exactly the
+// Launches the separable kernel when the lattice is in the regime of wn::brick_sep_args (wn_brick_list.hpp): exactly the
 // unbounded curl bricks' regime.
-int sep_try(const wn_tile *tile, const wn::BrickListPlan &plan, const CurlEval &e, const Obstacles &o, int nbands, const float *qmul,
-            const float *fv, const float *fg, const int32_t *bricks, size_t n, float *out_dev, hipStream_t stream)
+int sep_try(const wn_tile *tile, const wn::BrickListPlan &plan, const CurlEval &e, const Obstacles &o, const wn::BandFactors &f,
+            const int32_t *bricks, size_t n, float *out_dev, hipStream_t stream)
 {
     BoundedSepArgs a{};
-    if (!wn::field_sep_args(tile, plan, e.off, 3, kBoxCap, nbands, qmul, fv, fg, bricks, n, out_dev, &a)) return wn::kDeclined;
+    if (!wn::brick_sep_args(tile, plan, e.off, 3, kBoxCap, f, bricks, n, out_dev, &a)) return wn::kDeclined;
     a.o = o;
     const dim3 blocks(wn::stride_blocks((n + 1) / 2 * 256, kBoundedSepBlockCap)), block(256);
-    wn::brick_dispatch(nbands, [&](auto nb) {
+    wn::brick_dispatch(f.nbands, [&](auto nb) {
         hipLaunchKernelGGL(curl_bounded_bricks_sep_kernel<decltype(nb)::value>, blocks, block, 0, stream, a);
         return WN_OK;
     });
@@ -307,17 +282,9 @@ int bounded_bricks_call(const wn_tile *tile, const wn_grid *grid, const CurlEval
     const GridArgs &g = plan.g;
 
     if (!(grid->flags & WN_GRID_EXACT) && (!e.mb || e.nbands >= 1)) {
-        // band b: q = p * (2 * 2^(first_band+b)); the value factor of the gradient bricks, w_b / out_div * out_scale, and the
-        // curl bricks' derivative factor, that * qmul (wn_wavelet_brick_fields.hip)
-        float qmul[kMaxBands] = {1.0f}, fv[kMaxBands] = {g.out_scale}, fg[kMaxBands] = {g.out_scale};
-        for (int b = 0; e.mb && b < e.nbands; ++b) {
-            qmul[b] = 2.0f * e.band_scale[b];
-            const double f = (double)e.band_w[b] / (double)e.out_div * (double)g.out_scale;
-            fv[b] = (float)f;
-            fg[b] = (float)(f * (double)qmul[b]);
-        }
-        if ((rc = sep_try(tile, plan, e, o, e.mb ? e.nbands : 1, qmul, fv, fg, bricks_dev, n, out_dev, stream)) != wn::kDeclined)
-            return rc;
+        // the value factor of the gradient bricks and the derivative factor of the curl bricks (wn_wavelet_brick_fields.hip)
+        const wn::BandFactors f = wn::band_factors(e, e.mb, g.out_scale);
+        if ((rc = sep_try(tile, plan, e, o, f, bricks_dev, n, out_dev, stream)) != wn::kDeclined) return rc;
     }
     const BoundedExactArgs d{e, o, g, wn::inv_den_of(g.den), plan.range, bricks_dev, n, out_dev};
     const dim3 blocks(wn::stride_blocks(d.count * kSamples, kBoundedExactBlockCap)), block(256);

@@ -10,13 +10,13 @@
 //   grad_bricks_sep_kernel<NB>       the default tier: the frame of bricks_sep_kernel (256 lanes, two bricks per workgroup, 128
 //   curl_bricks_sep_kernel<NB>       lanes per brick, a lane owns 4 consecutive x samples, per brick and band a box of at most
 //                                    7 x 6 x 6 coefficients in static LDS; the curl keeps three, one per potential, each filled
-//                                    from the tile shifted by its offset) around the column contractions of
-//                                    grad3d_grid_sep_kernel (wn_wavelet_grad.hip) and curl3d_grid_sep_kernel
-//                                    (wn_wavelet_curl.hip): z, then y, then x in the 4-column window, the same fused
-//                                    multiply-adds in the same order.  A sample therefore has the bits of the dense default-tier
-//                                    grid wherever that runs its separable kernel (both windows start at multiples of 4), and
-//                                    the gradient's channel 0 has the bits of bricks_sep_kernel.  One float4 per channel and
-//                                    lane: a wave writes 1 KiB contiguous per channel.
+//                                    from the tile shifted by its offset) around the column contractions of wn_brick.hpp,
+//                                    which grad3d_grid_sep_kernel (wn_wavelet_grad.hip), curl3d_grid_sep_kernel
+//                                    (wn_wavelet_curl.hip) and bricks_sep_kernel call too (the gradient's column step is
+//                                    written out in both gradient kernels, line for line).  A sample therefore has the bits of
+//                                    the dense default-tier grid wherever that runs its separable kernel (both windows start at
+//                                    multiples of 4), and the gradient's channel 0 has the bits of bricks_sep_kernel.  One
+//                                    float4 per channel and lane: a wave writes 1 KiB contiguous per channel.
 //
 // All kernels read a brick's triple with the same address in every lane of a wave and decide in-range per brick,
 // wave-uniformly; an out-of-range brick's slots are not touched in any channel.
@@ -29,13 +29,12 @@ namespace {
 
 using wn::BrickRange;
 using wn::CurlEval;
-using wn::FieldBand;
+using wn::BrickSepArgs;
 using wn::GridArgs;
 using wn::box_geometry;
 using wn::brick_coord;
 using wn::brick_in_range;
 using wn::fill_box;
-using wn::kMaxBands;
 using wn::pair_brick;
 using wn::store_slots;
 
@@ -94,22 +93,8 @@ constexpr int kBoxCap = 7 * 6 * 6;              // floats per box, as wn_wavelet
 constexpr size_t kSepBlockCap = 256u * 8u;       // workgroups of the pair-stride launches
 constexpr size_t kCurlExactBlockCap = 256u * 8u; // of the exact curl launch: the cap of curl3d_points_kernel, whose body it runs
 
-struct FieldsSepArgs {
-    const float *coef; // linear tile
-    int n, nmask;
-    int off[9]; // curl: (x, y, z) of psi0, psi1, psi2, each in [0, n)
-    GridArgs g; // z0 == 0
-    float inv_den;
-    BrickRange range;
-    const int32_t *bricks;
-    size_t count;
-    float *out;
-    int vec4_ok; // out is 16-byte aligned, and with it every slot of every channel
-    FieldBand band[kMaxBands];
-};
-
 template <int NB>
-__global__ __launch_bounds__(256) void grad_bricks_sep_kernel(const FieldsSepArgs a)
+__global__ __launch_bounds__(256) void grad_bricks_sep_kernel(const BrickSepArgs a)
 {
     __shared__ float box[2][NB][kBoxCap]; // [brick of the pair][band]: the only LDS
     const GridArgs &g = a.g;
@@ -140,7 +125,8 @@ __global__ __launch_bounds__(256) void grad_bricks_sep_kernel(const FieldsSepArg
         __syncthreads();
         if (!live) continue;
 
-        // ---- this lane's 4 samples: grad3d_grid_sep_kernel's contraction per band, bands one after the other
+        // ---- this lane's 4 samples: the gradient contraction (wn_brick.hpp; its column step exactly as
+        // grad3d_grid_sep_kernel writes it) per band, bands one after the other
         float px[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) px[q] = brick_coord(g, den, a.inv_den, kEdge * bx + x_in + q);
@@ -166,28 +152,21 @@ __global__ __launch_bounds__(256) void grad_bricks_sep_kernel(const FieldsSepArg
 #pragma unroll
                 for (int fy = 0; fy < 3; ++fy) {
                     const float c0 = base[(0 * ey + fy) * ex + c], c1 = base[(1 * ey + fy) * ex + c], c2 = base[(2 * ey + fy) * ex + c];
-                    zw[fy] = __builtin_fmaf(wz[2], c2, __builtin_fmaf(wz[1], c1, wz[0] * c0));
-                    zd[fy] = __builtin_fmaf(dz[2], c2, __builtin_fmaf(dz[1], c1, dz[0] * c0));
+                    zw[fy] = wn::tap3(wz, c0, c1, c2);
+                    zd[fy] = wn::tap3(dz, c0, c1, c2);
                 }
-                A[c] = __builtin_fmaf(wy[2], zw[2], __builtin_fmaf(wy[1], zw[1], wy[0] * zw[0]));
-                B[c] = __builtin_fmaf(dy[2], zw[2], __builtin_fmaf(dy[1], zw[1], dy[0] * zw[0]));
-                D[c] = __builtin_fmaf(wy[2], zd[2], __builtin_fmaf(wy[1], zd[1], wy[0] * zd[0]));
+                A[c] = wn::tap3(wy, zw[0], zw[1], zw[2]);
+                B[c] = wn::tap3(dy, zw[0], zw[1], zw[2]);
+                D[c] = wn::tap3(wy, zd[0], zd[1], zd[2]);
             }
             const float fv = a.band[b].fv, fg = a.band[b].fg;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                float v = 0.0f, gx = 0.0f, gy = 0.0f, gz = 0.0f;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    v = __builtin_fmaf(xw.w[q][c], A[c], v);
-                    gx = __builtin_fmaf(xw.d[q][c], A[c], gx);
-                    gy = __builtin_fmaf(xw.w[q][c], B[c], gy);
-                    gz = __builtin_fmaf(xw.w[q][c], D[c], gz);
-                }
-                acc[0][q] = __builtin_fmaf(fv, v, acc[0][q]);
-                acc[1][q] = __builtin_fmaf(fg, gx, acc[1][q]);
-                acc[2][q] = __builtin_fmaf(fg, gy, acc[2][q]);
-                acc[3][q] = __builtin_fmaf(fg, gz, acc[3][q]);
+                const wn::GradSample s = wn::grad_x(xw.w[q], xw.d[q], A, B, D);
+                acc[0][q] = __builtin_fmaf(fv, s.v, acc[0][q]);
+                acc[1][q] = __builtin_fmaf(fg, s.gx, acc[1][q]);
+                acc[2][q] = __builtin_fmaf(fg, s.gy, acc[2][q]);
+                acc[3][q] = __builtin_fmaf(fg, s.gz, acc[3][q]);
             }
         }
         store_slots(a.out + i * kSamples + 4 * l, a.count * kSamples, a.vec4_ok, acc);
@@ -195,7 +174,7 @@ __global__ __launch_bounds__(256) void grad_bricks_sep_kernel(const FieldsSepArg
 }
 
 template <int NB>
-__global__ __launch_bounds__(256) void curl_bricks_sep_kernel(const FieldsSepArgs a)
+__global__ __launch_bounds__(256) void curl_bricks_sep_kernel(const BrickSepArgs a)
 {
     __shared__ float box[2][NB][3][kBoxCap]; // [brick of the pair][band][potential]: the only LDS
     const GridArgs &g = a.g;
@@ -227,7 +206,7 @@ __global__ __launch_bounds__(256) void curl_bricks_sep_kernel(const FieldsSepArg
         __syncthreads();
         if (!live) continue;
 
-        // ---- this lane's 4 samples: curl3d_grid_sep_kernel's contraction per band, bands one after the other
+        // ---- this lane's 4 samples: the curl contraction (wn_brick.hpp) per band, bands one after the other
         float px[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) px[q] = brick_coord(g, den, a.inv_den, kEdge * bx + x_in + q);
@@ -246,8 +225,8 @@ __global__ __launch_bounds__(256) void curl_bricks_sep_kernel(const FieldsSepArg
             wn::bspline_grad(pz * qm, mz, wz, dz);
             const int ex = geo[3], ey = geo[4];
             const float *base = box[half][b][0] + ((mz - 1 - geo[2]) * ey + (my - 1 - geo[1])) * ex + xw.col;
-            // per window column: P = B2 - D1 (for vx), D0 and A2 (vy), A1 and B0 (vz)
-            float P[4], D0[4], A2[4], A1[4], B0[4];
+            // per window column (wn_brick.hpp): P = B2 - D1 (for vx), D0 and A2 (vy), A1 and B0 (vz)
+            wn::CurlColumns cols;
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 float zw[3][3], zd[2][3]; // [potential][fy]: Z for all three, Z' for psi0 and psi1
@@ -257,50 +236,37 @@ __global__ __launch_bounds__(256) void curl_bricks_sep_kernel(const FieldsSepArg
                     for (int fy = 0; fy < 3; ++fy) {
                         const float *bk = base + k3 * kBoxCap;
                         const float c0 = bk[(0 * ey + fy) * ex + c], c1 = bk[(1 * ey + fy) * ex + c], c2 = bk[(2 * ey + fy) * ex + c];
-                        zw[k3][fy] = __builtin_fmaf(wz[2], c2, __builtin_fmaf(wz[1], c1, wz[0] * c0));
-                        if (k3 < 2) zd[k3][fy] = __builtin_fmaf(dz[2], c2, __builtin_fmaf(dz[1], c1, dz[0] * c0));
+                        zw[k3][fy] = wn::tap3(wz, c0, c1, c2);
+                        if (k3 < 2) zd[k3][fy] = wn::tap3(dz, c0, c1, c2);
                     }
-                B0[c] = __builtin_fmaf(dy[2], zw[0][2], __builtin_fmaf(dy[1], zw[0][1], dy[0] * zw[0][0]));
-                D0[c] = __builtin_fmaf(wy[2], zd[0][2], __builtin_fmaf(wy[1], zd[0][1], wy[0] * zd[0][0]));
-                A1[c] = __builtin_fmaf(wy[2], zw[1][2], __builtin_fmaf(wy[1], zw[1][1], wy[0] * zw[1][0]));
-                const float D1 = __builtin_fmaf(wy[2], zd[1][2], __builtin_fmaf(wy[1], zd[1][1], wy[0] * zd[1][0]));
-                A2[c] = __builtin_fmaf(wy[2], zw[2][2], __builtin_fmaf(wy[1], zw[2][1], wy[0] * zw[2][0]));
-                const float B2 = __builtin_fmaf(dy[2], zw[2][2], __builtin_fmaf(dy[1], zw[2][1], dy[0] * zw[2][0]));
-                P[c] = B2 - D1;
+                cols.B0[c] = wn::tap3(dy, zw[0][0], zw[0][1], zw[0][2]);
+                cols.D0[c] = wn::tap3(wy, zd[0][0], zd[0][1], zd[0][2]);
+                cols.A1[c] = wn::tap3(wy, zw[1][0], zw[1][1], zw[1][2]);
+                const float D1 = wn::tap3(wy, zd[1][0], zd[1][1], zd[1][2]);
+                cols.A2[c] = wn::tap3(wy, zw[2][0], zw[2][1], zw[2][2]);
+                const float B2 = wn::tap3(dy, zw[2][0], zw[2][1], zw[2][2]);
+                cols.P[c] = B2 - D1;
                 // one column's 27 LDS reads in flight, not all 108, as in curl3d_grid_sep_kernel (registers with and without:
                 // profiles/brick_fields_kernels.txt)
                 __builtin_amdgcn_sched_barrier(0);
             }
             const float fg = a.band[b].fg;
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                float vx = 0.0f, vy = 0.0f, vz = 0.0f;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    vx = __builtin_fmaf(xw.w[q][c], P[c], vx);
-                    vy = __builtin_fmaf(xw.w[q][c], D0[c], vy);
-                    vy = __builtin_fmaf(-xw.d[q][c], A2[c], vy);
-                    vz = __builtin_fmaf(xw.d[q][c], A1[c], vz);
-                    vz = __builtin_fmaf(-xw.w[q][c], B0[c], vz);
-                }
-                acc[0][q] = __builtin_fmaf(fg, vx, acc[0][q]);
-                acc[1][q] = __builtin_fmaf(fg, vy, acc[1][q]);
-                acc[2][q] = __builtin_fmaf(fg, vz, acc[2][q]);
-            }
+            for (int q = 0; q < 4; ++q) wn::curl_x(xw.w[q], xw.d[q], cols, fg, acc, q);
         }
         store_slots(a.out + i * kSamples + 4 * l, a.count * kSamples, a.vec4_ok, acc);
     }
 }
 
 // Launches a separable kernel when the lattice, rounded up to whole bricks (plan.gr), is in the regime of
-// wn::field_sep_args (wn_brick_list.hpp): that of the value bricks' sep_try (wn_wavelet_bricks.hip).
-int sep_try(const wn_tile *tile, const wn::BrickListPlan &plan, const CurlEval &e, bool curl, int nbands, const float *qmul,
-            const float *fv, const float *fg, const int32_t *bricks, size_t n, float *out_dev, hipStream_t stream)
+// wn::brick_sep_args (wn_brick_list.hpp).
+int sep_try(const wn_tile *tile, const wn::BrickListPlan &plan, const CurlEval &e, bool curl, const wn::BandFactors &f,
+            const int32_t *bricks, size_t n, float *out_dev, hipStream_t stream)
 {
-    FieldsSepArgs a{};
-    if (!wn::field_sep_args(tile, plan, e.off, curl ? 3 : 1, kBoxCap, nbands, qmul, fv, fg, bricks, n, out_dev, &a)) return wn::kDeclined;
+    BrickSepArgs a{};
+    if (!wn::brick_sep_args(tile, plan, e.off, curl ? 3 : 1, kBoxCap, f, bricks, n, out_dev, &a)) return wn::kDeclined;
     const dim3 blocks(wn::stride_blocks((n + 1) / 2 * 256, kSepBlockCap)), block(256);
-    wn::brick_dispatch(nbands, [&](auto nb) {
+    wn::brick_dispatch(f.nbands, [&](auto nb) {
         if (curl) hipLaunchKernelGGL(curl_bricks_sep_kernel<decltype(nb)::value>, blocks, block, 0, stream, a);
         else hipLaunchKernelGGL(grad_bricks_sep_kernel<decltype(nb)::value>, blocks, block, 0, stream, a);
         return WN_OK;
@@ -330,28 +296,11 @@ int fields_call(const wn_tile *tile, const wn_grid *grid, CurlEval e, bool curl,
     const GridArgs &g = plan.g;
 
     if (!(grid->flags & WN_GRID_EXACT) && (!e.mb || e.nbands >= 1)) {
-        // band b: q = p * (2 * 2^(first_band+b)); value factor w_b / out_div * out_scale, derivative factor that * qmul: as
-        // grad_grid (wn_wavelet_grad.hip) and curl_grid (wn_wavelet_curl.hip) form them
-        float qmul[kMaxBands] = {1.0f}, fv[kMaxBands] = {g.out_scale}, fg[kMaxBands] = {g.out_scale};
-        for (int b = 0; e.mb && b < e.nbands; ++b) {
-            qmul[b] = 2.0f * e.band_scale[b];
-            if (curl) {
-                fg[b] = (float)((double)e.band_w[b] / (double)e.out_div * (double)g.out_scale * (double)qmul[b]);
-            } else {
-                const double f = (double)e.band_w[b] / (double)e.out_div * (double)g.out_scale;
-                fv[b] = (float)f;
-                fg[b] = (float)(f * (double)qmul[b]);
-            }
-        }
-        if ((rc = sep_try(tile, plan, e, curl, e.mb ? e.nbands : 1, qmul, fv, fg, bricks_dev, n, out_dev, stream)) != wn::kDeclined)
-            return rc;
+        // the bands and factors of grad_grid (wn_wavelet_grad.hip) and curl_grid (wn_wavelet_curl.hip)
+        const wn::BandFactors f = wn::band_factors(e, e.mb, g.out_scale);
+        if ((rc = sep_try(tile, plan, e, curl, f, bricks_dev, n, out_dev, stream)) != wn::kDeclined) return rc;
     }
-    if (!curl && e.mb && e.nbands == 0) {
-        // no band contributes: 0 (/ out_div) * out_scale in all four channels, evaluated on the device as grad_grid does
-        e.nbands = 1;
-        e.band_scale[0] = 1.0f;
-        e.band_w[0] = 0.0f;
-    }
+    if (!curl && e.mb) e.zero_band_if_none(); // as grad_grid does
     const FieldsExactArgs d{e, g, wn::inv_den_of(g.den), plan.range, bricks_dev, n, out_dev};
     if (curl) launch_exact<true>(tile, d, stream);
     else launch_exact<false>(tile, d, stream);

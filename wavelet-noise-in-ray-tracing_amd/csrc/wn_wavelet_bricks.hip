@@ -13,26 +13,27 @@
 //                                    (periodic wrap resolved, x fastest: brick_fill's layout) of at most 7 x 6 x 6 floats -- the
 //                                    6^3 cells under 8 samples at a step below 1/3 cell, and the window's fourth column -- is
 //                                    staged in LDS; every lane then contracts the 4 box columns under its samples over z, then
-//                                    y, then x (fused), and the band sum is one FMA per band.  Nothing is summed across samples:
-//                                    a sample's bits depend on its own lattice index, the lattice, the tile and the bands only.
-//                                    A wave's 64 float4 stores are 1 KiB contiguous.
+//                                    y, then x (the value contraction wn_brick.hpp states, from wn::tap3), and the band sum is
+//                                    one FMA per band.  Nothing is summed across samples: a sample's bits depend on its own
+//                                    lattice index, the lattice, the tile and the bands only.  A wave's 64 float4 stores are
+//                                    1 KiB contiguous.
 //
 // Both kernels read a brick's triple with the same address in every lane of a wave and decide in-range per brick, wave-uniformly;
 // an out-of-range brick's slot is not touched.
 //
-// The in-range decision, a sample's coordinate and a box's geometry are wn_brick_list.hpp's, shared with the gradient and curl
-// bricks of wn_wavelet_brick_fields.hip.
+// The in-range decision, a sample's coordinate, a box's geometry and the separable kernel's arguments, regime and frame are
+// wn_brick_list.hpp's, shared with the gradient and curl bricks of wn_wavelet_brick_fields.hip.
 #include "wn_brick_list.hpp"
 #include "wnoise_bricks.h"
 
 namespace {
 
 using wn::BrickRange;
+using wn::BrickSepArgs;
 using wn::GridArgs;
 using wn::box_geometry;
 using wn::brick_coord;
 using wn::brick_in_range;
-using wn::kMaxBands;
 
 constexpr int kEdge = WN_BRICK, kSamples = kEdge * kEdge * kEdge;
 static_assert(kEdge == wn::kBrickEdge && kSamples == wn::kBrickSamples, "wn_brick_list.hpp's brick");
@@ -75,25 +76,8 @@ __global__ __launch_bounds__(256) void bricks_exact_kernel(const BricksExactArgs
 constexpr int kBoxCap = 7 * 6 * 6;        // floats per box: extent(8) <= 6 cells per axis inside two_mids, + the window's fourth column
 constexpr size_t kSepBlockCap = 256u * 8u; // workgroups of the pair-stride launch: 8 per compute unit, 32 waves
 
-struct ListBand : wn::BrickBand {
-    float f; // everything that scales the band: w_b / out_div * out_scale
-};
-
-struct BricksSepArgs {
-    const float *coef; // linear tile
-    int n, nmask;
-    GridArgs g; // z0 == 0
-    float inv_den;
-    BrickRange range;
-    const int32_t *bricks;
-    size_t count;
-    float *out;
-    int vec4_ok; // out is 16-byte aligned, and with it every slot
-    ListBand band[kMaxBands];
-};
-
 template <int NB>
-__global__ __launch_bounds__(256) void bricks_sep_kernel(const BricksSepArgs a)
+__global__ __launch_bounds__(256) void bricks_sep_kernel(const BrickSepArgs a)
 {
     __shared__ float box[2][NB][kBoxCap]; // [brick of the pair][band]: the only LDS
     const GridArgs &g = a.g;
@@ -106,18 +90,9 @@ __global__ __launch_bounds__(256) void bricks_sep_kernel(const BricksSepArgs a)
 
     for (size_t pair = blockIdx.x; pair < pairs; pair += gridDim.x) {
         const size_t i = 2 * pair + half;
-        int bx = 0, by = 0, bz = 0;
-        bool live = i < a.count;
-        if (live) {
-            bx = __builtin_amdgcn_readfirstlane(a.bricks[3 * i]);
-            by = __builtin_amdgcn_readfirstlane(a.bricks[3 * i + 1]);
-            bz = __builtin_amdgcn_readfirstlane(a.bricks[3 * i + 2]);
-            live = brick_in_range(a.range, bx, by, bz);
-        }
+        int bx, by, bz;
+        bool live = wn::pair_brick(a, i, bx, by, bz);
         __syncthreads(); // the previous pair's reads are done: the boxes may be overwritten
-
-        // ---- fill: box[k][j][i] = coef[Mod(kz0+k)][Mod(jy0+j)][Mod(ix0+i)], the brick's 128 lanes over the flat box (rows are
-        // at most 7 cells: brick_fill's row per wave would leave 57 of 64 lanes idle)
         if (live) {
 #pragma unroll
             for (int b = 0; b < NB; ++b) {
@@ -127,14 +102,7 @@ __global__ __launch_bounds__(256) void bricks_sep_kernel(const BricksSepArgs a)
                     live = false;
                     break;
                 }
-                const int ex = geo[3], exy = geo[3] * geo[4], cells = exy * geo[5];
-                float *bb = box[half][b];
-                for (int c = l; c < cells; c += 128) {
-                    const int k = c / exy, r = c - k * exy;
-                    const int j = r / ex, ii = r - j * ex;
-                    bb[c] = a.coef[((size_t)wn::dmod(geo[2] + k, a.n, a.nmask) * a.n + wn::dmod(geo[1] + j, a.n, a.nmask)) * a.n +
-                                   wn::dmod(geo[0] + ii, a.n, a.nmask)];
-                }
+                wn::fill_box(box[half][b], a, geo, 0, 0, 0, l);
             }
         }
         __syncthreads();
@@ -145,7 +113,7 @@ __global__ __launch_bounds__(256) void bricks_sep_kernel(const BricksSepArgs a)
 #pragma unroll
         for (int q = 0; q < 4; ++q) px[q] = brick_coord(g, den, a.inv_den, kEdge * bx + x_in + q);
         const float py = brick_coord(g, den, a.inv_den, kEdge * by + y_in), pz = brick_coord(g, den, a.inv_den, kEdge * bz + z_in);
-        float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        float acc[1][4] = {};
 #pragma unroll 1
         for (int b = 0; b < NB; ++b) {
             const float qm = a.band[b].qmul;
@@ -166,58 +134,32 @@ __global__ __launch_bounds__(256) void bricks_sep_kernel(const BricksSepArgs a)
 #pragma unroll
                 for (int fy = 0; fy < 3; ++fy) {
                     const float c0 = base[(0 * ey + fy) * ex + c], c1 = base[(1 * ey + fy) * ex + c], c2 = base[(2 * ey + fy) * ex + c];
-                    zw[fy] = __builtin_fmaf(wz[2], c2, __builtin_fmaf(wz[1], c1, wz[0] * c0));
+                    zw[fy] = wn::tap3(wz, c0, c1, c2);
                 }
-                A[c] = __builtin_fmaf(wy[2], zw[2], __builtin_fmaf(wy[1], zw[1], wy[0] * zw[0]));
+                A[c] = wn::tap3(wy, zw[0], zw[1], zw[2]);
             }
-            const float f = a.band[b].f;
+            const float fv = a.band[b].fv;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 float v = 0.0f;
 #pragma unroll
                 for (int c = 0; c < 4; ++c) v = __builtin_fmaf(xw.w[q][c], A[c], v);
-                acc[q] = __builtin_fmaf(f, v, acc[q]);
+                acc[0][q] = __builtin_fmaf(fv, v, acc[0][q]);
             }
         }
-        float *dst = a.out + i * kSamples + 4 * l;
-        if (a.vec4_ok) {
-            *reinterpret_cast<v4f *>(dst) = v4f{acc[0], acc[1], acc[2], acc[3]};
-        } else {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) dst[q] = acc[q];
-        }
+        wn::store_slots(a.out + i * kSamples + 4 * l, kSamples, a.vec4_ok, acc);
     }
 }
 
-// Launches the separable kernel when the lattice, rounded up to whole bricks (gr), is in its regime: a tile that is not
-// empty, and in every band a step >= 0 below 1/3 cell (LatticeStep::two_mids) with coordinates inside the planners' gate;
-// the box of 8 samples then has at most 6 cells per axis and always fits.
-int sep_try(const wn_tile *tile, const GridArgs &g, const GridArgs &gr, const BrickRange &range, int nbands, const float *qmul,
-            const float *f, const int32_t *bricks, size_t n, float *out_dev, hipStream_t stream)
+// Launches the separable kernel when the lattice, rounded up to whole bricks (plan.gr), is in the regime of
+// wn::brick_sep_args (wn_brick_list.hpp).
+int sep_try(const wn_tile *tile, const wn::BrickListPlan &plan, const wn::BandFactors &f, const int32_t *bricks, size_t n,
+            float *out_dev, hipStream_t stream)
 {
-    if (tile->n == 0 || nbands < 1 || nbands > kMaxBands) return wn::kDeclined;
-    BricksSepArgs a{};
-    for (int b = 0; b < nbands; ++b) {
-        wn::LatticeStep ls;
-        if (!wn::lattice_step(gr, g.octave_scale * qmul[b], false, false, 0.0, &ls) || !ls.two_mids()) return wn::kDeclined;
-        if ((ls.extent(kEdge) + 1) * ls.extent(kEdge) * ls.extent(kEdge) > kBoxCap) return wn::kDeclined; // never inside two_mids
-        a.band[b].qmul = qmul[b];
-        a.band[b].box_off = b * kBoxCap;
-        a.band[b].box_cap = kBoxCap;
-        a.band[b].f = f[b];
-    }
-    a.coef = tile->dev;
-    a.n = tile->n;
-    a.nmask = wn::pow2_mask(tile->n);
-    a.g = g;
-    a.inv_den = wn::inv_den_of(g.den);
-    a.range = range;
-    a.bricks = bricks;
-    a.count = n;
-    a.out = out_dev;
-    a.vec4_ok = (reinterpret_cast<uintptr_t>(out_dev) & 15) == 0;
+    BrickSepArgs a{};
+    if (!wn::brick_sep_args(tile, plan, nullptr, 1, kBoxCap, f, bricks, n, out_dev, &a)) return wn::kDeclined;
     const size_t pairs = (n + 1) / 2;
-    wn::brick_dispatch(nbands, [&](auto nb) {
+    wn::brick_dispatch(f.nbands, [&](auto nb) {
         hipLaunchKernelGGL(bricks_sep_kernel<decltype(nb)::value>, dim3(wn::stride_blocks(pairs * 256, kSepBlockCap)), dim3(256),
                            0, stream, a);
         return WN_OK;
@@ -238,21 +180,10 @@ int bricks_call(const wn_tile *tile, const wn_grid *grid, BricksExactArgs d, boo
     const BrickRange &range = plan.range;
 
     if (!(grid->flags & WN_GRID_EXACT) && plan.roundable && (!mb || d.nbands >= 1)) {
-        // band b: q = p * (2 * 2^(first_band+b)), factor w_b / out_div * out_scale
-        float qmul[kMaxBands] = {1.0f}, f[kMaxBands] = {g.out_scale};
-        for (int b = 0; mb && b < d.nbands; ++b) {
-            qmul[b] = 2.0f * d.band_scale[b];
-            f[b] = (float)((double)d.band_w[b] / (double)d.out_div * (double)g.out_scale);
-        }
-        if ((rc = sep_try(tile, g, plan.gr, range, mb ? d.nbands : 1, qmul, f, bricks_dev, n, out_dev, stream)) != wn::kDeclined)
-            return rc;
+        const wn::BandFactors f = wn::band_factors(d, mb, g.out_scale);
+        if ((rc = sep_try(tile, plan, f, bricks_dev, n, out_dev, stream)) != wn::kDeclined) return rc;
     }
-    if (mb && d.nbands == 0) {
-        // no band contributes: 0 (/ out_div) * out_scale, evaluated on the device
-        d.nbands = 1;
-        d.band_scale[0] = 1.0f;
-        d.band_w[0] = 0.0f;
-    }
+    if (mb) d.zero_band_if_none();
     d.coef = tile->dev_padded ? tile->dev_padded : tile->dev;
     d.n = tile->n;
     d.nmask = wn::pow2_mask(tile->n);

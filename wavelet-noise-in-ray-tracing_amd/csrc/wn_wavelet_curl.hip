@@ -79,14 +79,11 @@ __global__ __launch_bounds__(256) void curl3d_grid_direct_kernel(const CurlDirec
 // ---- dense grids, default tier: the separable brick kernel ---------------------------------------------------------------
 // The brick frame of wn_brick.hpp.  Per band the workgroup stages THREE boxes, box_k[k][j][i] = coef[Mod(kz0+k+oz_k)]
 // [Mod(jy0+j+oy_k)][Mod(ix0+i+ox_k)], of one geometry (the potentials share the mids), and the lane forms the 4-wide x
-// window (Wx, Dx) once.  Per row, band and potential the lane contracts the 4 box columns under its samples' taps
-//     z:  Z = sum_k wz_k C[k][j][i],  Z' = sum_k dz_k C[k][j][i]
-//     y:  A = sum_j wy_j Z,  B = sum_j dy_j Z,  D = sum_j wy_j Z'
-// and needs only two of the three column contractions per potential:
-//     psi0: B, D      psi1: A, D      psi2: A, B  (no Z' at all)
-//     vx = sum_i Wx_i (B2 - D1),  vy = sum_i (Wx_i D0 - Dx_i A2),  vz = sum_i (Dx_i A1 - Wx_i B0)
-// the components accumulated with signs.  Every sample is summed in the same order from its own weights and coefficients,
-// wherever it sits in a brick: its bits do not depend on how the volume was cut into z-slabs.  Fused (FMA) arithmetic.
+// window (Wx, Dx) once.  Per row and band the lane contracts the 4 box columns under its samples' taps with the curl
+// contraction stated in wn_brick.hpp (two of the three column contractions per potential, written out here from wn::tap3
+// for the reason given there; then wn::curl_x, the components accumulated with signs).  Every sample is summed in the same order from its own weights and
+// coefficients, wherever it sits in a brick: its bits do not depend on how the volume was cut into z-slabs.  Fused (FMA)
+// arithmetic.
 using wn::kGWaves;
 using wn::kGX;
 using wn::kGY;
@@ -181,8 +178,8 @@ __global__ __launch_bounds__(64 * kGWaves) void curl3d_grid_sep_kernel(const Cur
             const int ex = s_geo[b][3], ey = s_geo[b][4];
             const int cap = a.band[b].box_cap;
             const float *base = box + a.band[b].box_off + ((mz - 1 - s_geo[b][2]) * ey + (my - 1 - s_geo[b][1])) * ex + xw.col;
-            // per window column: P = B2 - D1 (for vx), D0 and A2 (vy), A1 and B0 (vz)
-            float P[4], D0[4], A2[4], A1[4], B0[4];
+            // per window column (wn_brick.hpp): P = B2 - D1 (for vx), D0 and A2 (vy), A1 and B0 (vz)
+            wn::CurlColumns cols;
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 float zw[3][3], zd[2][3]; // [potential][fy]: Z for all three, Z' for psi0 and psi1
@@ -192,36 +189,23 @@ __global__ __launch_bounds__(64 * kGWaves) void curl3d_grid_sep_kernel(const Cur
                     for (int fy = 0; fy < 3; ++fy) {
                         const float *bk = base + k3 * cap;
                         const float c0 = bk[(0 * ey + fy) * ex + c], c1 = bk[(1 * ey + fy) * ex + c], c2 = bk[(2 * ey + fy) * ex + c];
-                        zw[k3][fy] = __builtin_fmaf(wz[2], c2, __builtin_fmaf(wz[1], c1, wz[0] * c0));
-                        if (k3 < 2) zd[k3][fy] = __builtin_fmaf(dz[2], c2, __builtin_fmaf(dz[1], c1, dz[0] * c0));
+                        zw[k3][fy] = wn::tap3(wz, c0, c1, c2);
+                        if (k3 < 2) zd[k3][fy] = wn::tap3(dz, c0, c1, c2);
                     }
-                B0[c] = __builtin_fmaf(dy[2], zw[0][2], __builtin_fmaf(dy[1], zw[0][1], dy[0] * zw[0][0]));
-                D0[c] = __builtin_fmaf(wy[2], zd[0][2], __builtin_fmaf(wy[1], zd[0][1], wy[0] * zd[0][0]));
-                A1[c] = __builtin_fmaf(wy[2], zw[1][2], __builtin_fmaf(wy[1], zw[1][1], wy[0] * zw[1][0]));
-                const float D1 = __builtin_fmaf(wy[2], zd[1][2], __builtin_fmaf(wy[1], zd[1][1], wy[0] * zd[1][0]));
-                A2[c] = __builtin_fmaf(wy[2], zw[2][2], __builtin_fmaf(wy[1], zw[2][1], wy[0] * zw[2][0]));
-                const float B2 = __builtin_fmaf(dy[2], zw[2][2], __builtin_fmaf(dy[1], zw[2][1], dy[0] * zw[2][0]));
-                P[c] = B2 - D1;
+                cols.B0[c] = wn::tap3(dy, zw[0][0], zw[0][1], zw[0][2]);
+                cols.D0[c] = wn::tap3(wy, zd[0][0], zd[0][1], zd[0][2]);
+                cols.A1[c] = wn::tap3(wy, zw[1][0], zw[1][1], zw[1][2]);
+                const float D1 = wn::tap3(wy, zd[1][0], zd[1][1], zd[1][2]);
+                cols.A2[c] = wn::tap3(wy, zw[2][0], zw[2][1], zw[2][2]);
+                const float B2 = wn::tap3(dy, zw[2][0], zw[2][1], zw[2][2]);
+                cols.P[c] = B2 - D1;
                 // one column's 27 LDS reads in flight, not all 108: 127 VGPRs (4 waves per SIMD) instead of 170 (2); measured
                 // 597 against 742 us at 512^3 (profiles/curl_kernels.txt)
                 __builtin_amdgcn_sched_barrier(0);
             }
             const float fg = a.band[b].fg;
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                float vx = 0.0f, vy = 0.0f, vz = 0.0f;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    vx = __builtin_fmaf(xw.w[q][c], P[c], vx);
-                    vy = __builtin_fmaf(xw.w[q][c], D0[c], vy);
-                    vy = __builtin_fmaf(-xw.d[q][c], A2[c], vy);
-                    vz = __builtin_fmaf(xw.d[q][c], A1[c], vz);
-                    vz = __builtin_fmaf(-xw.w[q][c], B0[c], vz);
-                }
-                acc[0][q] = __builtin_fmaf(fg, vx, acc[0][q]);
-                acc[1][q] = __builtin_fmaf(fg, vy, acc[1][q]);
-                acc[2][q] = __builtin_fmaf(fg, vz, acc[2][q]);
-            }
+            for (int q = 0; q < 4; ++q) wn::curl_x(xw.w[q], xw.d[q], cols, fg, acc, q);
         }
         float *dst = a.out + ((size_t)(z_first + zi) * g.ny + (y_first + yi)) * g.nx + x0;
         wn::brick_store_row(dst, a.vol, a.vec4_ok, x0, g.nx, acc);
@@ -281,13 +265,8 @@ int curl_grid(const wn_tile *tile, const wn_grid *grid, const CurlEval &e, float
     if (total == 0) return WN_OK;
     if (!out_dev) return wn::fail(WN_ERR_INVALID, "out_dev is NULL");
     if (!(grid->flags & WN_GRID_EXACT) && (!e.mb || e.nbands >= 1)) {
-        // band b: q = p * (2 * 2^(first_band+b)); derivative factor w_b / out_div * out_scale * 2 * 2^(first_band+b)
-        float qmul[kMaxBands] = {1.0f}, fg[kMaxBands] = {g.out_scale};
-        for (int b = 0; e.mb && b < e.nbands; ++b) {
-            qmul[b] = 2.0f * e.band_scale[b];
-            fg[b] = (float)((double)e.band_w[b] / (double)e.out_div * (double)g.out_scale * (double)qmul[b]);
-        }
-        if ((rc = curl_sep_try(tile, g, e.off, e.mb ? e.nbands : 1, qmul, fg, out_dev, stream)) != wn::kDeclined) return rc;
+        const wn::BandFactors f = wn::band_factors(e, e.mb, g.out_scale);
+        if ((rc = curl_sep_try(tile, g, e.off, f.nbands, f.qmul, f.fg, out_dev, stream)) != wn::kDeclined) return rc;
     }
     CurlDirectArgs d{e, out_dev, total, g};
     const dim3 blocks(wn::stride_blocks(total)), block(256);

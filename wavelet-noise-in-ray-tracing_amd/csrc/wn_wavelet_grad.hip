@@ -76,13 +76,10 @@ __global__ __launch_bounds__(256) void grad3d_grid_direct_kernel(const GradDirec
 
 // ---- dense grids, default tier: the separable brick kernel ---------------------------------------------------------------
 // The brick frame of wn_brick.hpp with one coefficient box per band.  Per row and band the lane contracts the 4 box
-// columns under its samples' taps:
-//     z:  Z = sum_k wz_k C[k][j][i],  Z' = sum_k dz_k C[k][j][i]             (2 values per (j, i))
-//     y:  A = sum_j wy_j Z,  B = sum_j dy_j Z,  D = sum_j wy_j Z'           (3 values per column i)
-//     x:  value = sum_i Wx_i A, d/dx = sum_i Dx_i A, d/dy = sum_i Wx_i B, d/dz = sum_i Wx_i D
-// with the x weights of each sample placed in a 4-wide window (Wx, Dx: zero outside its three taps), and stores a float4
-// per channel.  Every sample is summed in the same order from its own weights and coefficients, wherever it sits in a
-// brick: its bits do not depend on how the volume was cut into z-slabs.  Fused (FMA) arithmetic; within 1e-5 scaled.
+// columns under its samples' taps with the gradient contraction stated there (z, then y, written out here from wn::tap3
+// for the reason given there; then wn::grad_x in the 4-wide window), and stores a float4 per channel.  Every sample is
+// summed in the same order from its own weights and coefficients, wherever it sits in a brick: its bits do not depend
+// on how the volume was cut into z-slabs.  Fused (FMA) arithmetic; within 1e-5 scaled.
 using wn::kGWaves;
 using wn::kGX;
 using wn::kGY;
@@ -175,28 +172,21 @@ __global__ __launch_bounds__(64 * kGWaves) void grad3d_grid_sep_kernel(const Gra
 #pragma unroll
                 for (int fy = 0; fy < 3; ++fy) {
                     const float c0 = base[(0 * ey + fy) * ex + c], c1 = base[(1 * ey + fy) * ex + c], c2 = base[(2 * ey + fy) * ex + c];
-                    zw[fy] = __builtin_fmaf(wz[2], c2, __builtin_fmaf(wz[1], c1, wz[0] * c0));
-                    zd[fy] = __builtin_fmaf(dz[2], c2, __builtin_fmaf(dz[1], c1, dz[0] * c0));
+                    zw[fy] = wn::tap3(wz, c0, c1, c2);
+                    zd[fy] = wn::tap3(dz, c0, c1, c2);
                 }
-                A[c] = __builtin_fmaf(wy[2], zw[2], __builtin_fmaf(wy[1], zw[1], wy[0] * zw[0]));
-                B[c] = __builtin_fmaf(dy[2], zw[2], __builtin_fmaf(dy[1], zw[1], dy[0] * zw[0]));
-                D[c] = __builtin_fmaf(wy[2], zd[2], __builtin_fmaf(wy[1], zd[1], wy[0] * zd[0]));
+                A[c] = wn::tap3(wy, zw[0], zw[1], zw[2]);
+                B[c] = wn::tap3(dy, zw[0], zw[1], zw[2]);
+                D[c] = wn::tap3(wy, zd[0], zd[1], zd[2]);
             }
             const float fv = a.band[b].fv, fg = a.band[b].fg;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                float v = 0.0f, gx = 0.0f, gy = 0.0f, gz = 0.0f;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    v = __builtin_fmaf(xw.w[q][c], A[c], v);
-                    gx = __builtin_fmaf(xw.d[q][c], A[c], gx);
-                    gy = __builtin_fmaf(xw.w[q][c], B[c], gy);
-                    gz = __builtin_fmaf(xw.w[q][c], D[c], gz);
-                }
-                acc[0][q] = __builtin_fmaf(fv, v, acc[0][q]);
-                acc[1][q] = __builtin_fmaf(fg, gx, acc[1][q]);
-                acc[2][q] = __builtin_fmaf(fg, gy, acc[2][q]);
-                acc[3][q] = __builtin_fmaf(fg, gz, acc[3][q]);
+                const wn::GradSample s = wn::grad_x(xw.w[q], xw.d[q], A, B, D);
+                acc[0][q] = __builtin_fmaf(fv, s.v, acc[0][q]);
+                acc[1][q] = __builtin_fmaf(fg, s.gx, acc[1][q]);
+                acc[2][q] = __builtin_fmaf(fg, s.gy, acc[2][q]);
+                acc[3][q] = __builtin_fmaf(fg, s.gz, acc[3][q]);
             }
         }
         float *dst = a.out + ((size_t)(z_first + zi) * g.ny + (y_first + yi)) * g.nx + x0;
@@ -238,22 +228,10 @@ int grad_grid(const wn_tile *tile, const wn_grid *grid, GradDirectArgs d, bool m
     if (d.vol == 0) return WN_OK;
     if (!out_dev) return wn::fail(WN_ERR_INVALID, "out_dev is NULL");
     if (!(grid->flags & WN_GRID_EXACT) && (!mb || d.nbands >= 1)) {
-        // band b: q = p * (2 * 2^(first_band+b)); value factor w_b / out_div * out_scale, gradient factor that * 2 * 2^(..)
-        float qmul[kMaxBands] = {1.0f}, fv[kMaxBands] = {g.out_scale}, fg[kMaxBands] = {g.out_scale};
-        for (int b = 0; mb && b < d.nbands; ++b) {
-            qmul[b] = 2.0f * d.band_scale[b];
-            const double f = (double)d.band_w[b] / (double)d.out_div * (double)g.out_scale;
-            fv[b] = (float)f;
-            fg[b] = (float)(f * (double)qmul[b]);
-        }
-        if ((rc = grad_sep_try(tile, g, mb ? d.nbands : 1, qmul, fv, fg, out_dev, stream)) != wn::kDeclined) return rc;
+        const wn::BandFactors f = wn::band_factors(d, mb, g.out_scale);
+        if ((rc = grad_sep_try(tile, g, f.nbands, f.qmul, f.fv, f.fg, out_dev, stream)) != wn::kDeclined) return rc;
     }
-    if (mb && d.nbands == 0) {
-        // no band contributes: 0 (/ out_div) * out_scale in all four channels, evaluated on the device
-        d.nbands = 1;
-        d.band_scale[0] = 1.0f;
-        d.band_w[0] = 0.0f;
-    }
+    if (mb) d.zero_band_if_none();
     d.coef = tile->dev_padded ? tile->dev_padded : tile->dev;
     d.out = out_dev;
     d.n = tile->n;

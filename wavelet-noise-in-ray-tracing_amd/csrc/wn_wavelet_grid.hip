@@ -808,12 +808,7 @@ int wn_multiband3d_grid(const wn_tile *tile, const wn_grid *grid, float s, int f
             return rc;
         if ((rc = sep_try(tile, gb, d.nbands, oscale, d.band_w, d.out_div, out_dev, as_stream(stream))) != kDeclined) return rc;
     }
-    if (d.nbands == 0) {
-        // no band contributes: result = 0 (/ out_div) * out_scale, evaluated on the device
-        d.nbands = 1;
-        d.band_scale[0] = 1.0f;
-        d.band_w[0] = 0.0f;
-    }
+    d.zero_band_if_none();
     launch_direct(d, tile, total, as_stream(stream));
     WN_LAUNCH_CHECK("grid3d_direct_kernel(multiband)");
     return WN_OK;
