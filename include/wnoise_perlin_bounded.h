@@ -45,7 +45,7 @@
  * Names: the suffix says what the points are, _f64 for packed doubles (NOISE potentials only, as wn_perlin_curl_points) and
  * _f32 for packed floats with `kind` and `depth` (as wn_perlin_curl_points_vec3).
  *
- * Not provided: dense grids and brick lists; a background stream; moving obstacles and potentials that change with time;
+ * Not provided: dense grids (brick lists: wnoise_perlin_bounded_bricks.h); a background stream; moving obstacles and potentials that change with time;
  * Bridson's variant that keeps the normal component of Psi.
  */
 #ifndef WNOISE_PERLIN_BOUNDED_H

@@ -49,8 +49,8 @@
  * The calls only enqueue on `stream`: no allocation, no synchronisation, no launch on the null stream, no host read of the
  * list.  They can be captured into a graph and replayed on other lists in the same buffers.
  *
- * Not provided: solid boundaries on the curl bricks (wnoise_perlin_bounded.h's obstacles); footprints; brick edges other
- * than 8.
+ * Not provided: solid boundaries on the curl bricks (wnoise_perlin_bounded.h's obstacles) in this header: they are
+ * wnoise_perlin_bounded_bricks.h's wn_perlin_curl_bounded_bricks; footprints; brick edges other than 8.
  */
 #ifndef WNOISE_PERLIN_BRICKS_H
 #define WNOISE_PERLIN_BRICKS_H

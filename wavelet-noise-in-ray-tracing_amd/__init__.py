@@ -32,7 +32,7 @@ from .noise import (  # noqa: E402
     wavelet_gradient_bricks, multiband_gradient_bricks, curl_bricks, multiband_curl_bricks,
     curl_bounded_bricks, multiband_curl_bounded_bricks,
     perlin_bricks, turb_bricks, fractal_bricks, perlin_gradient_bricks, turb_gradient_bricks, fractal_gradient_bricks,
-    perlin_curl_bricks,
+    perlin_curl_bricks, perlin_curl_bounded_bricks,
 )
 from .shard import slab_bounds, gather_volume, NativeComm  # noqa: E402
 from . import formats  # noqa: E402
@@ -53,6 +53,7 @@ __all__ = [
     "multiband_curl_volume", "perlin_curl_volume", "wavelet_bricks", "multiband_bricks",
     "wavelet_gradient_bricks", "multiband_gradient_bricks", "curl_bricks", "multiband_curl_bricks",
     "curl_bounded_bricks", "multiband_curl_bounded_bricks", "perlin_bricks", "turb_bricks", "fractal_bricks",
-    "perlin_gradient_bricks", "turb_gradient_bricks", "fractal_gradient_bricks", "perlin_curl_bricks", "slab_bounds",
+    "perlin_gradient_bricks", "turb_gradient_bricks", "fractal_gradient_bricks", "perlin_curl_bricks", "perlin_curl_bounded_bricks",
+    "slab_bounds",
     "gather_volume", "NativeComm", "formats",
 ]

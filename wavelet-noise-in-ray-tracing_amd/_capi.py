@@ -1,7 +1,8 @@
 """ctypes binding of libwnoise_hip.so (include/wnoise.h, include/wnoise_perlin_curl.h, include/wnoise_footprint.h,
 include/wnoise_perlin_footprint.h, include/wnoise_multiband2d.h, include/wnoise_advect.h, include/wnoise_bounded.h,
 include/wnoise_perlin_advect.h, include/wnoise_curl2d.h, include/wnoise_bounded2d.h, include/wnoise_bricks.h,
-include/wnoise_brick_fields.h, include/wnoise_bounded_bricks.h, include/wnoise_perlin_bounded.h).
+include/wnoise_brick_fields.h, include/wnoise_bounded_bricks.h, include/wnoise_perlin_bounded.h,
+include/wnoise_perlin_bounded_bricks.h).
 
 The library is the product: if it is missing or fails to load this module raises, it never
 substitutes a CPU implementation.
@@ -227,6 +228,12 @@ SIGNATURES_PERLIN_BOUNDED = {
     "wn_perlin_bounded_advect_launch_steps": (_i, [_i, _i, _i, _i]),
 }
 
+# name -> (restype, argtypes); every symbol include/wnoise_perlin_bounded_bricks.h declares.
+SIGNATURES_PERLIN_BOUNDED_BRICKS = {
+    # perm, grid, kind, depth, offsets9, obstacles, nobs, bricks, n, out, stream
+    "wn_perlin_curl_bounded_bricks": (_i, [_vp, _gp, _i, _i, _i32p, _op, _i, _vp, _sz, _vp, _vp]),
+}
+
 # name -> (restype, argtypes); every symbol include/wnoise_curl2d.h declares, and its wn_advect2d.
 class wn_advect2d(C.Structure):
     _fields_ = [("method", C.c_int32), ("steps", C.c_int32), ("h", C.c_float), ("gain", C.c_float),
@@ -300,7 +307,8 @@ def load():
                               *ADVECT_SIGNATURES.items(), *BOUNDED_SIGNATURES.items(), *PERLIN_ADVECT_SIGNATURES.items(),
                               *CURL2D_SIGNATURES.items(), *BOUNDED2D_SIGNATURES.items(), *BRICKS_SIGNATURES.items(),
                               *BRICK_FIELDS_SIGNATURES.items(), *BOUNDED_BRICKS_SIGNATURES.items(),
-                              *SIGNATURES_PERLIN_BOUNDED.items(), *SIGNATURES_PERLIN_BRICKS.items()):
+                              *SIGNATURES_PERLIN_BOUNDED.items(), *SIGNATURES_PERLIN_BRICKS.items(),
+                              *SIGNATURES_PERLIN_BOUNDED_BRICKS.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

@@ -18,36 +18,30 @@
 //   * the running sums of a lane's 8 samples live in registers (1, 4 or 6 sums per sample: value, gradient, curl) in the
 //     reference's accumulation order, unfused; the 8 samples are unrolled inside the rolled loop over cells, so the sums
 //     are indexed at compile time.
+// The field enumerators and the axis slice are wn_perlin_brick_walk.hpp's.  That header also states the walk below (octave
+// tabulation, segment loop, per-potential body) as a function template for wn_perlin_bounded_bricks.hip; this file keeps its
+// own text of it, because calling the function from here changes the nine kernels' register allocation and schedule
+// (profiles/perlin_bounded_bricks_kernels.txt).  A change to one text is a change to both:
+// tests/test_perlin_bounded_bricks_host.py compares them.
 // LDS: the permutation table of the workgroup and one axis slice per wave (kPermBytes, kSliceBytes below).  Evaluators,
 // hashes, corner constants and lerps are those of wn_perlin_frame.hpp / wn_perlin_run.hpp / wn_eval.hpp: fp64, contraction
 // off, the bits of the dense grids and of the point entries.
-#include "wn_perlin_frame.hpp"
-#include "wn_brick_list.hpp"
+#include "wn_perlin_brick_walk.hpp"
 #include "wnoise_perlin_bricks.h"
-
-#include <type_traits>
 
 namespace {
 
 using wn::GridArgs, wn::BrickRange, wn::kNoise, wn::kTurb, wn::kFractal, wn::kBrickEdge, wn::kBrickSamples;
-using wn::RunAxisEntryD;
+using wn::RunAxisEntryD, wn::BrickAxisSlice, wn::kValue, wn::kGrad, wn::kCurl, wn::field_sums, wn::field_potentials;
 static_assert(WN_PERLIN_CURL_NOISE == kNoise && WN_PERLIN_CURL_TURB == kTurb && WN_PERLIN_CURL_FRACTAL == kFractal,
               "the public kinds are the kernels' kinds");
 
-enum { kValue = 0, kGrad = 1, kCurl = 2 };                                                     // the field of a call
 constexpr int field_channels(int field) { return field == kValue ? 1 : (field == kGrad ? 4 : 3); }
-constexpr int field_sums(int field) { return field == kValue ? 1 : (field == kGrad ? 4 : 6); } // running sums per sample
-constexpr int field_potentials(int field) { return field == kCurl ? 3 : 1; }
 
 constexpr int kWaves = 4;                   // bricks (waves) per workgroup: they share the permutation table
-constexpr int kAxisEntries = 3 * kBrickEdge; // x, y, z indices of a brick
+constexpr int kAxisEntries = wn::kBrickAxisEntries;
 constexpr size_t kBrickBlockCap = 256u * 8u; // workgroups of the brick-stride launch
 
-// A wave's axis tables of one octave: entries 0..7 x, 8..15 y, 16..23 z.
-struct BrickAxisSlice {
-    RunAxisEntryD e[kAxisEntries];
-    uint8_t cell[kAxisEntries];
-};
 constexpr int kPermBytes = 512;
 constexpr int kSliceBytes = 600; // 24 x {f, fade, fade'} + 24 cell bytes
 static_assert(sizeof(BrickAxisSlice) == kSliceBytes && kSliceBytes % 8 == 0, "the slice as stated");
@@ -239,7 +233,6 @@ int perlin_bricks(const wn_perm *perm, const wn_grid *grid, int field, int kind,
     if (rc) return rc;
     GridArgs checked;
     if ((rc = wn::check_grid(grid, true, &checked)) != WN_OK) return rc;
-    if (field == kCurl && !offsets9_host) return wn::fail(WN_ERR_INVALID, "offsets9_host is NULL");
     wn::BrickListPlan plan;
     bool launch;
     rc = wn::brick_list_plan(grid, bricks_dev, n, field_channels(field), out_dev, &plan, &launch);
@@ -311,9 +304,9 @@ int wn_perlin_curl_bricks(const wn_perm *perm, const wn_grid *g, int kind, int d
                           const int32_t *bricks_dev, size_t n, float *out_dev, void *stream)
 {
     WN_ENTRY();
-    if (kind < kNoise || kind > kFractal) return wn::fail(WN_ERR_INVALID, "kind must be 0 (noise), 1 (turb) or 2 (fractal_noise)");
-    if (kind == kTurb)
-        if (const int rc = check_depth(depth)) return rc;
+    // kind, depth, table, grid and offsets, stated once for this call and wn_perlin_curl_bounded_bricks; perlin_bricks looks
+    // at the table and the grid again
+    if (const int rc = wn::perlin_curl_bricks_checks(perm, g, kind, depth, offsets9_host)) return rc;
     return perlin_bricks(perm, g, kCurl, kind, depth, offsets9_host, bricks_dev, n, out_dev, stream, "perlin curl grid");
 }
 

@@ -17,6 +17,7 @@
 #include "wnoise_brick_fields.h"
 #include "wnoise_bricks.h"
 #include "wnoise_multiband2d.h"
+#include "wnoise_perlin_bounded_bricks.h"
 #include "wnoise_perlin_bricks.h"
 
 namespace wnhost {
@@ -320,4 +321,22 @@ inline void perlinCurlBricks(const Perlin &perlin, int den, const int32_t *brick
     wnhost::check(wn_perlin_curl_bricks(perlin.perm(), &g, kind, depth, reinterpret_cast<const int32_t *>(offsets9 ? offsets9 : def),
                                         bricks_dev, n, out_dev, stream),
                   "wn_perlin_curl_bricks");
+}
+
+// ---- Perlin curl brick lists with solid boundaries (include/wnoise_perlin_bounded_bricks.h; absent from the reference) --
+// perlinCurlBricks with the potential faded to zero towards the nobs obstacles of include/wnoise_bounded.h, which live in the
+// coordinate noise() / turb() / fractal_noise() receives: the sample's p.  nobs == 0 gives the unbounded bits.
+template <class Perlin>
+inline void perlinCurlBoundedBricks(const Perlin &perlin, int den, const int32_t *bricks_dev, size_t n, int octave,
+                                    const wn_obstacle *obstacles, int nobs, float *out_dev, int kind = WN_PERLIN_CURL_NOISE,
+                                    int depth = 7, const int *offsets9 = nullptr, const int *bounds = nullptr,
+                                    void *stream = nullptr)
+{
+    static_assert(sizeof(int) == sizeof(int32_t), "offsets are int32");
+    static const int def[9] = {0, 0, 0, 85, 85, 85, 170, 170, 170};
+    const wn_grid g = wnhost::perlin_brick_lattice(den, bounds, octave);
+    wnhost::check(wn_perlin_curl_bounded_bricks(perlin.perm(), &g, kind, depth,
+                                                reinterpret_cast<const int32_t *>(offsets9 ? offsets9 : def), obstacles, nobs,
+                                                bricks_dev, n, out_dev, stream),
+                  "wn_perlin_curl_bounded_bricks");
 }

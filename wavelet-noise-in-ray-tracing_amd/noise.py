@@ -1503,3 +1503,16 @@ def perlin_curl_bricks(perlin_obj, den, bricks, octave, kind="noise", depth=7, o
     (3, n, 8, 8, 8) -- vx, vy, vz as out[component][i][z][y][x]."""
     return _perlin_bricks(_lib.wn_perlin_curl_bricks, perlin_obj, den, bricks, octave, bounds, out, 3,
                           _PERLIN_CURL_KINDS[kind], int(depth), perlin._curl_offsets(offsets))
+
+
+# ---- Perlin curl brick lists with solid boundaries (include/wnoise_perlin_bounded_bricks.h) ---------------
+def perlin_curl_bounded_bricks(perlin_obj, den, bricks, octave, obstacles, kind="noise", depth=7, offsets=None, bounds=None,
+                               out=None):
+    """perlin_curl_bricks with its potential faded to zero towards every solid of `obstacles`
+    (wn_perlin_curl_bounded_bricks): (3, n, 8, 8, 8).  `obstacles` as perlin.noise_curl_bounded takes them, in the samples'
+    coordinates p = (i / den) * 4 * 2^octave; a sample inside a solid gets 0, one at distance >= d0 from all of them (and
+    obstacles=[]) the bits of perlin_curl_bricks, every other sample (float) of perlin.noise_curl_bounded /
+    turb_curl_bounded / fractal_noise_curl_bounded at its float coordinates."""
+    obs, nobs = WaveletNoise._obstacles(obstacles)
+    return _perlin_bricks(_lib.wn_perlin_curl_bounded_bricks, perlin_obj, den, bricks, octave, bounds, out, 3,
+                          _PERLIN_CURL_KINDS[kind], int(depth), perlin._curl_offsets(offsets), obs, nobs)
